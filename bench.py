@@ -6,12 +6,17 @@ updates, in-kernel Philox noise) on a per-GPU batch of (B,3,16,64,64) clips alre
 HBM.  N > 1 ranks (launched by torch.distributed.run) shard the global batch B*N data-parallel
 and all-reduce gradients over RCCL; scaling is weak (per-GPU batch fixed).
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps iterations, writes
+the last iteration's outputs if --dump-outputs DIR is given, and prints the line.  With --full the
+line carries besides the contract fields
   roofline     : the VideoDiscriminator Conv3d implicit-GEMM kernels (78 % of the step's FLOPs):
                  algorithmic FLOPs per step / summed launch durations measured with HIP events on
-                 the launch stream during the timed steps, against the fp32 MFMA peak;
+                 the launch stream during an instrumented one-stream pass of --steps iterations,
+                 against the fp32 MFMA peak;
   cpu_baseline : the NumPy restatement of the Chainer-CPU algorithm (oracle/, im2col + BLAS, fp32)
-                 timed on this host's cores on a bounded sample of the same workload.
+                 timed on this host's cores on a bounded sample of the same workload;
+  secondary    : the other workloads BASELINE.json names, a few steps each;
+and the detailed record goes to bench_detail.json.
 """
 import argparse
 import json
@@ -94,6 +99,120 @@ def pmc_traffic(batch, dtype='f32'):
         except Exception:
             continue
     return None, None
+
+
+def roofline_fields(dtype, B, steps, overlap, timing, dt_serial_instr):
+    """`roofline` of a result line (--full): the D_V conv family's algorithmic FLOPs over the launch durations that the
+    instrumented one-stream pass of `steps` iterations recorded (`timing`, hiplib.timing_end()), against the MFMA peak."""
+    tot, f_fwd, f_wg, f_dg = dv_conv_flops_per_step(B)
+    dv_ms = {k: timing.get('D_V.' + k, (0, 0.0)) for k in ('fprop', 'wgrad', 'dgrad')}
+    dv_split_ms = timing.get('D_V.split', (0, 0.0))[1] / steps      # 'f32x3': the passes that split the GEMM operands count as GEMM time
+    dv_total_ms = sum(v[1] for v in dv_ms.values()) / steps + dv_split_ms
+    achieved = tot / (dv_total_ms * 1e-3) / 1e12 if dv_total_ms > 0 else 0.0
+    kern = {}
+    for k, fl in (('fprop', f_fwd), ('wgrad', f_wg), ('dgrad', f_dg)):
+        n_l, ms = dv_ms[k]
+        kern[k] = {"launches_per_step": n_l / steps, "ms_per_step": ms / steps,
+                   "tflops": fl / (ms / steps * 1e-3) / 1e12 if ms > 0 else 0.0}
+    all_conv_ms = sum(v[1] for k, v in timing.items() if ' N=' not in k) / steps
+    by_layer = {}
+    for k, (n_l, ms) in sorted(timing.items()):
+        if ' N=' not in k:
+            continue
+        f = dict(kv.split('=') for kv in k.split()[1:])
+        N_, T_, H_, Ci_, Co_ = (int(f[x]) for x in ('N', 'T', 'H', 'Ci', 'Co'))
+        kt_ = 4 if T_ > 1 else 1
+        gflop = 2.0 * N_ * (T_ - kt_ + 1) * (H_ // 2) ** 2 * kt_ * 16 * min(Ci_, 3 if Ci_ == 4 else Ci_) * Co_ / 1e9
+        by_layer[k] = {"launches_per_step": n_l / steps, "ms_per_launch": ms / n_l,
+                       "tflops": gflop * n_l / ms if ms > 0 else 0.0}
+    traffic, traffic_src = pmc_traffic(B, dtype)
+    # f32x3 executes six bf16 MFMA products per algorithmic fp32 product: its roof in ALGORITHMIC TFLOP/s is the dense bf16 peak / 6
+    peak = PEAK_BF16_MFMA_TFLOPS if dtype == 'bf16' else PEAK_F32X3_TFLOPS if dtype == 'f32x3' else PEAK_FP32_MFMA_TFLOPS
+    return {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+            "frac": achieved / peak, "dv_conv3d_mfma_util_pct": 100.0 * achieved / peak, "traffic": traffic,
+            "algorithmic_bytes": dv_conv_algorithmic_bytes_per_step(B, dtype),
+            "traffic_unit": "bytes per step (memory side of L2, incl. Infinity-Cache hits)",
+            "traffic_source": traffic_src,
+            "traffic_measured_in_run": False,      # PMC counters need rocprofv3 around the process: see traffic_source
+            "kernel": "VideoDiscriminator Conv3d implicit-GEMM family (%s<FpropP|DgradP|WgradP>), "
+                      % ("gemm_kernel" if dtype == 'f32' else "gemm_bf16_v2_kernel SPLIT / gemm_kernel" if dtype == 'f32x3' else "gemm_bf16_kernel") +
+                      "dc1..dc4, all launches of one step",
+            "algorithmic_gflop_per_step": tot / 1e9, "kernel_ms_per_step": dv_total_ms, "by_pass": kern,
+            **({"operand_split_ms_per_step": dv_split_ms,
+                "note": "fp32 products on the bf16 matrix pipe: operands as three bf16 terms, six bf16 MFMA products per "
+                        "fp32 product (DESIGN.md); `peak` = dense bf16 MFMA peak / 6 in algorithmic TFLOP/s",
+                "x_fp32_mfma_peak": achieved / PEAK_FP32_MFMA_TFLOPS} if dtype == 'f32x3' else {}),
+            "all_conv_kernels_ms_per_step": all_conv_ms,
+            "by_network_and_pass_ms_per_step": {k: v[1] / steps for k, v in sorted(timing.items()) if ' N=' not in k},
+            "by_layer": by_layer,
+            "measured": "HIP events around every launch of the family during %d one-stream iterations "
+                        "(%.3f ms/step with the event records); the headline pass %s"
+                        % (steps, dt_serial_instr / steps * 1e3,
+                           "overlaps independent kernels on side streams, which stretches individual launches"
+                           if overlap else "is one-stream too"),
+            "dv_conv_share_of_step_time": dv_total_ms / (dt_serial_instr / steps * 1e3)}
+
+
+DUMP_LIMIT = 64 << 20                  # bytes of all --dump-outputs files together
+DUMP_CLIP_ELEMS = 8 << 20              # x_fake: whole up to this many values (batch 32: 6.3 M), a seeded sample beyond
+DUMP_PARAM_ELEMS = 1 << 17             # per parameter array: whole up to this many values, a seeded sample beyond
+
+
+def _dump_sample(a, n, seed):
+    """`a` flattened when it holds at most n values, else n of its values at fixed seeded positions (ascending)."""
+    import numpy as np
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.size <= n:
+        return a
+    idx = np.sort(np.random.RandomState(seed).randint(0, a.size, n))
+    return a[idx]
+
+
+def net_state(net):
+    """A copy of what an iteration reads from and advances in a network: parameters, Adam moments and step count,
+    BatchNorm running statistics and counts."""
+    return (net.fp.p.clone(), net.fp.m.clone(), net.fp.v.clone(), {k: v.clone() for k, v in net.running.items()},
+            dict(net.bn_count), net.t)
+
+
+def load_net_state(net, state):
+    """net_state()'s copy back into the network; the derived weight forms (bf16 copy, 'f32x3' split filters) follow."""
+    p, m, v, running, count, t = state
+    net.fp.p.copy_(p), net.fp.m.copy_(m), net.fp.v.copy_(v)
+    for k, x in running.items():
+        net.running[k].copy_(x)
+    net.bn_count.update(count)
+    net.t = t
+    net.fp.touch()                                  # (the split filters are rebuilt from p at their next use)
+    if net.fp.p16 is not None:
+        net.fp.refresh16()
+
+
+def dump_outputs(directory, ts, res):
+    """--dump-outputs: what the last timed iteration handed its caller -- the three losses, the generated clips x_fake
+    (N,C,T,H,W), the discriminators' logits and the updated parameters of the three networks in the reference layout --
+    as DIR/<name>.npy, float32 (losses float64).  Arrays larger than the caps above are written as fixed seeded samples.
+    That last step starts from the seeded initial state of the networks (measure() restores it), so two runs agree to
+    rounding: carried over a trajectory, the order of the kernels' float-atomic sums would make them drift apart."""
+    import numpy as np
+    import mocogan_chainer_amd.layout as lay
+    os.makedirs(directory, exist_ok=True)
+    arrays = {'losses': np.array([v for _, v in sorted(ts.losses().items())], dtype=np.float64)}
+    x_fake = lay.act_from_dev(res['x_fake'], ts.gen.out_channels).float().cpu().numpy()
+    arrays['x_fake'] = x_fake if x_fake.size <= DUMP_CLIP_ELEMS else _dump_sample(x_fake, DUMP_CLIP_ELEMS, 1)
+    for k in ('y_real_i', 'y_real_v', 'y_fake_i', 'y_fake_v'):
+        arrays[k] = res[k].float().cpu().numpy()
+    for seed, (tag, net) in enumerate((('gen', ts.gen), ('dis_i', ts.dis_i), ('dis_v', ts.dis_v)), 2):
+        for k, v in sorted(net.export_reference_params().items()):
+            if v.dtype.kind == 'f':
+                name = 'param.%s.%s' % (tag, k.replace('/', '.'))
+                arrays[name] = _dump_sample(v.astype(np.float32), DUMP_PARAM_ELEMS, seed) if v.size > DUMP_PARAM_ELEMS else v.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit('bench.py --dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def _cpu_time_shape(channels, dim_zl, batch, warmup, steps):
@@ -214,8 +333,9 @@ def compact_line(out, secondary, cpu, detail_path):
     cfg = out.get("config") or {}
     line["config"] = {k: cfg[k] for k in ("workload", "variant", "per_gpu_batch", "global_batch", "parallelism", "side_streams", "sync_bn",
                                           "input_ready_early") if k in cfg}
-    line["roofline"] = {k: _round(rl[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "kernel", "kernel_ms_per_step", "traffic",
-                                                   "algorithmic_bytes", "traffic_source", "algorithmic_gflop_per_step") if k in rl}
+    if rl:                                           # (measured with --full only)
+        line["roofline"] = {k: _round(rl[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "kernel", "kernel_ms_per_step", "traffic",
+                                                       "algorithmic_bytes", "traffic_source", "algorithmic_gflop_per_step") if k in rl}
     if "by_pass" in rl:
         line["roofline"]["tflops_by_pass"] = {k: _round(v["tflops"], 1) for k, v in rl["by_pass"].items()}
     if cpu is not None:
@@ -276,7 +396,7 @@ def main():
                          "bf16 terms, six bf16 products per fp32 product, fp32 accumulate: fp32 results, held to the fp32 tolerances by "
                          "the same tests); f32 = the same iteration on the fp32 MFMA (first secondary line); bf16 = configs[2] (use with "
                          "--batch 256), fp32 accumulation / parameters / Adam")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--autotune', type=int, default=1,
                     help='1 (default): the first launch of each conv geometry times the 7 tile candidates once (warm-up)')
     ap.add_argument('--sync-bn', type=int, default=0, help='N > 1 only: 1 = synchronised BatchNorm (not the headline semantics)')
@@ -288,7 +408,7 @@ def main():
                          'streams lost with the kernels of that time; re-measured in round 4 at batch 256: 12.1 k against 11.6 k '
                          'clips/s with them.)  The roofline pass is always one-stream.')
     ap.add_argument('--secondary', type=int, default=1,
-                    help='1 (default): when the headline workload is configs[1] (no --model/--dtype/--batch), also time '
+                    help='1 (default): with --full, when the headline workload is configs[1] (no --model/--dtype/--batch), also time '
                          'configs[2] (bf16, batch 256) and configs[3] (infogan) -- or, on 8 GPUs, configs[4] (128 clips per GPU) -- '
                          'for a few steps each and report them under "secondary" on the same line')
     ap.add_argument('--secondary-steps', type=int, default=20, help='timed iterations of each secondary workload (20: as the headline; with 8 the fill\n'
@@ -296,6 +416,13 @@ def main():
     ap.add_argument('--cpu-sample-batch', type=int, default=8, help='BASELINE.md section 3: batch 8')
     ap.add_argument('--cpu-sample-steps', type=int, default=5, help='timed iterations (median reported)')
     ap.add_argument('--cpu-sample-warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the roofline pass (one stream, HIP events around every '
+                         'conv launch), the secondary workloads, the CPU baseline, and the detailed record (bench_detail.json)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps write what the last of them computed (losses, x_fake, logits, updated parameters; '
+                         'seeded samples of the large arrays) as DIR/<name>.npy.  That step starts from the seeded initial state of '
+                         'the networks (restored between two synchronisations inside the timed region), so runs agree to rounding')
     args = ap.parse_args()
     if args.overlap is None:
         args.overlap = int(os.environ.get('MCG_OVERLAP', '1'))
@@ -351,9 +478,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(model, dtype, B, steps, warmup, overlap):
+    def measure(model, dtype, B, steps, warmup, overlap, roofline=True, dump_dir=''):
         """One workload: builds the three networks, runs the roofline pass (one stream, HIP events around every conv
-        launch) and the timed headline pass; returns the fields of a result line."""
+        launch; only if `roofline`) and the timed headline pass, writes the last timed iteration's outputs to `dump_dir`
+        (if given); returns the fields of a result line."""
         if exchange is not None:
             # every rank runs the SAME tile codes: geometries the shipped table does not hold are tuned by one local
             # iteration on throw-away networks, then rank 0's choices are broadcast (a straggler sets the step time)
@@ -362,6 +490,7 @@ def main():
         if exchange is not None:                                                # ... and made identical by construction
             for net in (gen, di, dv):
                 exchange.broadcast_params([net.fp.p, net.fp.m, net.fp.v] + list(net.running.values()))
+        seeded = [net_state(net) for net in (gen, di, dv)] if dump_dir else None
         # input_ready_early: the batch is resident, so the next iteration's real chain may start under the end of this one -- the
         # schedule model.updater.Updater runs too when its iterator stays a batch ahead (trainer.PrefetchIterator hands over the
         # copy's event); MCG_INPUT_EARLY=0 switches it off.  It only matters where the two-chain schedule is on (>= 64 clips).
@@ -378,16 +507,17 @@ def main():
         for _ in range(warmup):
             ts.run(x_real, t_real)
         barrier()
-        hl.timing_begin()
         timing = None
-        try:
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                ts.run(x_real, t_real)
-            barrier()
-            dt_serial_instr = time.perf_counter() - t0
-        finally:
-            timing = hl.timing_end()                   # (an exception must not leave the event records armed for the next workload)
+        if roofline:
+            hl.timing_begin()
+            try:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    ts.run(x_real, t_real)
+                barrier()
+                dt_serial_instr = time.perf_counter() - t0
+            finally:
+                timing = hl.timing_end()               # (an exception must not leave the event records armed for the next workload)
         # Pass 2 (headline): un-instrumented, EXACTLY `steps` iterations between barrier + synchronize, with the
         # side-stream placement unless --overlap 0.  Same kernels, same arithmetic, same results.
         ts.set_overlap(bool(overlap))
@@ -403,7 +533,17 @@ def main():
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(steps):
-            ts.run(x_real, t_real)
+            if dump_dir and i == steps - 1:
+                # --dump-outputs: the last step starts from the seeded state, so that what it computes depends on the seeded
+                # inputs alone (the order of the kernels' float-atomic sums varies, and the iterations before would amplify it).
+                # The synchronisations keep the side streams' work of the previous step and the restore apart.
+                torch.cuda.synchronize()
+                for net, st in zip((gen, di, dv), seeded):
+                    load_net_state(net, st)
+                torch.cuda.synchronize()
+                last = ts.run(x_real, t_real)          # (only the last iteration's results are kept: nothing else outlives its step)
+            else:
+                ts.run(x_real, t_real)
             marks[i + 1].record()
         barrier()
         dt_local = time.perf_counter() - t0
@@ -418,6 +558,10 @@ def main():
             dist.all_reduce(tall, op=dist.ReduceOp.MAX)
         dt_best = float(tall)
         losses = ts.losses()
+        if dump_dir:
+            if rank == 0:
+                dump_outputs(dump_dir, ts, last)
+            del last, seeded
         early_used = bool(early and overlap and mstep.chain_iterations > chains_before)
         del ts, gen, di, dv, x_real
         torch.cuda.empty_cache()
@@ -425,30 +569,7 @@ def main():
             return None
         ms_per_step = dt_best / steps * 1e3
         value = B * world * steps / dt_best
-        tot, f_fwd, f_wg, f_dg = dv_conv_flops_per_step(B)
-        dv_ms = {k: timing.get('D_V.' + k, (0, 0.0)) for k in ('fprop', 'wgrad', 'dgrad')}
-        dv_split_ms = timing.get('D_V.split', (0, 0.0))[1] / steps      # 'f32x3': the passes that split the GEMM operands count as GEMM time
-        dv_total_ms = sum(v[1] for v in dv_ms.values()) / steps + dv_split_ms
-        achieved = tot / (dv_total_ms * 1e-3) / 1e12 if dv_total_ms > 0 else 0.0
-        kern = {}
-        for k, fl in (('fprop', f_fwd), ('wgrad', f_wg), ('dgrad', f_dg)):
-            n_l, ms = dv_ms[k]
-            kern[k] = {"launches_per_step": n_l / steps, "ms_per_step": ms / steps,
-                       "tflops": fl / (ms / steps * 1e-3) / 1e12 if ms > 0 else 0.0}
-        all_conv_ms = sum(v[1] for k, v in timing.items() if ' N=' not in k) / steps
-        by_layer = {}
-        for k, (n_l, ms) in sorted(timing.items()):
-            if ' N=' not in k:
-                continue
-            f = dict(kv.split('=') for kv in k.split()[1:])
-            N_, T_, H_, Ci_, Co_ = (int(f[x]) for x in ('N', 'T', 'H', 'Ci', 'Co'))
-            kt_ = 4 if T_ > 1 else 1
-            gflop = 2.0 * N_ * (T_ - kt_ + 1) * (H_ // 2) ** 2 * kt_ * 16 * min(Ci_, 3 if Ci_ == 4 else Ci_) * Co_ / 1e9
-            by_layer[k] = {"launches_per_step": n_l / steps, "ms_per_launch": ms / n_l,
-                           "tflops": gflop * n_l / ms if ms > 0 else 0.0}
-        traffic, traffic_src = pmc_traffic(B, dtype)
-        # f32x3 executes six bf16 MFMA products per algorithmic fp32 product: its roof in ALGORITHMIC TFLOP/s is the dense bf16 peak / 6
-        peak = PEAK_BF16_MFMA_TFLOPS if dtype == 'bf16' else PEAK_F32X3_TFLOPS if dtype == 'f32x3' else PEAK_FP32_MFMA_TFLOPS
+        rl = roofline_fields(dtype, B, steps, overlap, timing, dt_serial_instr) if roofline else None
         cfg_name = "configs[2]" if (dtype == 'bf16' and B == 256 and model == 'normal') else \
             "configs[1]" if (dtype == 'f32' and B == 32 and model == 'normal') else \
             "configs[1], fp32 products on the bf16 pipe" if (dtype == 'f32x3' and B == 32 and model == 'normal') else \
@@ -466,29 +587,7 @@ def main():
                        "per_gpu_batch": B, "global_batch": B * world, "n_filters": 64, "dim_zl": 6,
                        "parallelism": "dp%d" % world, "side_streams": bool(overlap), "input_ready_early": early_used,
                        "sync_bn": bool(args.sync_bn)},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak, "dv_conv3d_mfma_util_pct": 100.0 * achieved / peak, "traffic": traffic,
-                         "algorithmic_bytes": dv_conv_algorithmic_bytes_per_step(B, dtype),
-                         "traffic_unit": "bytes per step (memory side of L2, incl. Infinity-Cache hits)",
-                         "traffic_source": traffic_src,
-                         "traffic_measured_in_run": False,      # PMC counters need rocprofv3 around the process: see traffic_source
-                         "kernel": "VideoDiscriminator Conv3d implicit-GEMM family (%s<FpropP|DgradP|WgradP>), "
-                                   % ("gemm_kernel" if dtype == 'f32' else "gemm_bf16_v2_kernel SPLIT / gemm_kernel" if dtype == 'f32x3' else "gemm_bf16_kernel") +
-                                   "dc1..dc4, all launches of one step",
-                         "algorithmic_gflop_per_step": tot / 1e9, "kernel_ms_per_step": dv_total_ms, "by_pass": kern,
-                         **({"operand_split_ms_per_step": dv_split_ms,
-                             "note": "fp32 products on the bf16 matrix pipe: operands as three bf16 terms, six bf16 MFMA products per "
-                                     "fp32 product (DESIGN.md); `peak` = dense bf16 MFMA peak / 6 in algorithmic TFLOP/s",
-                             "x_fp32_mfma_peak": achieved / PEAK_FP32_MFMA_TFLOPS} if dtype == 'f32x3' else {}),
-                         "all_conv_kernels_ms_per_step": all_conv_ms,
-                         "by_network_and_pass_ms_per_step": {k: v[1] / steps for k, v in sorted(timing.items()) if ' N=' not in k},
-                         "by_layer": by_layer,
-                         "measured": "HIP events around every launch of the family during %d one-stream iterations "
-                                     "(%.3f ms/step with the event records); the headline pass %s"
-                                     % (steps, dt_serial_instr / steps * 1e3,
-                                        "overlaps independent kernels on side streams, which stretches individual launches"
-                                        if overlap else "is one-stream too"),
-                         "dv_conv_share_of_step_time": dv_total_ms / (dt_serial_instr / steps * 1e3)},
+            **({"roofline": rl} if rl is not None else {}),
             "dist": {"backend": dist.get_backend() if dp else None, "world_size": dist.get_world_size() if dp else 1,
                      "per_rank_ms_per_step": {"min": per_rank_ms[0], "median": per_rank_ms[len(per_rank_ms) // 2],
                                               "max": per_rank_ms[-1]}},
@@ -523,8 +622,9 @@ def main():
         torch.cuda.empty_cache()
         return all_ranks_ok(ok)
 
-    out = measure(args.model, args.dtype, args.batch, args.steps, args.warmup, args.overlap)
-    # The other single-GPU workloads BASELINE.json names ride on the same line (a few steps each): configs[2] (bf16
+    out = measure(args.model, args.dtype, args.batch, args.steps, args.warmup, args.overlap, roofline=args.full,
+                  dump_dir=args.dump_outputs)
+    # --full: the other single-GPU workloads BASELINE.json names ride on the same line (a few steps each): configs[2] (bf16
     # networks, batch 256) and configs[3] (--model infogan, batch 32); on 8 GPUs configs[4] (global batch 1024).
     # MCG_BENCH_REHEARSAL_BATCH (single-device rehearsals only, tests/test_gpu_dp.py): the per-rank batch that stands in for the
     # headline's 32 and the 8-GPU secondaries' 128, so that a one-GPU box can walk the `world == 8` branch below in seconds
@@ -549,7 +649,7 @@ def main():
             secondary.append(measure(model, dtype, B, args.secondary_steps, 3, default_overlap(dtype, B)))
         except Exception as exc:                                   # noqa: BLE001
             secondary.append({"config": {"workload": "%s %s batch %d" % (model, dtype, B)}, "dtype": dtype, "error": repr(exc)[:300]})
-    if args.secondary and headline_cfg:
+    if args.full and args.secondary and headline_cfg:
         other = 'f32' if HEADLINE_DTYPE == 'f32x3' else 'f32x3'
         if world == 1:
             also('normal', other, 32)          # configs[1] again in the other form of its fp32 arithmetic (fp32 MFMA / bf16 pipe): first
@@ -562,18 +662,20 @@ def main():
         hl.save_tile_choices(args.save_tiles)
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(args.cpu_sample_batch, args.cpu_sample_warmup, args.cpu_sample_steps)
-        tiles = {"%s N=%d T=%d H=%d Ci=%d Co=%d p=%d" % (k[0], k[1], k[2], k[3], k[5], k[6], k[9]): v
-                 for k, v in sorted(hl.tile_choices().items(), key=str)}
-        detail = dict(out, secondary=[s_ for s_ in secondary if s_ is not None], tile_choices=tiles, cpu_baseline=cpu)
-        detail_path = os.environ.get('MCG_BENCH_DETAIL', os.path.join(ROOT, DETAIL_FILE))
-        try:
-            with open(detail_path, 'w') as f:
-                json.dump(detail, f, indent=1)
-        except OSError as exc:
-            sys.stderr.write('bench.py: could not write %s: %r\n' % (detail_path, exc))
-            detail_path = None
+        detail_path = None
+        if args.full:
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(args.cpu_sample_batch, args.cpu_sample_warmup, args.cpu_sample_steps)
+            tiles = {"%s N=%d T=%d H=%d Ci=%d Co=%d p=%d" % (k[0], k[1], k[2], k[3], k[5], k[6], k[9]): v
+                     for k, v in sorted(hl.tile_choices().items(), key=str)}
+            detail = dict(out, secondary=[s_ for s_ in secondary if s_ is not None], tile_choices=tiles, cpu_baseline=cpu)
+            detail_path = os.environ.get('MCG_BENCH_DETAIL', os.path.join(ROOT, DETAIL_FILE))
+            try:
+                with open(detail_path, 'w') as f:
+                    json.dump(detail, f, indent=1)
+            except OSError as exc:
+                sys.stderr.write('bench.py: could not write %s: %r\n' % (detail_path, exc))
+                detail_path = None
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(compact_line(out, secondary, cpu, detail_path), flush=True)

@@ -531,3 +531,22 @@ def test_bench_stdout_line_stays_small():
     line = json.loads(text)
     assert len(text) <= bench.LINE_LIMIT and line["value"] == 2142.0 and line["metric"] and line["unit"] == "clips/s" and line["n_gpus"] == 1
 
+
+
+def test_bench_plain_line_and_dump_sample():
+    """A plain bench run (no --full) measures no roofline, secondaries or CPU baseline: its line carries the contract fields without
+    them.  --dump-outputs writes large arrays as a fixed seeded sample: the same positions on every run."""
+    import json
+    import numpy as np
+    import bench
+    out = {"metric": "training clips/sec (16×3×64×64)", "value": 2830.25, "unit": "clips/s", "n_gpus": 1, "steps": 20, "warmup": 5,
+           "ms_per_step": 11.3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32x3", "data": "synthetic",
+           "config": {"workload": "w", "variant": "normal", "per_gpu_batch": 32}, "losses": {"image_dis/loss": 0.5}}
+    line = json.loads(bench.compact_line(out, [], None, None))
+    assert {k: line[k] for k in ("value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps")} == \
+        {"value": 2830.25, "unit": "clips/s", "ms_per_step": 11.3, "higher_is_better": True, "dtype": "f32x3", "steps": 20}
+    assert "roofline" not in line and "cpu_baseline" not in line and "secondary" not in line and line["detail"] is None
+    a = np.arange(1000, dtype=np.float32).reshape(10, 100)
+    assert np.array_equal(bench._dump_sample(a, 1000, 3), a.reshape(-1))
+    s1, s2 = bench._dump_sample(a, 64, 3), bench._dump_sample(a.copy(), 64, 3)
+    assert s1.shape == (64,) and np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0)

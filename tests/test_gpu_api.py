@@ -281,3 +281,42 @@ def test_train_on_single_channel_moving_mnist(tmp_path, monkeypatch):
     assert all(np.isfinite(v) for v in tr.updater.observation.values())
     with np.load(tmp_path / 'result' / 'mm1' / 'image_gen_epoch_fianl.npz') as f:
         assert f['dc5/W'].shape == (8, 1, 4, 4)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: exactly K timed steps, the contract fields on one line
+    and nothing of what --full adds (roofline pass, secondary workloads, CPU baseline, detail file); DIR holds the last timed
+    iteration's losses, clips, logits and updated parameters as float32 / float64 .npy files within 64 MB.  Two runs with the
+    same arguments write the same outputs to rounding (the last step starts from the seeded state)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MCG_BENCH_DETAIL=str(tmp_path / 'detail.json'))
+    runs = []
+    for k in ('a', 'b'):
+        dump = tmp_path / k
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '2', '--dtype', 'f32',
+               '--dump-outputs', str(dump)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1, lines
+        runs.append((json.loads(lines[0]), {p.name: np.load(p) for p in dump.iterdir()}))
+    line, files = runs[0]
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    assert line['unit'] == 'clips/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert 'roofline' not in line and 'secondary' not in line and 'cpu_baseline' not in line and line['detail'] is None
+    assert not (tmp_path / 'detail.json').exists()
+    assert {'losses.npy', 'x_fake.npy', 'y_fake_v.npy', 'param.gen.dc1.W.npy', 'param.dis_v.dc1.W.npy'} <= set(files), sorted(files)
+    assert all(a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files['x_fake.npy'].shape == (2, 3, 16, 64, 64)
+    assert np.allclose(files['losses.npy'], [v for _, v in sorted(line['losses'].items())], rtol=0, atol=1e-4)   # (the line rounds to 4 places)
+    other = runs[1][1]
+    assert sorted(other) == sorted(files)
+    for name in ('losses.npy', 'x_fake.npy'):
+        assert rel_l2(other[name], files[name]) < 1e-5, name
+    for name, a in files.items():               # (measured on the MI355X: at most 4e-4, the latent input's filter; 5e-8 typical)
+        assert rel_l2(other[name], a) < 1e-2, name

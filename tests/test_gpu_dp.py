@@ -298,7 +298,7 @@ def test_four_rank_single_device_rehearsal_of_the_eight_gpu_branch():
             env.pop(k, None)
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr', '127.0.0.1',
                '--master-port', '37733', os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1', '--batch', '2',
-               '--secondary-steps', '2']
+               '--secondary-steps', '2', '--full']
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [l for l in out.stdout.strip().splitlines() if l.startswith('{')]
