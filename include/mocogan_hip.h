@@ -120,8 +120,9 @@ typedef struct mcg_conv_geom {
 
 /* ABI revision of this header: a host built against another revision must not call in (argument lists differ).
  * 3 = round 3 (mcg_randint, bf16 tensors in the synchronised-BatchNorm backward; round 2 changed mcg_bn_act_fwd / mcg_bn_act_bwd / mcg_adam_wd / mcg_conv_geom);
- * 6 = round 5 (mcg_split_planes_multi); 7 = round 6 (mcg_pack_clip_u8; nothing else changed). */
-#define MCG_ABI_VERSION 7
+ * 6 = round 5 (mcg_split_planes_multi); 7 = round 6 (mcg_pack_clip_u8; nothing else changed);
+ * 8 = the sampling path (mcg_bn_fold_deconv, mcg_clip_to_u8, MCG_ACT_RELU in mcg_conv_dgrad / mcg_conv_dgrad_ex; no argument list changed). */
+#define MCG_ABI_VERSION 8
 int mcg_version(void);
 
 /* ---- implicit-GEMM convolution on the fp32 MFMA (v_mfma_f32_32x32x2_f32) ------------------- */
@@ -132,10 +133,13 @@ int mcg_version(void);
 int mcg_conv_fprop(const mcg_conv_geom* g, const float* x, const float* w, const float* bias,
                    float* y, void* stream);
 
-/* x (+)= conv_transpose(y, w) + bias; optional tanh.  Replaces the forward of
+/* x (+)= conv_transpose(y, w) + bias; optional tanh or ReLU.  Replaces the forward of
  * L.DeconvolutionND dc2..dc5 (model/net.py:111-114, tanh at :114) and the input-gradient of
  * the convolutions (loss.backward() in model/updater.py:111-113).  accumulate != 0 adds into x
- * (used to add D_I's frame-t gradient onto D_V's clip gradient).  bias may be NULL. */
+ * (used to add D_I's frame-t gradient onto D_V's clip gradient).  bias may be NULL.
+ * act = MCG_ACT_RELU (ABI 8): x = max(conv_transpose(y, w) + bias, 0) in the store -- with w, bias from mcg_bn_fold_deconv this is
+ * F.relu(bn(dc(.))) of model/net.py:111-113 in test mode, one launch.  Every dgrad kernel of the wide layers (Ci > 4) carries it;
+ * MCG_ERR_UNSUPPORTED together with a split-K tile code (+1000 / +2000), accumulate, or (mcg_conv_dgrad_ex) a sums / mask epilogue. */
 int mcg_conv_dgrad(const mcg_conv_geom* g, const float* y, const float* w, const float* bias,
                    float* x, int act, int accumulate, void* stream);
 
@@ -169,7 +173,8 @@ typedef struct mcg_conv_epilogue {
     const float* bn_stats[2];   /*                  per group: the 4*C floats mcg_bn_stats wrote */
     int32_t bn_act;             /*                  MCG_ACT_RELU / MCG_ACT_LRELU behind that BatchNorm */
     /* fprop only: out = act(conv + bias) + noise, and the sign of the pre-activation as one bit per element */
-    int32_t act;                /* MCG_ACT_NONE (nothing of this block applies) or MCG_ACT_LRELU */
+    int32_t act;                /* MCG_ACT_NONE (nothing of this block applies) or MCG_ACT_LRELU; mcg_conv_dgrad_ex (ABI 8): MCG_ACT_RELU
+                                 * = mcg_conv_dgrad's act, so that ReLU and out_bf16 travel together (sums == MCG_SUMS_NONE, no mask) */
     const float* addend[2];     /* per group: pre-scaled noise laid out like the group's output rows, or NULL */
     float sigma;                /* else sigma * N(0,1) from Philox4x32-10 (seed, stream_id[group]) when sigma > 0: one
                                  * counter per (row quad, channel) of the group's output -- element (m, c) is normal
@@ -241,6 +246,16 @@ int mcg_bn_act_fwd(int64_t M, int C, int c_valid, const float* y, int64_t y_rows
  * (activations, output gradients: MCG_IO_OUT_BF16) and the GEMM outputs these passes read (pre-BatchNorm values
  * MCG_IO_Y_BF16, input gradients MCG_IO_G_BF16) in bf16.  1 == MCG_IO_OUT_BF16 keeps the meaning of the former boolean. */
 
+/* Test-mode BatchNorm (chainer.config.train = False: the running averages, eps inside the square root) folded into the
+ * deconvolution in front of it (model/net.py:110-113) (ABI 8): with s_c = gamma_c / sqrt(avg_var_c + eps),
+ *   w_out[r][c] = w[r][c] * s_c        (w [rows][Cp]: a deconvolution's filter in the device layout, whose innermost axis is the
+ *                                       deconvolution's OUTPUT channel -- rows = Co * kt * 16 of mcg_conv_geom's dgrad reading)
+ *   bias_out[c] = (bias[c] - avg_mean_c) * s_c + beta_c     (bias [Cp] or NULL = 0)
+ * so that bn(conv_transpose(y, w) + bias) = conv_transpose(y, w_out) + bias_out.  gamma .. avg_var hold C values; channels
+ * C .. Cp are copied.  fp32 only: mcg_split_planes / a bf16 copy make the other operand forms of the folded filter. */
+int mcg_bn_fold_deconv(int64_t rows, int C, int Cp, const float* w, const float* bias, const float* gamma, const float* beta,
+                       const float* avg_mean, const float* avg_var, float eps, float* w_out, float* bias_out, void* stream);
+
 /* Backward of the line above + BN.  g_out: gradient w.r.t. `out`.  Computes
  * g_bn = g_out * act'(y*scale+shift) (the mask is recomputed from the SAVED scale/shift, i.e.
  * the forward's output sign, as Chainer's retained-output backward does), then
@@ -305,6 +320,14 @@ int mcg_pack_clip(int N, int C, int Cp, int T, int HW, const float* x, int64_t x
  * x + n*x_stride_n + t*x_stride_t + hw*C + c, so frame t of every clip is T = 1 with x + t*HW*C and the clip's x_stride_n. */
 int mcg_pack_clip_u8(int N, int C, int Cp, int T, int HW, const uint8_t* x, int64_t x_stride_n, int64_t x_stride_t,
                      const float* addend, float sigma, uint64_t seed, uint64_t stream_id, float* out, void* stream);
+/* The way out (ABI 8), the inverse of mcg_pack_clip_u8: in[N][T][HW][Cp] fp32 -> uint8 out[n*stride_n + t*stride_t + hw*C + c], so
+ * (N,T,H,W,C) and the reference's frame order (T,N,H,W,C) are one call each.  The byte is generate_samples.py:39's
+ * ((x / 2. + 0.5) * 255).astype(np.uint8): three separately rounded fp32 operations and a truncating cast (values outside
+ * [0, 255] saturate), bit for bit what NumPy makes of the same x.  act = MCG_ACT_NONE: `in` holds x; act = MCG_ACT_TANH: `in` is
+ * the last deconvolution's output before bias and tanh (model/net.py:114) and x = tanh(in + bias[c]) (bias [Cp], may be NULL).
+ * Cp = 4 (MCG_ERR_UNSUPPORTED otherwise); strides in bytes, >= HW*C, items and frames must not overlap (MCG_ERR_BAD_ARG). */
+int mcg_clip_to_u8(int N, int C, int Cp, int T, int HW, const float* in, const float* bias, int act, uint8_t* out,
+                   int64_t stride_n, int64_t stride_t, void* stream);
 /* cgan (model/updater.py:65-76, concat_label_video): out[n][p][0..Cq) = x[n][p][0..C), then dl label planes -- +1 at channel
  * C + labels[n], -1 at the others -- then zeros; x is [N][P][Cp], out [N][P][Cq], Cq % 4 == 0, labels int32 [N] in [0, dl).
  * dl == 0 (labels may be NULL): a channel slice into another row width -- the way back, where label planes carry no gradient. */

@@ -494,7 +494,7 @@ struct DgradP {
             return;
         }
         if (bias) v += bias[n];
-        if (act == MCG_ACT_TANH) v = tanhf(v);
+        if (act != MCG_ACT_NONE) v = act == MCG_ACT_TANH ? tanhf(v) : fmaxf(v, 0.f);      // (act is a kernel argument: one scalar branch; else MCG_ACT_RELU)
         if (e.out16) { reinterpret_cast<__bf16*>(x)[o] = (__bf16)v; return; }      // (never with accumulate: conv_dgrad_impl)
         if (accumulate) v += x[o];
         x[o] = v;
@@ -509,16 +509,24 @@ struct DgradP {
             return;
         }
         if (add_bias && bias) v += *reinterpret_cast<const f32x4*>(bias + n);
-        if (act == MCG_ACT_TANH) { v[0] = tanhf(v[0]); v[1] = tanhf(v[1]); v[2] = tanhf(v[2]); v[3] = tanhf(v[3]); }
+        // ReLU exists in the plain store only (add_bias, a constant after inlining): the fused epilogues' instantiations keep their code
+        if (add_bias ? act != MCG_ACT_NONE : act == MCG_ACT_TANH) {
+            if (!add_bias || act == MCG_ACT_TANH) { v[0] = tanhf(v[0]); v[1] = tanhf(v[1]); v[2] = tanhf(v[2]); v[3] = tanhf(v[3]); }
+            else v = __builtin_elementwise_max(v, f32x4{0.f, 0.f, 0.f, 0.f});
+        }
         if (accumulate) v += *reinterpret_cast<const f32x4*>(x + o);
         *reinterpret_cast<f32x4*>(x + o) = v;
     }
     __device__ void store_vec8_bf16(long long ro, int n, f32x4 lo, f32x4 hi, bool add_bias) const {      // (never with accumulate)
         if (ro < 0 || n >= g.Ci) return;
         if (add_bias && bias) { lo += *reinterpret_cast<const f32x4*>(bias + n); hi += *reinterpret_cast<const f32x4*>(bias + n + 4); }
-        if (act == MCG_ACT_TANH) {
+        if (add_bias ? act != MCG_ACT_NONE : act == MCG_ACT_TANH) {      // (as store_vec4)
+            if (!add_bias || act == MCG_ACT_TANH) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { lo[i] = tanhf(lo[i]); hi[i] = tanhf(hi[i]); }
+                for (int i = 0; i < 4; ++i) { lo[i] = tanhf(lo[i]); hi[i] = tanhf(hi[i]); }
+            } else {
+                lo = __builtin_elementwise_max(lo, f32x4{0.f, 0.f, 0.f, 0.f}); hi = __builtin_elementwise_max(hi, f32x4{0.f, 0.f, 0.f, 0.f});
+            }
         }
         typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
         typedef float f32x8_t __attribute__((ext_vector_type(8)));
@@ -3877,7 +3885,10 @@ int make_epi(const mcg_conv_epilogue* ep, const Geom& g, int pass, Epi& e) {
             e.bn_y16 = ep->bn_y_bf16 ? 1 : 0;
         }
     }
-    if (ep->act != MCG_ACT_NONE) {
+    if (pass == 1 && ep->act == MCG_ACT_RELU) {
+        // dgrad: ReLU in the plain store (conv_dgrad_impl checks what it excludes); no epilogue class of its own
+        if (ep->mask_out) return MCG_ERR_BAD_ARG;
+    } else if (ep->act != MCG_ACT_NONE) {
         if (pass != 0 || ep->act != MCG_ACT_LRELU) return MCG_ERR_UNSUPPORTED;
         if (ep->addend[0] && ep->groups == 2 && !ep->addend[1]) return MCG_ERR_BAD_ARG;
         if (!ep->addend[0] && ep->sigma > 0.f && (e.grp_rows & 3)) return MCG_ERR_UNSUPPORTED;    // a row quad must not straddle two groups
@@ -3994,7 +4005,7 @@ extern "C" int mcg_conv_dgrad(const mcg_conv_geom* c, const float* y, const floa
 extern "C" int mcg_conv_dgrad_ex(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x,
                                  mcg_conv_epilogue* ep, void* stream) {
     if (ep) { ep->n_slots = 0; ep->slot_stride = 0; }
-    return conv_dgrad_impl(c, y, w, bias, x, MCG_ACT_NONE, 0, ep, stream);
+    return conv_dgrad_impl(c, y, w, bias, x, ep ? ep->act : MCG_ACT_NONE, 0, ep, stream);      // (ep->act: MCG_ACT_NONE or MCG_ACT_RELU, make_epi)
 }
 
 namespace {
@@ -4006,10 +4017,13 @@ int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, cons
     int st = make_geom(c, g);
     if (st) return st;
     if (!x || !w || !y) return MCG_ERR_BAD_ARG;
-    if (act != MCG_ACT_NONE && act != MCG_ACT_TANH) return MCG_ERR_UNSUPPORTED;
+    if (act != MCG_ACT_NONE && act != MCG_ACT_TANH && act != MCG_ACT_RELU) return MCG_ERR_UNSUPPORTED;
     Epi e;
     if ((st = make_epi(ep, g, 1, e)) != MCG_OK) return st;
     if (!e.mode) ep = nullptr;
+    // ReLU (test-mode BatchNorm folded into w and bias: x = max(conv_transpose(y, w') + b', 0)) lives in the store of whole output
+    // elements of the wide layers: never on partial tiles, an accumulating call, next to a sums / mask epilogue, or on the clip side
+    if (act == MCG_ACT_RELU && (g.ksplit > 1 || accumulate || e.mode || g.Ci == 4)) return MCG_ERR_UNSUPPORTED;
     if (e.mode) {                                                // the epilogue addresses x as a dense [pixels][Ci] tensor
         const long long frame_ = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
         if (g.perm_n || g.xs0 != frame_ || act != MCG_ACT_NONE || accumulate) return MCG_ERR_UNSUPPORTED;

@@ -601,6 +601,83 @@ __global__ __launch_bounds__(NT) void pack_clip_u8_kernel(int N, int C, int Cp, 
     }
 }
 
+// The way out of the generator, the inverse of pack_clip_u8_kernel: in[n][t][hw][4] fp32 (the padded 3-channel clip, 16 bytes per pixel)
+// -> uint8 out[n * sn + t * st + hw * C + c].  The byte is the reference's ((x / 2. + 0.5) * 255).astype(np.uint8)
+// (generate_samples.py:39): three separately rounded fp32 operations -- x / 2 is exact, so it is x * 0.5 -- and a truncating cast, so
+// that the bytes equal NumPy's on the same x.  act == MCG_ACT_TANH: `in` is the last deconvolution's output BEFORE bias and tanh
+// (what dgrad_c4_mfma_kernel leaves) and x = tanh(in + bias) is formed here as bn_act_fwd_kernel forms it.
+// PACK (C == 3, hw / strides / out multiples of 4): a thread takes 4 consecutive pixels, 64 bytes in, 12 bytes out as three words.
+__device__ __forceinline__ unsigned clip_byte(float x) {
+    float v = __fmul_rn(__fadd_rn(__fmul_rn(x, 0.5f), 0.5f), 255.f);
+    v = fminf(fmaxf(v, 0.f), 255.f);                  // (|x| <= 1 gives 0 .. 255 already; anything else saturates instead of wrapping)
+    return (unsigned)(int)v;
+}
+template <bool PACK>
+__global__ __launch_bounds__(NT) void clip_to_u8_kernel(long long nitems, int C, int T, int HW, const float* __restrict__ in,
+                                                        const float* __restrict__ bias, int act, uint8_t* __restrict__ out,
+                                                        long long sn, long long st) {
+    constexpr int PIX = PACK ? 4 : 1;
+    f32x4 b = {0.f, 0.f, 0.f, 0.f};
+    if (bias) b = *reinterpret_cast<const f32x4*>(bias);
+    const int per = HW / PIX;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < nitems; i += (long long)gridDim.x * NT) {
+        const int hw = (int)(i % per) * PIX;
+        const long long q = i / per;
+        const int t = (int)(q % T);
+        const long long n = q / T;
+        const f32x4* src = reinterpret_cast<const f32x4*>(in) + i * PIX;
+        uint8_t* dst = out + n * sn + (long long)t * st + (long long)hw * C;
+        unsigned by[PIX][4];
+#pragma unroll
+        for (int p = 0; p < PIX; ++p) {
+            f32x4 v = src[p];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float x = v[k];
+                if (act == MCG_ACT_TANH) x = tanhf(__fadd_rn(x, b[k]));
+                by[p][k] = clip_byte(x);
+            }
+        }
+        if constexpr (PACK) {                          // 4 pixels x 3 channels = 3 words (little endian: byte 0 is the lowest)
+            unsigned* d32 = reinterpret_cast<unsigned*>(dst);       // (4-byte aligned: mcg_clip_to_u8 checks out, strides and HW)
+            d32[0] = by[0][0] | (by[0][1] << 8) | (by[0][2] << 16) | (by[1][0] << 24);
+            d32[1] = by[1][1] | (by[1][2] << 8) | (by[2][0] << 16) | (by[2][1] << 24);
+            d32[2] = by[2][2] | (by[3][0] << 8) | (by[3][1] << 16) | (by[3][2] << 24);
+        } else {
+            for (int c = 0; c < C; ++c) dst[c] = (uint8_t)by[0][c];
+        }
+    }
+}
+
+// Test-mode BatchNorm folded into the deconvolution in front of it (model/net.py:110-113 under chainer.config.train = False):
+// bn(conv_transpose(y, W) + b) = conv_transpose(y, W') + b' with s_c = gamma_c / sqrt(avg_var_c + eps),
+// W'[..., c] = W[..., c] * s_c and b'_c = (b_c - avg_mean_c) * s_c + beta_c.  The BatchNorm channel is the innermost axis of the
+// device-layout filter w[rows][Cp] (the deconvolution runs as the input-gradient GEMM of that array); padded channels are copied.
+// One launch: items 0 .. rows * Cp / 4 are the filter, the last Cp / 4 items the bias.
+__global__ __launch_bounds__(NT) void bn_fold_deconv_kernel(long long n4, int C, int Cp, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const float* __restrict__ mean,
+                                                            const float* __restrict__ var, float eps, float* __restrict__ w_out,
+                                                            float* __restrict__ b_out) {
+    const int Cp4 = Cp >> 2;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n4 + Cp4; i += (long long)gridDim.x * NT) {
+        const bool is_w = i < n4;
+        const int c0 = (int)((is_w ? i : i - n4) % Cp4) * 4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (is_w) v = reinterpret_cast<const f32x4*>(w)[i];
+        else if (bias) v = *reinterpret_cast<const f32x4*>(bias + c0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + k;
+            if (c >= C) continue;
+            const float s = __fdiv_rn(gamma[c], __fsqrt_rn(__fadd_rn(var[c], eps)));
+            v[k] = is_w ? __fmul_rn(v[k], s) : fmaf(v[k] - mean[c], s, beta[c]);
+        }
+        if (is_w) reinterpret_cast<f32x4*>(w_out)[i] = v;
+        else *reinterpret_cast<f32x4*>(b_out + c0) = v;
+    }
+}
+
 // cgan (model/updater.py:65-76): the first C channels of every pixel, then dl label planes (+1 on the item's label, -1 elsewhere),
 // then zero padding.  dl == 0: a plain channel slice into another row width (the way back: label planes carry no gradient).
 __global__ __launch_bounds__(NT) void concat_label_planes_kernel(long long npix, long long P, int C, int Cp, int dl, int Cq,
@@ -1470,6 +1547,33 @@ extern "C" int mcg_pack_clip_u8(int N, int C, int Cp, int T, int HW, const uint8
     long long npix = (long long)N * T * HW;
     hipLaunchKernelGGL(pack_clip_u8_kernel, dim3(ew_grid(npix)), dim3(NT), 0, (hipStream_t)stream, N, C, Cp, T, HW, x,
                        (long long)x_stride_n, (long long)x_stride_t, addend, sigma, seed, stream_id, out);
+    return launch_status();
+}
+
+extern "C" int mcg_clip_to_u8(int N, int C, int Cp, int T, int HW, const float* in, const float* bias, int act, uint8_t* out,
+                              int64_t stride_n, int64_t stride_t, void* stream) {
+    if (!in || !out || N <= 0 || C <= 0 || Cp < C || (Cp & 3) || T <= 0 || HW <= 0) return MCG_ERR_BAD_ARG;
+    // a frame is HW * C dense bytes; items and frames must not overlap: (N,T,...) or (T,N,...) order, padded or not
+    const long long frame = (long long)HW * C;
+    if (stride_n < frame || stride_t < frame || !(stride_n >= (long long)T * stride_t || stride_t >= (long long)N * stride_n)) return MCG_ERR_BAD_ARG;
+    if (act != MCG_ACT_NONE && act != MCG_ACT_TANH) return MCG_ERR_BAD_ARG;
+    if (Cp != 4) return MCG_ERR_UNSUPPORTED;           // the clip side: one 16-byte load per pixel
+    const long long npix = (long long)N * T * HW;
+    const bool pack = C == 3 && (HW & 3) == 0 && (stride_n & 3) == 0 && (stride_t & 3) == 0 && ((uintptr_t)out & 3) == 0;
+    if (pack) hipLaunchKernelGGL(clip_to_u8_kernel<true>, dim3(ew_grid(npix / 4)), dim3(NT), 0, (hipStream_t)stream, npix / 4, C, T, HW, in, bias,
+                                 act, out, (long long)stride_n, (long long)stride_t);
+    else hipLaunchKernelGGL(clip_to_u8_kernel<false>, dim3(ew_grid(npix)), dim3(NT), 0, (hipStream_t)stream, npix, C, T, HW, in, bias, act, out,
+                            (long long)stride_n, (long long)stride_t);
+    return launch_status();
+}
+
+extern "C" int mcg_bn_fold_deconv(int64_t rows, int C, int Cp, const float* w, const float* bias, const float* gamma, const float* beta,
+                                  const float* avg_mean, const float* avg_var, float eps, float* w_out, float* bias_out, void* stream) {
+    if (!w || !gamma || !beta || !avg_mean || !avg_var || !w_out || !bias_out || rows <= 0 || C <= 0 || Cp < C || (Cp & 3) || !(eps >= 0.f))
+        return MCG_ERR_BAD_ARG;
+    const long long n4 = (long long)rows * (Cp >> 2);
+    hipLaunchKernelGGL(bn_fold_deconv_kernel, dim3(ew_grid(n4 + (Cp >> 2))), dim3(NT), 0, (hipStream_t)stream, n4, C, Cp, w, bias, gamma, beta,
+                       avg_mean, avg_var, eps, w_out, bias_out);
     return launch_status();
 }
 

@@ -76,6 +76,8 @@ SIGNATURES = {
     "mcg_pack_clip": (_I, [_I, _I, _I, _I, _I, _P, _I64, _I64, _P, _F, _U64, _U64, _P, _P]),
     "mcg_unpack_clip": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
     "mcg_pack_clip_u8": (_I, [_I, _I, _I, _I, _I, _P, _I64, _I64, _P, _F, _U64, _U64, _P, _P]),
+    "mcg_clip_to_u8": (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, _I64, _I64, _P]),
+    "mcg_bn_fold_deconv": (_I, [_I64, _I, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     "mcg_concat_label_planes": (_I, [_I, _I64, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mcg_tanh_bwd_to_frames": (_I, [_I, _I, _I64, _P, _P, _P, _P]),
     "mcg_gru_seq_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -89,7 +91,7 @@ SIGNATURES = {
     "mcg_split_planes_multi": (_I, [_I, _P, _P]),
 }
 
-ABI_VERSION = 7          # MCG_ABI_VERSION of include/mocogan_hip.h these prototypes were written against
+ABI_VERSION = 8          # MCG_ABI_VERSION of include/mocogan_hip.h these prototypes were written against
 
 _lib = None
 
@@ -286,6 +288,14 @@ def set_autotune(on, use_pretuned=True):
             # otherwise such a network would silently run every GEMM on the fp32 kernels (round 4's advice)
             if on or str(k[0]).startswith('split-'):
                 _tile_cache.setdefault(tuple(k), int(v))
+
+
+def use_pretuned_table():
+    """Load the shipped table WITHOUT switching the tuner on: what the sampling path reads (conv_dgrad_relu's tile codes, the split /
+    fp32 decisions of 'f32x3'); launches that tune ignore tile codes while the tuner is off, so nothing else changes."""
+    if os.path.exists(_PRETUNED) and os.environ.get('MCG_NO_PRETUNED') != '1':
+        for k, v in json.load(open(_PRETUNED)):
+            _tile_cache.setdefault(tuple(k), int(v))
 
 
 def reset_tuning():
@@ -509,8 +519,8 @@ def _fprop(g, x, w, bias, y):
 
 def _dgrad(g, y, w, bias, x, act, accumulate):
     if x.dtype == torch.bfloat16:
-        assert act == ACT_NONE and not accumulate
-        return _dgrad_ex(g, y, w, bias, x, epilogue(out_bf16=True), split_ok=True)
+        assert act in (ACT_NONE, ACT_RELU) and not accumulate       # (ReLU in the store travels in the epilogue's act field)
+        return _dgrad_ex(g, y, w, bias, x, epilogue(out_bf16=True, act=act), split_ok=True)
     g = _with_override(g)
     _check(load().mcg_conv_dgrad(C.byref(g), _pin(g, _dense(y), 'y'), _pin(g, _dense(w), 'w'), _p(bias), _p(x), act, int(accumulate), _stream()),
            "mcg_conv_dgrad")
@@ -640,9 +650,10 @@ def conv_fprop(g, x, w, bias, y, ep=None, must_fuse=False):
     return False
 
 
-def conv_dgrad(g, y, w, bias, x, act=ACT_NONE, accumulate=False, ep=None, must_fuse=False):
-    """ep / return value as in conv_fprop (ep needs act == ACT_NONE, no accumulate, dense x)."""
-    if _autotune and not g.tile:
+def conv_dgrad(g, y, w, bias, x, act=ACT_NONE, accumulate=False, ep=None, must_fuse=False, tune=True):
+    """ep / return value as in conv_fprop (ep needs act == ACT_NONE, no accumulate, dense x).  tune=False: never time candidates
+    from this call (the sampling path), whatever set_autotune says."""
+    if _autotune and tune and not g.tile:
         g = _tuned("dgrad", g, (act, int(accumulate)) + _ep_key(g, ep, x), 'x', _tune_run("dgrad", g, y, w, bias, x, ep, act, accumulate))
     if ep is not None and (must_fuse or _with_override(g).tile < 1000):
         assert act == ACT_NONE and not accumulate
@@ -650,6 +661,24 @@ def conv_dgrad(g, y, w, bias, x, act=ACT_NONE, accumulate=False, ep=None, must_f
         return True
     _launch("dgrad", _dgrad, g, y, w, bias, x, act, accumulate)
     return False
+
+
+def table_tile(kind, g, extra=()):
+    """the tile code the table holds for (pass, geometry, launch form) -- 0 when it holds none.  Never tunes."""
+    return _tile_cache.get(_geom_key(kind, g, extra), 0)
+
+
+def conv_dgrad_relu(g, y, w, bias, x):
+    """x = max(conv_transpose(y, w) + bias, 0): the sampling path's deconvolution with test-mode BatchNorm folded into w and bias
+    (bn_fold_deconv) and ReLU in the store; x fp32 or bf16.  Takes the tile the table holds for the PLAIN launch of this geometry
+    and output type with its split-K part dropped (code % 1000: partial tiles cannot carry an activation), else the library's
+    heuristic; the tuner is never run from here."""
+    if not g.tile:
+        code = table_tile("dgrad", g, (ACT_NONE, 0) + _ep_key(g, None, x)) % 1000
+        if code:
+            g = ConvGeom.from_buffer_copy(g)
+            g.tile = code
+    _launch("dgrad", _dgrad, g, y, w, bias, x, ACT_RELU, False)
 
 
 def conv_wgrad(g, x, y, dw):
@@ -778,6 +807,31 @@ def pack_clip_u8(N, Cn, Cp, T, HW, x, out, addend=None, sigma=0.0, seed=0, strea
     stride_n = T * stride_t if stride_n is None else stride_n
     _check(load().mcg_pack_clip_u8(N, Cn, Cp, T, HW, _p(x, torch.uint8), stride_n, stride_t, _p(_dense(addend)), sigma, seed, stream_id,
                                    _p(_dense(out)), _stream()), "mcg_pack_clip_u8")
+
+
+def clip_to_u8(N, Cn, Cp, T, HW, inp, out, bias=None, act=ACT_NONE, stride_n=None, stride_t=None):
+    """inp [N][T][HW][Cp] fp32 -> uint8 out[n * stride_n + t * stride_t + hw * Cn + c] = ((x / 2 + 0.5) * 255) truncated
+    (generate_samples.py:39); default strides: dense (N,T,H,W,C).  act = ACT_TANH: inp is the pre-activation, x = tanh(inp + bias)."""
+    stride_t = HW * Cn if stride_t is None else stride_t
+    stride_n = T * stride_t if stride_n is None else stride_n
+    need = (N - 1) * stride_n + (T - 1) * stride_t + HW * Cn
+    if out.numel() < need or inp.numel() < N * T * HW * Cp or (bias is not None and bias.numel() < Cp):
+        raise McgError("clip_to_u8: a tensor is smaller than the extents passed")
+    _check(load().mcg_clip_to_u8(N, Cn, Cp, T, HW, _p(_dense(inp)), _p(bias), act, _p(_dense(out), torch.uint8), stride_n, stride_t,
+                                 _stream()), "mcg_clip_to_u8")
+
+
+def bn_fold_deconv(w, bias, c, gamma, beta, avg_mean, avg_var, w_out, bias_out, eps=2e-5):
+    """w [..][Cp] (device-layout deconvolution filter, innermost axis = its output channels), bias [Cp] -> the filter and bias with
+    test-mode BatchNorm (the running averages) folded in: mcg_bn_fold_deconv."""
+    cp = w.shape[-1]
+    for t, n in ((gamma, c), (beta, c), (avg_mean, c), (avg_var, c), (bias_out, cp), (w_out, w.numel())):
+        if t.numel() < n:
+            raise McgError("bn_fold_deconv: a tensor is smaller than the extents passed")
+    if bias is not None and bias.numel() < cp:
+        raise McgError("bn_fold_deconv: bias shorter than the padded channel count")
+    _check(load().mcg_bn_fold_deconv(w.numel() // cp, c, cp, _p(_dense(w)), _p(bias), _p(gamma), _p(beta), _p(avg_mean), _p(avg_var),
+                                     eps, _p(_dense(w_out)), _p(bias_out), _stream()), "mcg_bn_fold_deconv")
 
 
 def concat_label_planes(x, c, dl, labels, out):

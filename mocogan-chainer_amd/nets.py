@@ -455,6 +455,8 @@ class _Net:
             self.fp.p16 = self.fp.p16.to(device)
         self.fp.touch()
         self.__dict__.pop('_wsplits', None)
+        for k in ('_fold', '_fold16', '_fold_splits', '_sbuf', '_unit_ss'):      # the sampling path's buffers are rebuilt on the new device
+            self.__dict__.pop(k, None)
         self.running = {k: v.to(device) for k, v in self.running.items()}
         self.ws = self.ws.to(device)
         self._part = None
@@ -1053,6 +1055,166 @@ class GenNet(_Net):
             hl.conv_dgrad(g5, saved['a'][5], fp.param('dc5/W'), fp.param('dc5/b'), x, act=hl.ACT_TANH)
         saved['x'] = x
         return x, saved
+
+    # ---- sampling (test mode only) -------------------------------------------------------------
+    # What a trained generator is for: chainer.config.train = False, forward only.  The fixed BatchNorm of the running averages is
+    # known before the GEMM, so it is folded into the filter and bias of the deconvolution in front of it (hl.bn_fold_deconv) and
+    # ReLU runs in that deconvolution's store (hl.conv_dgrad_relu): dc2..dc4 are one launch each, with no BatchNorm-apply pass.
+    # dc1 (mcg_fc_dgrad, 7 % of the activations) keeps a ReLU pass -- bn_act_fwd with a constant (1, 0) scale / shift -- behind its
+    # folded GEMM.  Nothing is saved for a backward pass and the running statistics are only read.
+    def _fold_bn(self):
+        """fold bn1..bn4 into copies of dc1..dc4 (on every call: 3.5 M weights at full width, and no cache that a training step
+        updating the running averages without touching fp.version could leave stale)"""
+        fp = self.fp
+        lo, hi = fp.offsets['dc1/W'], fp.offsets['dc5/W']
+        f = self.__dict__.get('_fold')
+        if f is None:
+            f = self._fold = torch.empty(hi - lo, device=self.device)
+            self._fold16 = None
+        for l in (1, 2, 3, 4):
+            bn = 'bn%d' % l
+            hl.bn_fold_deconv(fp.param('dc%d/W' % l), fp.param('dc%d/b' % l), self.chans[l], fp.param(bn + '/gamma'), fp.param(bn + '/beta'),
+                              self.running[bn + '/avg_mean'], self.running[bn + '/avg_var'], self._folded('dc%d/W' % l), self._folded('dc%d/b' % l))
+        if self.precision == 'bf16':                                # the bf16 shadow of the folded filters (as FlatParams.refresh16)
+            if self._fold16 is None:
+                self._fold16 = torch.empty_like(f, dtype=torch.bfloat16)
+            self._fold16.copy_(f)
+
+    def _folded(self, name, stored16=False):
+        o = self.fp.offsets[name] - self.fp.offsets['dc1/W']
+        shape = self.fp.shapes[name]
+        return (self._fold16 if stored16 else self._fold)[o:o + int(np.prod(shape))].view(shape)
+
+    def _folded_split(self, name):
+        """'f32x3': the split form of a folded filter as the input-gradient GEMM reads it (planes of 16 filters)"""
+        w = self._folded(name)
+        cache = self.__dict__.setdefault('_fold_splits', {})
+        out = cache.get(name)
+        cache[name] = out = hl.split_planes(w, run=16 * (w.numel() // w.shape[0]), out=out)
+        return out
+
+    def _sview(self, i, shape, dtype=torch.float32):
+        """a tensor in ping-pong buffer i (0 / 1; 2: sample_many's byte output): held by the net, grown on demand, reused by every
+        sample call"""
+        bufs = self.__dict__.setdefault('_sbuf', [None, None, None])
+        nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        b = bufs[i]
+        if b is None or b.numel() < nbytes:
+            bufs[i] = b = None                                      # (release before growing: the peak holds one copy)
+            bufs[i] = b = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return b[:nbytes].view(dtype).view(shape)
+
+    def _unit_scale_shift(self, c):
+        """[scale | shift] = (1, 0) for bn_act_fwd as a plain activation pass, built once by fills"""
+        u = self.__dict__.get('_unit_ss')
+        if u is None or u.numel() != 2 * c:
+            u = self._unit_ss = torch.empty(2 * c, device=self.device)
+            u[:c].fill_(1.0)
+            u[c:].zero_()
+        return u
+
+    def sample(self, n, draw, video_len=None, out='float', order='NT', u8_out=None):
+        """Test-mode forward of n clips.  draw: as forward (h0 [n][dz], e [T][n][dz], zc [n][dc], labels int32 [n] | None; on the
+        device); video_len: frames per clip (default: the constructor's -- the GRU and the per-frame decoder take any T).
+        out='float': fp32 clip tensor in the device layout, [n][T][64][64][cp_out] (order='NT') or [T][n][64][64][cp_out] ('TN', the
+        reference's frame order); out='uint8': ((x / 2 + 0.5) * 255) truncated to bytes (generate_samples.py:39), [n][T][64][64][C] or
+        [T][n][64][64][C].  The result is a fresh tensor (or u8_out, a caller's uint8 tensor of that shape); the activations live in
+        two buffers the net keeps."""
+        assert out in ('float', 'uint8') and order in ('NT', 'TN')
+        dev = self.device
+        T = self.video_len if video_len is None else int(video_len)
+        dz, dl, dc = self.dim_zm, self.dim_zl, self.dim_zc
+        assert n >= 1 and T >= 1
+        assert tuple(draw['h0'].shape) == (n, dz) and tuple(draw['e'].shape) == (T, n, dz) and tuple(draw['zc'].shape) == (n, dc), \
+            "draw does not match (n, video_len)"
+        assert (draw['labels'] is not None) == bool(dl), "labels are given exactly when the generator has a label input"
+        frames = T * n
+        fp = self.fp
+        hl.set_tag('G')
+        self._fold_bn()
+        z = torch.empty((frames, dc + dz), device=dev)
+        gsaved = torch.empty((T, n, 4 * dz), device=dev)
+        hl.gru_seq_fwd(n, T, dz, dl, dc, fp.param('g0'), draw['h0'], draw['e'], draw['labels'], draw['zc'], z, gsaved)
+        c1 = self.chans[1]
+        k1 = 16 * c1
+        y = self._sview(0, (frames, 4, 4, c1))
+        hl.fc_dgrad(frames, k1, self.n_hidden, z, self._folded('dc1/W').view(self.n_hidden, k1), self._folded('dc1/b'), c1, y.view(frames, k1))
+        a = self._sview(1, y.shape, torch.bfloat16 if self._s16(2) else torch.float32)
+        hl.bn_act_fwd(frames * 16, c1, y, self._unit_scale_shift(c1), hl.ACT_RELU, a)
+        g5 = self._geom(5, frames, clip_order_n=n if order == 'NT' else 0)
+        for l in (2, 3, 4):
+            h = 4 << (l - 1)
+            geom = self._geom(l, frames)
+            if l < 4:
+                o16 = self._s16(l + 1)
+            else:                                                   # (as forward: the 64-channel neighbour of the clip in bf16 when its reader takes it)
+                o16 = (OUT16 and Y16 and self.precision == 'bf16' and self._s16(4)
+                       and hl.dgrad_c4_mfma_covers(hl.with_precision(g5, 'bf16y')))
+            x = self._sview(l % 2, (frames, h, h, self.chans[l]), torch.bfloat16 if o16 else torch.float32)
+            name = 'dc%d/W' % l
+            if self.precision == 'f32x3' and hl.split_decided('dgrad', geom):
+                # the table says this geometry's GEMM pays on the bf16 pipe: split operands in, fp32 + ReLU out
+                hl.conv_dgrad_relu(hl.with_precision(geom, 'f32x3'), hl.split_planes(a), self._folded_split(name), self._folded('dc%d/b' % l), x)
+            else:
+                hl.conv_dgrad_relu(geom, a, self._folded(name, self._s16(l)), self._folded('dc%d/b' % l), x)
+            a = x
+        if a.dtype == torch.bfloat16:
+            g5 = hl.with_precision(g5, 'bf16y')
+        lead = (n, T) if order == 'NT' else (T, n)
+        shape = lead + (IMG, IMG, self.cp_out)
+        to_u8 = out == 'uint8'
+        x = self._sview(1, shape) if to_u8 else torch.empty(shape, device=dev)
+        u8 = None
+        if to_u8:
+            u8 = torch.empty(lead + (IMG, IMG, self.out_channels), device=dev, dtype=torch.uint8) if u8_out is None else u8_out
+            assert u8.dtype == torch.uint8 and tuple(u8.shape) == lead + (IMG, IMG, self.out_channels) and u8.is_contiguous()
+        hw = IMG * IMG
+        if hl.dgrad_c4_mfma_covers(g5):
+            # the last deconvolution on the matrix pipe (as forward); its bias + tanh pass becomes the byte conversion when bytes are
+            # asked for: the 4-channel fp32 clip is written once, read once, and 3 bytes per pixel leave
+            hl.conv_dgrad(g5, a, fp.param('dc5/W'), None, x, tune=False)
+            if to_u8:
+                hl.clip_to_u8(lead[0], self.out_channels, self.cp_out, lead[1], hw, x, u8, bias=fp.param('dc5/b'), act=hl.ACT_TANH)
+            else:
+                if getattr(self, '_one_bias', None) is None or self._one_bias.device != dev:
+                    self._one_bias = torch.ones(2 * self.cp_out, device=dev)
+                self._one_bias[self.cp_out:].copy_(fp.param('dc5/b'))
+                hl.bn_act_fwd(x.numel() // self.cp_out, self.cp_out, x, self._one_bias, hl.ACT_TANH, x)
+        else:
+            hl.conv_dgrad(g5, a, fp.param('dc5/W'), fp.param('dc5/b'), x, act=hl.ACT_TANH, tune=False)
+            if to_u8:
+                hl.clip_to_u8(lead[0], self.out_channels, self.cp_out, lead[1], hw, x, u8)
+        return u8 if to_u8 else x
+
+    def sample_many(self, num, chunk, draw, video_len=None, order='NT'):
+        """Generator over ceil(num / chunk) uint8 arrays, chunk clips each (the last one the rest), in the order of `draw`: HOST
+        tensors or arrays h0 [num][dz], e [T][num][dz], zc [num][dc], labels [num] | None for all num clips (220 floats per clip at
+        the default sizes).  Each chunk's slice is uploaded, sampled (sample(..., out='uint8')) into a byte buffer the net keeps and
+        copied into one pinned host buffer; what is yielded is a NumPy copy of it.  Device memory is bounded by chunk, not num: after
+        the first chunk nothing but the chunk's latents and GRU scratch (a few hundred KB) is allocated."""
+        assert num >= 1 and chunk >= 1
+        host = {k: (None if v is None else torch.as_tensor(np.asarray(v))) for k, v in draw.items()}
+        pinned = None
+        for lo in range(0, num, chunk):
+            m = min(chunk, num - lo)
+            u8 = self._sample_chunk(host, lo, m, video_len, order)
+            if pinned is None:
+                pinned = torch.empty(u8.numel() // m * min(chunk, num), dtype=torch.uint8).pin_memory()
+            hbuf = pinned[:u8.numel()].view(u8.shape)
+            hbuf.copy_(u8, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            del u8
+            yield hbuf.numpy().copy()
+
+    def _sample_chunk(self, host, lo, m, video_len, order):
+        dev = self.device
+        d = {'labels': None if host['labels'] is None else host['labels'][lo:lo + m].to(torch.int32).to(dev),
+             'h0': host['h0'][lo:lo + m].to(torch.float32).contiguous().to(dev),
+             'e': host['e'][:, lo:lo + m].to(torch.float32).contiguous().to(dev),
+             'zc': host['zc'][lo:lo + m].to(torch.float32).contiguous().to(dev)}
+        T = self.video_len if video_len is None else int(video_len)
+        u8 = self._sview(2, ((m, T) if order == 'NT' else (T, m)) + (IMG, IMG, self.out_channels), torch.uint8)
+        return self.sample(m, d, video_len=video_len, out='uint8', order=order, u8_out=u8)
 
     # ---- backward --------------------------------------------------------------------------
     def grad_bucket_late(self):

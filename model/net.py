@@ -101,6 +101,69 @@ class ImageGenerator(_Link):
         return x, labels
 
 
+    # ---- sampling: test mode, chosen latents (an extension: the reference samples through __call__ only) ----
+    def _latents(self, batchsize, labels, zc, h0, e, video_len):
+        """Host arrays (labels int64 | None, h0, e, zc): what is not given is drawn from np.random in the reference's order --
+        labels, h0, e_0 .. e_{T-1}, zc (model/net.py:91-92,66,71,102) -- so sample(n) consumes the stream exactly as __call__(n) does.
+        A given array with one row (zc (dim_zc,) or (1, dim_zc); h0 likewise; e (T, dim_zm) or (T, 1, dim_zm); one label) is shared
+        by all videos."""
+        n, T = int(batchsize), int(video_len)
+
+        def rows(a, width, name):
+            a = np.asarray(a, dtype=np.float32)
+            a = a.reshape(1, -1) if a.ndim == 1 else a
+            if a.ndim != 2 or a.shape[1] != width or a.shape[0] not in (1, n):
+                raise ValueError('%s must have shape (%d, %d) or one row of %d values, got %s' % (name, n, width, width, a.shape))
+            return np.array(np.broadcast_to(a, (n, width)), order='C')
+        if self.use_label:
+            if labels is None:
+                labels = np.random.randint(self.dim_zl, size=n)
+            labels = np.asarray(labels)
+            if labels.dtype.kind not in 'iu':
+                raise ValueError('labels must be integers')
+            labels = np.array(np.broadcast_to(labels.reshape(-1) if labels.ndim else labels, (n,)), dtype=np.int64, order='C')
+            if labels.min() < 0 or labels.max() >= self.dim_zl:
+                raise ValueError('labels must lie in [0, %d)' % self.dim_zl)
+        elif labels is not None:
+            raise ValueError('this generator has no label input (dim_zl = 0)')
+        h0 = self.make_hidden(n, self.dim_zm) if h0 is None else rows(h0, self.dim_zm, 'h0')
+        if e is None:
+            e = np.stack([self.make_hidden(n, self.dim_zm) for _ in range(T)])
+        else:
+            e = np.asarray(e, dtype=np.float32)
+            e = e[:, None, :] if e.ndim == 2 else e
+            if e.ndim != 3 or e.shape[0] != T or e.shape[2] != self.dim_zm or e.shape[1] not in (1, n):
+                raise ValueError('e must have shape (%d, %d, %d) or (%d, %d), got %s' % (T, n, self.dim_zm, T, self.dim_zm, e.shape))
+            e = np.array(np.broadcast_to(e, (T, n, self.dim_zm)), order='C')
+        zc = self.make_hidden(n, self.dim_zc) if zc is None else rows(zc, self.dim_zc, 'zc')
+        return labels, h0, e, zc
+
+    def sample(self, batchsize, labels=None, zc=None, h0=None, e=None, video_len=None, as_uint8=False):
+        """Videos from the generator in TEST mode (the running BatchNorm statistics, whatever config.train says), with the latents
+        the caller chooses: labels (batchsize,) ints, zc (batchsize, dim_zc) content codes, h0 (batchsize, dim_zm) and
+        e (video_len, batchsize, dim_zm) the motion path's start and per-frame noise; video_len frames (default: the constructor's).
+        -> (x, labels): x of shape (video_len, batchsize, channel, 64, 64) like __call__ -- fp32 in [-1, 1], or (as_uint8) the
+        reference's bytes ((x / 2 + 0.5) * 255 truncated, generate_samples.py:39) formed on the device.  Nothing of the generator's
+        state changes."""
+        T = self.video_len if video_len is None else int(video_len)
+        labels, h0, e, zc = self._latents(batchsize, labels, zc, h0, e, T)
+        x = self.impl.sample(batchsize, self._to_device(labels, h0, e, zc), video_len=T, out='uint8' if as_uint8 else 'float', order='TN')
+        return x[..., :self.out_channels].permute(0, 1, 4, 2, 3), labels
+
+    def sample_many(self, num, chunk, labels=None, zc=None, h0=None, e=None, video_len=None):
+        """num videos in chunks of `chunk`: yields uint8 arrays (clips, video_len, 64, 64, channel), in order.  The latents of all num
+        videos are chosen / drawn up front exactly as sample(num) does (host memory, 220 floats per video), so the videos are
+        those of sample(num) whatever the chunk; device memory is bounded by chunk."""
+        T = self.video_len if video_len is None else int(video_len)
+        labels, h0, e, zc = self._latents(num, labels, zc, h0, e, T)
+        return self.impl.sample_many(num, chunk, {'labels': labels, 'h0': h0, 'e': e, 'zc': zc}, video_len=T, order='NT')
+
+    def _to_device(self, labels, h0, e, zc):
+        dev = self.impl.device
+        return {'labels': None if labels is None else torch.as_tensor(labels, dtype=torch.int32, device=dev),
+                'h0': torch.as_tensor(h0, device=dev), 'e': torch.as_tensor(e, device=dev), 'zc': torch.as_tensor(zc, device=dev)}
+
+
 class _Discriminator(_Link):
     NDIM = 2
 
