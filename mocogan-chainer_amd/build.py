@@ -13,7 +13,7 @@ def lib_path():
 
 
 def _flags():
-    return os.environ.get("MCG_HIPCC_FLAGS", "").split()        # e.g. -DMCG_STAMPS for the diagnostic builds of tools/
+    return os.environ.get("MCG_HIPCC_FLAGS", "").split()        # extra hipcc flags of an A/B variant build (tools/ab_variant.sh)
 
 
 def _stamp_path():
@@ -24,7 +24,7 @@ def _stale():
     out = lib_path()
     if not os.path.exists(out):
         return True
-    # a library built with other compile flags (a diagnostic build such as -DMCG_STAMPS, or the reverse) is not this build
+    # a library built with other compile flags (an A/B variant build, or the reverse) is not this build
     try:
         if open(_stamp_path()).read() != " ".join(_flags()):
             return True

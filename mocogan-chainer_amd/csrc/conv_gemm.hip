@@ -12,7 +12,7 @@
 // outputs as 32x32 accumulator tiles.  Global loads of K-step s+1 are issued before the MFMAs of
 // step s (register staging).
 //
-// What bounds these kernels (measured with in-kernel stamps, tools/stamp_phases.py, and
+// What bounds these kernels (measured with in-kernel cycle stamps, profiles/NOTES.md, and
 // tools/mfma_probe.hip): the f32 MFMA runs at the f32 vector rate and shares the SIMD with the VALU,
 // so every vector instruction of the loaders is time taken from the matrix pipe.  The MFMA + LDS-read
 // + barrier skeleton alone sustains 150 TFLOP/s; the K-loop's address arithmetic is what costs.  The
@@ -37,15 +37,6 @@ typedef unsigned int u32;
 constexpr int PAD = 4;
 constexpr int NTHREADS = 256;
 constexpr u32 OOB = 0x80000000u;   // byte offsets >= 2 GiB are outside every buffer (make_geom checks sizes)
-
-// Diagnostic build only (-DMCG_STAMPS, tools/stamp_phases.py): per-phase shader-cycle totals of the K-loop.
-// Stamps serialise the schedule, so only the SHARES are meaningful, never this build's run time.
-#ifdef MCG_STAMPS
-__device__ unsigned long long g_stamp[8];
-#define MCG_T(var) do { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define MCG_T(var) do { } while (0)
-#endif
 
 struct Geom {
     int N, Ti, Hi, Wi, Ci, To, Ho, Wo, Co, kt;
@@ -137,30 +128,12 @@ __device__ __forceinline__ f32x4 bload_s(__amdgpu_buffer_rsrc_t r, u32 lane_off,
 __device__ __forceinline__ constexpr int sw_cols(int row, int chunks_per_row) {
     return chunks_per_row >= 16 ? (row & 3) << 2 : ((row >> 1) & 1) << 2;
 }
-// gemm_bf16_v2_kernel's forward / input-gradient launches multiply with v_mfma_f32_16x16x32_bf16 (MCG_V2_M16, round 4): a 32-lane
+// gemm_bf16_v2_kernel's forward / input-gradient launches multiply with v_mfma_f32_16x16x32_bf16 (round 4): a 32-lane
 // half of the transposing read of the input gradient's filter tile then covers k rows q and 8 + q (q = 0..3) of 16 columns, so
 // k-row bit 3 joins the key -- the eight (row, chunk pair) sets of a half tile the 256-byte bank row exactly.  (Split launches,
 // the weight gradient and the patch-stationary kernel keep 32x32x16 and sw_cols.)
-#ifndef MCG_V2_M16
-#define MCG_V2_M16 1
-#endif
-#ifndef MCG_V2_EARLY             // (round 5 experiment, measured and NOT kept: 1 = the barrier of K-step s + 1 in the middle of step s and
-#define MCG_V2_EARLY 0           //  that step's first fragments read under the last MFMA group of step s; see the K loop)
-#endif
-#ifndef MCG_PATCH_MERGE          // (1 = dgrad_patch_kernel with one barrier per two stages; see its pipeline comment)
-#define MCG_PATCH_MERGE 0
-#endif
-#ifndef MCG_V2_SKEW              // (round 5 experiment, measured and NOT kept: 1 = the two waves of a SIMD issue their LDS-DMA pieces at
-#define MCG_V2_SKEW 0            //  opposite ends of a K-step; see the K loop)
-#endif
-#ifndef MCG_C4_AB                // (round 6 experiment, measured and NOT kept: 1 = D_V's first layer forward as fprop_c4_ab_kernel -- its two
-#define MCG_C4_AB 0              //  wave groups half a frame step apart, filters in registers; see that kernel)
-#endif
-#ifndef MCG_PROBE_HALFREADS      // (tools/probe_variant.py: the LDS-DMA GEMM with half its fragment reads -- what a body with half the
-#define MCG_PROBE_HALFREADS 0    //  LDS read bytes per FLOP could gain at most; results are garbage)
-#endif
 __device__ __forceinline__ constexpr int sw_cols16(int row, int chunks_per_row) {
-    return sw_cols(row, chunks_per_row) | (MCG_V2_M16 ? ((row >> 3) & 1) << 1 : 0);
+    return sw_cols(row, chunks_per_row) | ((row >> 3) & 1) << 1;
 }
 
 // ---------------- fprop ----------------
@@ -199,13 +172,11 @@ struct FpropP {
         zz = z;
         ak = SW ? ((tid % KC4) ^ ((tid / (2 * KC4)) & (KC4 - 1))) * E : (tid % KC4) * E;
         krot = 0;
-#ifndef MCG_NO_KROT          // (timing A/B only)
         if (g.kt == 4) {
             const int q0 = m0 >> (g.lgWo + g.lgHo);
             const int to0 = q0 - div_To(g, q0) * g.To;
             krot = ((4 - (to0 & 3)) & 3) * 16 * g.Ci;
         }
-#endif
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
             int m = m0 + tid / KC4 + RSTEP * j;
@@ -267,7 +238,6 @@ struct FpropP {
     // Only for layers whose K-steps lie inside one filter tap (channel count a power of two and a multiple of BK: v2_ok).
     __device__ __amdgpu_buffer_rsrc_t a_rsrc() const { return xr; }
     __device__ __amdgpu_buffer_rsrc_t b_rsrc() const { return wr; }
-    __device__ void store_probe(float v) const { y[0] = v; }
     template <class F> __device__ void each_a(int k0, F&& f) const {
         const int kr = rotated(k0);
         const int tap = kr >> g.lgCi, ci0 = kr & (g.Ci - 1), sp = tap & 15;
@@ -359,9 +329,7 @@ struct DgradP {
             tmax = div_N(g, mlast >> (g.lgWo + g.lgHo));
         }
         krot = 0;
-#ifndef MCG_NO_KROT
         if (g.kt == 4 && (4 * g.Co) % BK == 0) krot = (tmin & 3) * 4 * g.Co;      // whole K-steps must stay inside one temporal tap
-#endif
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
             int m = m0 + tid / KC4 + RSTEP * j;
@@ -399,7 +367,6 @@ struct DgradP {
     // LDS-DMA kernels (as FpropP::each_a / each_b; layers with Co a power of two and a multiple of BK)
     __device__ __amdgpu_buffer_rsrc_t a_rsrc() const { return yr; }
     __device__ __amdgpu_buffer_rsrc_t b_rsrc() const { return wr; }
-    __device__ void store_probe(float v) const { x[0] = v; }
     template <class F> __device__ void each_a(int k0, F&& f) const {
         const int kr = rotated(k0);
         const int ts = kr >> g.lgCo, co0 = kr & (g.Co - 1);
@@ -420,9 +387,6 @@ struct DgradP {
     // first K-step >= k0 that has a valid temporal tap for some row of this block
     __device__ int next_valid(int k0) const {
         if (g.kt == 1) return k0;
-#ifdef MCG_PROBE_NOSKIP
-        return k0;
-#endif
         while (k0 < K) {
             int q0, q1, r_;
             const int kr = rotated(k0);
@@ -591,7 +555,6 @@ struct WgradP {
     // LDS-DMA kernels (as FpropP::each_a / each_b)
     __device__ __amdgpu_buffer_rsrc_t a_rsrc() const { return yr; }
     __device__ __amdgpu_buffer_rsrc_t b_rsrc() const { return xr; }
-    __device__ void store_probe(float v) const { dw[0] = v; }
     template <class F> __device__ void each_a(int k0, F&& f) const {
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
@@ -885,28 +848,12 @@ __device__ __forceinline__ void fused_epilogue(const P& p, f32x16 (&acc)[TM][TN]
 
 // dgrad: linear block index -> (M tile bx, N tile by, bz = K chunk * 4 + parity class); false for the padding of the tile count to a
 // multiple of 8.  (M tile, N tile) pairs are dealt round-robin over the XCDs in dispatch order, the four parity classes of a pair
-// are consecutive workgroups of one XCD (see gemm_kernel).  Split-K launches of 3-D layers (round 6, MCG_DGRAD_HEAVY_FIRST): rows
-// are time-major and a K chunk of a tile near the clip's ends holds few or no live temporal taps, so blocks differ 0 : 1 : 2 in
-// length; in plain order (chunk slowest, frames ascending) the long blocks of the middle frames' second chunk start last and the
-// launch ends with them alone (3 tap-units on 512 block slots where 2 are needed: D_V dc4 at 64 clips).  With the switch on the tile
-// groups go from the MIDDLE frames outwards with the chunks of a group adjacent: long blocks first, the short and empty ones fill
-// the end.  MEASURED (alternating A/B on one MI355X, f32x3 operands, profiles/r06_dgrad_heavy_first_ab.txt) and NOT kept: dc4 at 64
-// clips 1010: 0.450 -> 0.488 ms, 2010: 0.457 -> 0.550, 1007: 0.538 -> 0.471; at 32 clips 1010: 0.291 -> 0.276, 2010: 0.262 -> 0.340;
-// dc3 at 64 clips 1010: 0.76 -> 0.81.  The scheduling model is not what bounds these launches: in plain order every resident block
-// works on the SAME K chunk -- the same filter slab streams through the L2s once for all of them -- and interleaving the chunks
-// doubles the filter bytes in flight (dc4's blocks re-stream 67 MB of split filters per 128-row tile).  Off.
-#ifndef MCG_DGRAD_HEAVY_FIRST
-#define MCG_DGRAD_HEAVY_FIRST 0
-#endif
+// are consecutive workgroups of one XCD (see gemm_kernel).  Split-K: the K chunk is the slowest index, so every resident block works
+// on the same filter slab.  (round 6: a longest-first order -- middle frames first, the chunks of a tile adjacent -- was measured
+// slower, profiles/NOTES_r06.md section 1)
 template <class P> __device__ __forceinline__ bool dgrad_block(const P& p, int Lb, int& bx, int& by, int& bz) {
     const int xq = Lb & 7, qq = Lb >> 3, cls = qq & 3, rr = qq >> 2;
-    int split, g8;
-    const int nsplit = p.kchunk < p.K ? (p.K + p.kchunk - 1) / p.kchunk : 1;
-    if (MCG_DGRAD_HEAVY_FIRST != 0 && nsplit > 1 && p.g.kt == 4) {
-        const int j = rr / nsplit, c = (p.tiles8 - 1) >> 1;
-        split = rr - j * nsplit;
-        g8 = (j & 1) ? c + 1 + (j >> 1) : c - (j >> 1);
-    } else { split = rr / p.tiles8; g8 = rr - split * p.tiles8; }
+    const int split = rr / p.tiles8, g8 = rr - split * p.tiles8;
     const int tl = g8 * 8 + xq;
     if (tl >= p.gxm * p.gyn) return false;
     by = tl % p.gyn; bx = tl / p.gyn; bz = split * 4 + cls;
@@ -958,26 +905,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(P p) {
             // and blocks near the temporal boundary skip most K-steps, so a contiguous range per XCD would give the
             // XCDs unequal work (measured: dc2 0.81 -> 0.97 ms) -- and the FOUR PARITY CLASSES of a pair, which read
             // the same y rows at the same K phase, are consecutive workgroups of one XCD (1-D grid, launch_dgrad).
-#ifndef MCG_NO_CLASS_ADJ
             if (!dgrad_block(p, blockIdx.x, bx, by, bz)) return;      // padding of the tile count to a multiple of 8
-#else
-            bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-#endif
         } else {                        // wgrad: all (Co, tap*Ci) tiles of one pixel chunk together
             bx = t % gx; by = (t / gx) % gy; bz = t / (gx * gy);
         }
     }
     const int m0 = bx * BM, n0 = by * BN;
-#ifdef MCG_PROBE_SAMETILE
-    // diagnostic build (tools/probe_variant.py): every block LOADS tile (0,0,0) -- all operand traffic hits
-    // in L1/L2 -- but keeps its own output rows; the time difference to the real build is what the memory
-    // system costs
-    const int z = 0;
-    p.init(0, 0, tid, 0);
-#else
     const int z = bz;
     p.init(m0, n0, tid, z);
-#endif
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -991,19 +926,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(P p) {
     const int kend = p.k_end(z);
     int k0 = p.next_valid(p.k_begin(z));
     if (block_idle(p, k0, kend, 0)) return;
-#ifdef MCG_PROBE_NOLOOP        // (tools/probe_variant.py: what a block costs WITHOUT its K loop -- row decode, tap masks, store)
-    k0 = kend;
-#endif
     if (k0 < kend) { p.load_a(k0, ra); p.load_b(k0, rb); }
 
     constexpr int A_C4 = A_C / 4, B_C4 = B_C / 4;
-#ifdef MCG_STAMPS
-    unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, acc_w = 0, acc_l = 0, acc_c = 0, acc_b = 0;
-#endif
     while (k0 < kend) {
-        MCG_T(ts0);
         // registers -> LDS
-#ifndef MCG_PROBE_NOWRITE      // (MCG_PROBE_*: timing ablations of tools/probe_variant.py; results are garbage)
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
             int q = tid + NTHREADS * j;
@@ -1015,19 +942,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(P p) {
             *reinterpret_cast<f32x4*>(&Bs[(q / B_C4) * B_LD + (q % B_C4) * 4]) = rb[j];
         }
         __syncthreads();
-#endif
-        MCG_T(ts1);
         const int kn = p.next_valid(k0 + BK);
         // prefetch the next live step; past the end the CURRENT step is loaded again (nothing is consumed), which keeps the
         // loop body free of divergent branches and every generated address one the policy produces for a live step
         // (round 3 loaded step kend - BK there, which is a negative pixel range for a weight gradient with fewer than BK pixels)
-#ifndef MCG_PROBE_NOLOADS
         { const int kl = kn < kend ? kn : k0; p.load_a(kl, ra); p.load_b(kl, rb); }
-#endif
-        MCG_T(ts2);
-#ifdef MCG_SETPRIO          // (experiment: the wave's MFMA phase at raised issue priority)
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int gk = 0; gk < BK / 8; ++gk) {
             float fa[TM][4], fb[TN][4];
@@ -1059,26 +978,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(P p) {
                     for (int b = 0; b < TN; ++b)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a][j], fb[b][j], acc[a][b], 0, 0, 0);
         }
-        MCG_T(ts3);
-#ifdef MCG_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#ifndef MCG_PROBE_NOBAR2
         __syncthreads();
-#endif
-        MCG_T(ts4);
-#ifdef MCG_STAMPS
-        acc_w += ts1 - ts0; acc_l += ts2 - ts1; acc_c += ts3 - ts2; acc_b += ts4 - ts3;
-#endif
         k0 = kn;
     }
 
-#ifdef MCG_STAMPS
-    if (lane == 0) {
-        atomicAdd(&g_stamp[0], acc_w); atomicAdd(&g_stamp[1], acc_l); atomicAdd(&g_stamp[2], acc_c); atomicAdd(&g_stamp[3], acc_b);
-        atomicAdd(&g_stamp[4], 1ull);
-    }
-#endif
     if constexpr (EPI != 0) {           // its own instantiation: the plain kernel keeps its register allocation
         fused_epilogue<P, BM, BN, WM, WN, TM, TN, EPI>(p, acc, m0, n0, bx, bz, tid, lds);
         return;
@@ -1152,22 +1055,15 @@ template <int OFF>
 __device__ __forceinline__ void ds128_issue(bf16x8& d, u32 addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(d) : "v"(addr), "n"(OFF));
 }
-// (MCG_PROBE_NOFRAGWAIT, timing ablation of tools/ab_variant.sh: no fragment read is ever waited for -- what the LDS latency costs;
-//  results are garbage)
-#ifdef MCG_PROBE_NOFRAGWAIT
-#define MCG_FRAGWAIT(N) 15
-#else
-#define MCG_FRAGWAIT(N) (N)
-#endif
 template <int N>
 __device__ __forceinline__ void ds128_wait(bf16x8& d) {
     static_assert(N >= 0 && N < 16, "lgkmcnt is a 4-bit field");
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(d) : "n"(MCG_FRAGWAIT(N)));
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(d) : "n"(N));
 }
 template <int N>
 __device__ __forceinline__ bf16x8 tr16_wait(s16x4& lo, s16x4& hi) {
     static_assert(N >= 0 && N < 16, "lgkmcnt is a 4-bit field");
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(lo), "+v"(hi) : "n"(MCG_FRAGWAIT(N)));
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(lo), "+v"(hi) : "n"(N));
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
@@ -1202,25 +1098,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_bf16_kernel(P p) {
         if constexpr (P::ORDER == 0) {
             by = t % gy; bx = (t / gy) % gx; bz = t / (gy * gx);
         } else if constexpr (P::ORDER == 1) {
-#ifndef MCG_NO_CLASS_ADJ
             if (!dgrad_block(p, blockIdx.x, bx, by, bz)) return;
-#else
-            bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-#endif
         }
         else { bx = t % gx; by = (t / gx) % gy; bz = t / (gx * gy); }
     }
     const int m0 = bx * BM, n0 = by * BN;
-#ifdef MCG_PROBE_SAMETILE
-    // diagnostic build (tools/probe_variant.py): every block LOADS tile (0,0,0) -- all operand traffic hits
-    // in L1/L2 -- but keeps its own output rows; the time difference to the real build is what the memory
-    // system costs
-    const int z = 0;
-    p.init(0, 0, tid, 0);
-#else
     const int z = bz;
     p.init(m0, n0, tid, z);
-#endif
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -1526,10 +1410,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
     const int wm0 = (wave / WN) * (BM / WM), wn0 = (wave % WN) * (BN / WN);
-#ifdef MCG_STAMPS
-    unsigned long long tv_start = 0;
-    MCG_T(tv_start);
-#endif
     int bx, by, bz;
     {   // XCD-aware tile mapping, as in gemm_kernel
         const int gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
@@ -1545,11 +1425,7 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     }
     const int m0 = bx * BM, n0 = by * BN;
     const int z = bz;
-#ifdef MCG_PROBE_SAMETILE        // (tools/probe_variant.py: every block LOADS tile (0,0): what the memory system costs)
-    p.init(0, 0, tid, z);
-#else
     p.init(m0, n0, tid, z);
-#endif
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -1563,9 +1439,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     const __amdgpu_buffer_rsrc_t ar = p.a_rsrc(), br = p.b_rsrc();
     // slot j of this thread is the 16-byte LDS position tid + NT2 * j of its tile: piece (wave, j) starts at wave KiB + 8 j KiB
     auto issue = [&](int k, int buf) {
-#ifdef MCG_PROBE_NOLOADS         // (tools/probe_variant.py: the LDS-read + MFMA + barrier skeleton alone, on whatever LDS holds)
-        return;
-#endif
         unsigned char* sa = smem + buf * STAGE + wave * 1024;
         unsigned char* sb = sa + A_BYTES;
         const bool live = k < kend;
@@ -1590,9 +1463,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
         p.each_b(kk, [&](int j, u32 vo, u32 so) { dvo[NA + j] = live ? vo : OOB; dso[NA + j] = so; });
     };
     auto issue_part = [&](int buf, int part) {                 // pieces [part * PIECES / 4, (part + 1) * PIECES / 4) of the planned step
-#ifdef MCG_PROBE_NOLOADS
-        return;
-#endif
         unsigned char* sa = smem + buf * STAGE + wave * 1024;
         unsigned char* sb = sa + A_BYTES;
 #pragma unroll
@@ -1635,11 +1505,11 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     //   tile in global orientation: two transposing reads of k rows 32 c + 8 g4 + q (+ 4), columns 4 p .. 4 p + 3 of the block
     //     (q = l15 >> 2, p = lane & 3), chunk key sw_cols16.
     // Same LDS bytes, same MFMA cycles as the 32x32x16 form; the chip holds a higher clock on this shape (the guide's DVFS notes).
-    // Measured on one MI355X against the 32x32x16 build (-DMCG_V2_M16=0), bf16-stored operands, 512 clips: forward +4..8 %, input
+    // Measured on one MI355X against the 32x32x16 form, bf16-stored operands, 512 clips: forward +4..8 %, input
     // gradient (B transposed) +3..5 % on the tiles the table uses, weight gradient (both operands through the transposing read)
     // -1..-6 %; the split form ('f32x3': six products as three 32-deep MFMAs over plane PAIRS, twice the fragment reads) forward
     // +-2 %, weight gradient -4..-13 %.  Hence: launches whose A operand is K-contiguous and not split.
-    constexpr bool M16 = !F32 && !SPLIT && P::A_KC && MCG_V2_M16 != 0;
+    constexpr bool M16 = !F32 && !SPLIT && P::A_KC;
     constexpr int TM16 = 2 * TM, TN16 = 2 * TN, HB = TN, NG = 2;                   // HB: column blocks per half of the wave's tile
     const int l15 = lane & 15, g4 = lane >> 4;
     u32 xk[NG], rob[NG], tb16[TN16];
@@ -1678,54 +1548,34 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             k_nx[s] = k;
         }
     }
-    // EARLY (round 5 experiment, -DMCG_V2_EARLY=1; three-buffer rings, bf16 operands, not split): the barrier of K-step s + 1 sits in
-    // the MIDDLE of step s and the first fragments of step s + 1 are read during the last MFMA group of step s.  Idea: with the barrier
-    // at the top of a step every wave starts the step by issuing its first fragment reads and waiting for them with nothing to run
-    // meanwhile, and the other wave of the SIMD stands at the same place (the .s: barrier, eight reads, `lgkmcnt(2)`, first MFMA).
-    // MEASURED (MI355X, D_V dc2..dc4 at 512 clips, bf16-stored, 256x128 / 128x256 three-buffer tiles, alternating runs on one box,
-    // profiles/r05_early_ab.txt): forward -2 %, input gradient -1..-3 %, weight gradient +-1 % -- no gain; that latency is not what the
-    // K loop loses.  Correct (every LDS-DMA op and guard-band test passes with it) and kept as a switch.  Ring bookkeeping: the loads of step s + 2 go
-    // into the buffer of step s - 1, which every wave has finished reading when it passes the mid-step barrier of step s (its last
-    // reads of that buffer were waited for in step s - 1) -- so they are issued in the two MFMA groups BEHIND that barrier, and
-    // `vmcnt(0)` in front of the next mid-step barrier finds them a full step old.
-    constexpr bool EARLY = STAGES == 3 && !F32 && !SPLIT && MCG_V2_EARLY != 0;
     constexpr bool TRA_ = !P::A_KC && !F32, TRB_ = !P::B_KC && !F32;   // operands read with the transposing read (inline asm)
-    // fragment registers live across K-steps (EARLY prefetches the next step's first fragments)
     typedef typename std::conditional<F32, f32x4, bf16x8>::type frag_t;
-    // DIST2 (-DMCG_V2_EARLY=2, M16 launches): the fragments of phase ph + 2 are read under the MFMAs of phase ph (two phases of
-    // look-ahead instead of one; the B fragments then live in four buffers, one per phase)
-    constexpr bool DIST2 = EARLY && M16 && MCG_V2_EARLY == 2 && MCG_PROBE_HALFREADS == 0;
-    constexpr int NBB = DIST2 ? 4 : 2;
-    bf16x8 fa16[2][M16 ? TM16 : 1], fb16[NBB][M16 ? HB : 1];
-    s16x4 blo16[NBB][M16 ? HB : 1], bhi16[NBB][M16 ? HB : 1];
+    bf16x8 fa16[2][M16 ? TM16 : 1], fb16[2][M16 ? HB : 1];
+    s16x4 blo16[2][M16 ? HB : 1], bhi16[2][M16 ? HB : 1];
     frag_t fa[2][TM], fb[2][TN];
     s16x4 alo[2][TM], ahi[2][TM], blo[2][TN], bhi[2][TN];
-    constexpr bool HR16 = MCG_PROBE_HALFREADS != 0;              // (timing ablation: half the fragment reads, results garbage)
-    constexpr int NRA16 = HR16 ? TM16 / 2 : TM16, NRB16 = (TRB_ ? 2 : 1) * HB;
+    constexpr int NRA16 = TM16, NRB16 = (TRB_ ? 2 : 1) * HB;
     auto reads16 = [&](auto ph_, u32 sb32) {                     // M16: the read set of phase ph = (group c, column half h)
-        constexpr int ph = decltype(ph_)::value, c = ph >> 1, h = ph & 1, bb = DIST2 ? ph : h;
+        constexpr int ph = decltype(ph_)::value, c = ph >> 1, h = ph & 1;
         if constexpr (h == 0) {
             static_for<0, TM16>([&](auto i_) {
                 constexpr int i = decltype(i_)::value;
-                if constexpr (!HR16 || (i & 1) == 0) ds128_issue<i * 2048>(fa16[c][i], sb32 + a_row16 + xk[c]);
+                ds128_issue<i * 2048>(fa16[c][i], sb32 + a_row16 + xk[c]);
             });
         }
-        if constexpr (!HR16 || h == 0)
         static_for<0, HB>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
-            if constexpr (TRB_) tr16_issue<0, 4 * (BN * 2)>(blo16[bb][j], bhi16[bb][j], sb32 + tb16[h * HB + j] + rob[c]);
-            else ds128_issue<(h * HB + j) * 2048>(fb16[bb][j], sb32 + b_row16 + xk[c]);
+            if constexpr (TRB_) tr16_issue<0, 4 * (BN * 2)>(blo16[h][j], bhi16[h][j], sb32 + tb16[h * HB + j] + rob[c]);
+            else ds128_issue<(h * HB + j) * 2048>(fb16[h][j], sb32 + b_row16 + xk[c]);
         });
     };
-    constexpr bool HR = MCG_PROBE_HALFREADS != 0 && !F32 && !SPLIT && TM >= 2 && TN >= 2;     // (timing ablation: half the fragment reads)
     // bf16 tiles: EVERY fragment read is inline asm (see ds128_issue) and counted here; NRD = LDS reads per k chunk, in issue order
     // A (TM rows x 1 or 2 reads) then B.  (fp32 tiles: plain loads, counted by the compiler.)
-    constexpr int NRD = F32 ? 0 : ((TRA_ ? 2 * TM : TM) + (TRB_ ? 2 * TN : TN)) / (HR ? 2 : 1);
+    constexpr int NRD = F32 ? 0 : (TRA_ ? 2 * TM : TM) + (TRB_ ? 2 * TN : TN);
     auto frags = [&](auto kc_, const unsigned char* sbase, u32 sb32) {      // 32x32 MFMA: the fragments of k chunk kc
         constexpr int kc = decltype(kc_)::value, slot = kc & 1;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            if (HR && (i & 1)) continue;
             if constexpr (P::A_KC && F32) fa[slot][i] = *reinterpret_cast<const frag_t*>(sbase + a_row + xo[kc] + i * 4096);
             else if constexpr (P::A_KC) {
                 if (i == 0) ds128_issue<0>(fa[slot][0], sb32 + a_row + xo[kc]);
@@ -1740,7 +1590,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
         }
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
-            if (HR && (i & 1)) continue;
             if constexpr (P::B_KC && F32) fb[slot][i] = *reinterpret_cast<const frag_t*>(sbase + b_row + xo[kc] + i * 4096);
             else if constexpr (P::B_KC) {
                 if (i == 0) ds128_issue<0>(fb[slot][0], sb32 + b_row + xo[kc]);
@@ -1754,58 +1603,12 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             } else tr16_issue<kc * 16 * (BN * 2), kc * 16 * (BN * 2) + 4 * (BN * 2)>(blo[slot][i], bhi[slot][i], sb32 + tb[i]);
         }
     };
-    // EARLY: the loads of the step two ahead in the two MFMA groups behind the mid-step barrier (half each); otherwise a quarter in
-    // front of each of the four groups
-    // SKEW (round 5): the two waves that share a SIMD (waves w and w + 4: a workgroup's waves go to the SIMDs cyclically) do the SAME
-    // work per K-step in a different ORDER -- waves 4..7 issue all of the step's LDS-DMA pieces in a burst right behind the barrier,
-    // while waves 0..3 run their MFMA groups; waves 0..3 issue theirs behind their last MFMA group, while waves 4..7 run theirs.
-    // The in-kernel stamps (profiles/r05_stamps_v2_*.txt) showed why: behind the barrier all eight waves run in lockstep, every
-    // LDS-DMA issue holds its wave for 60-180 cycles, and the two waves of a SIMD ended up one after the other (a K-step took the SUM
-    // of their bodies: body 1646 + barrier wait 523 cycles per wave for 512 cycles of MFMAs each).
-    constexpr bool SKEW = MCG_V2_SKEW != 0 && !EARLY && !F32;
-    const bool late_dma = wave < 4;                               // (scalar: `wave` is uniform)
-    auto dma = [&](auto ph_, int nbuf) {
-        constexpr int ph = decltype(ph_)::value;
-        if constexpr (SKEW) {
-            if constexpr (ph == 0) {
-                if (!late_dma) { issue_part(nbuf, 0); issue_part(nbuf, 1); issue_part(nbuf, 2); issue_part(nbuf, 3); }
-            }
-        } else if constexpr (EARLY) {
-            if constexpr (ph == 2) { issue_part(nbuf, 0); issue_part(nbuf, 1); }
-            if constexpr (ph == 3) { issue_part(nbuf, 2); issue_part(nbuf, 3); }
-        } else issue_part(nbuf, ph);
-    };
-    auto dma_tail = [&](int nbuf) {                               // behind the step's last MFMA group
-        if constexpr (SKEW) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (late_dma) { issue_part(nbuf, 0); issue_part(nbuf, 1); issue_part(nbuf, 2); issue_part(nbuf, 3); }
-        }
-    };
+    // One barrier per K-step; a quarter of the step's loads in front of each of its four MFMA groups.  (round 5: a mid-step barrier,
+    // two-phase look-ahead and skewed LDS-DMA issue were measured: no gain, profiles/NOTES_r05.md)
     int buf = 0, nbuf = 0;
-#ifdef MCG_STAMPS                // (diagnostic build, tools/stamp_phases_v2.py: where a wave's cycles go; the shares are meaningful, the run time is not)
-    unsigned long long tv0 = 0, tv1 = 0, tv2 = 0, tv3 = 0, av_vm = 0, av_bar = 0, av_body = 0, av_steps = 0, tv_loop = 0;
-    MCG_T(tv_loop);
-#endif
-    if constexpr (EARLY) {
-        if (k_cur < kend) {
-            wait_vmcnt<(STAGES - 2) * PIECES>();                 // this wave's pieces of the first step
-            __builtin_amdgcn_s_barrier();
-            if constexpr (M16) {
-                reads16(std::integral_constant<int, 0>{}, lds_addr(smem));
-                if constexpr (DIST2) reads16(std::integral_constant<int, 1>{}, lds_addr(smem));
-            } else frags(std::integral_constant<int, 0>{}, smem, lds_addr(smem));
-        }
-    }
     while (k_cur < kend) {
-        if constexpr (!EARLY) {
-            MCG_T(tv0);
-            wait_vmcnt<(STAGES - 2) * PIECES>();                 // this wave's pieces of step k_cur have landed
-            MCG_T(tv1);
-#ifndef MCG_PROBE_NOBAR          // (timing ablation: the K loop without its barrier; results are garbage)
-            __builtin_amdgcn_s_barrier();                        // ... and everyone's; everyone has finished reading the previous step
-#endif
-            MCG_T(tv2);
-        }
+        wait_vmcnt<(STAGES - 2) * PIECES>();                     // this wave's pieces of step k_cur have landed
+        __builtin_amdgcn_s_barrier();                            // ... and everyone's; everyone has finished reading the previous step
         {
             const int kl = k_nx[STAGES - 2];                     // the step STAGES - 1 ahead: into the buffer read one step ago
             int nb = buf + STAGES - 1; nb = nb >= STAGES ? nb - STAGES : nb;
@@ -1819,53 +1622,35 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
         }
         const unsigned char* sbase = smem + buf * STAGE;
         const int buf1 = buf + 1 == STAGES ? 0 : buf + 1;
-        const u32 sb32 = lds_addr(sbase), sb32n = lds_addr(smem + buf1 * STAGE);
+        const u32 sb32 = lds_addr(sbase);
         if constexpr (M16) {
             // four phases (group c, column half h): the reads of the next phase are in flight under the MFMAs of this one.  Read sets:
             // phase (c, 0) = the A blocks of group c + the B blocks of half 0, phase (c, 1) = the B blocks of half 1.  Every read is
             // inline asm (see ds128_issue) and counted here.
-            if constexpr (!EARLY) reads16(std::integral_constant<int, 0>{}, sb32);
+            reads16(std::integral_constant<int, 0>{}, sb32);
             static_for<0, 2 * NG>([&](auto ph_) {
                 constexpr int ph = decltype(ph_)::value, c = ph >> 1, h = ph & 1;
-                if constexpr (DIST2) {
-                    if constexpr (ph + 2 < 2 * NG) reads16(std::integral_constant<int, ph + 2>{}, sb32);
-                    else reads16(std::integral_constant<int, ph + 2 - 2 * NG>{}, sb32n);          // the next step's first two phases
-                } else if constexpr (ph + 1 < 2 * NG) reads16(std::integral_constant<int, ph + 1>{}, sb32);
-                else if constexpr (EARLY) reads16(std::integral_constant<int, 0>{}, sb32n);      // the next step's first fragments
-                dma(ph_, nbuf);
+                if constexpr (ph + 1 < 2 * NG) reads16(std::integral_constant<int, ph + 1>{}, sb32);
+                issue_part(nbuf, ph);
                 __builtin_amdgcn_sched_barrier(0);               // (keeps these loads in front of this MFMA group)
-                constexpr bool MORE = ph + 1 < 2 * NG || EARLY;  // reads issued after the ones used now: those of the following phase(s)
-                // (DIST2: the read sets of the two following phases -- one with the A blocks, one without, whatever ph is)
-                constexpr int NEXT = !MORE ? 0 : DIST2 ? NRA16 + 2 * NRB16 : (h == 0 ? (HR16 ? 0 : NRB16) : NRA16 + NRB16);
+                // reads issued after the ones used now: those of the following phase
+                constexpr int NEXT = ph + 1 == 2 * NG ? 0 : h == 0 ? NRB16 : NRA16 + NRB16;
                 constexpr int YOUNGER = NEXT < 15 ? NEXT : 15;
-                constexpr int bb = DIST2 ? ph : h;
                 if constexpr (h == 0) {
 #pragma unroll
-                    for (int i = 0; i < TM16; i += HR16 ? 2 : 1) ds128_wait<YOUNGER>(fa16[c][i]);
+                    for (int i = 0; i < TM16; ++i) ds128_wait<YOUNGER>(fa16[c][i]);
                 }
-                if constexpr (!HR16 || h == 0) {
 #pragma unroll
                 for (int j = 0; j < HB; ++j) {
-                    if constexpr (TRB_) fb16[bb][j] = tr16_wait<YOUNGER>(blo16[bb][j], bhi16[bb][j]);
-                    else ds128_wait<YOUNGER>(fb16[bb][j]);
-                }
+                    if constexpr (TRB_) fb16[h][j] = tr16_wait<YOUNGER>(blo16[h][j], bhi16[h][j]);
+                    else ds128_wait<YOUNGER>(fb16[h][j]);
                 }
 #pragma unroll
                 for (int i = 0; i < TM16; ++i)
 #pragma unroll
                     for (int j = 0; j < HB; ++j)
-#ifdef MCG_PROBE_NOMFMA          // (timing ablation: loads, fragment reads, waits and the barrier without the MFMAs; results are garbage)
-                        asm volatile("" :: "v"(fa16[c][HR16 ? (i & ~1) : i]), "v"(fb16[HR16 ? 0 : bb][j]));
-#else
-                        acc4[i][h * HB + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa16[c][HR16 ? (i & ~1) : i], fb16[HR16 ? 0 : bb][j], acc4[i][h * HB + j], 0, 0, 0);
-#endif
-                if constexpr (EARLY && ph == 1) {
-                    __builtin_amdgcn_sched_barrier(0);           // (behind this group's MFMAs: hipcc hoisted the barrier in front of them)
-                    wait_vmcnt<0>();                             // this wave's pieces of the NEXT step (issued a step ago)
-                    __builtin_amdgcn_s_barrier();                // ... everyone's; and everyone has finished reading the previous step's buffer
-                }
+                        acc4[i][h * HB + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa16[c][i], fb16[h][j], acc4[i][h * HB + j], 0, 0, 0);
             });
-            dma_tail(nbuf);
         } else {
         // operand fragments two deep: the reads of k chunk kc + 1 are in flight under the MFMAs of chunk kc
         frag_t sfa[SPLIT ? 3 : 1][TM], sfb[SPLIT ? 3 : 1][TN];
@@ -1913,36 +1698,29 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
                 constexpr int c = decltype(c_)::value;
                 constexpr int pa = (c == 0 || c == 1 || c == 3) ? 0 : (c == 2 || c == 4) ? 1 : 2;
                 constexpr int pb = (c == 0 || c == 2 || c == 5) ? 0 : (c == 1 || c == 4) ? 1 : 2;
-                if constexpr (SKEW) {
-                    if constexpr (c == 0) {
-                        if (!late_dma) { issue_part(nbuf, 0); issue_part(nbuf, 1); issue_part(nbuf, 2); issue_part(nbuf, 3); }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else if constexpr (c < 4) { issue_part(nbuf, c); __builtin_amdgcn_sched_barrier(0); }
+                if constexpr (c < 4) { issue_part(nbuf, c); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
                     for (int b = 0; b < TN; ++b)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfa[pa][a], sfb[pb][b], acc[a][b], 0, 0, 0);
             });
-            dma_tail(nbuf);
         } else {
-        if constexpr (!EARLY) frags(std::integral_constant<int, 0>{}, sbase, sb32);
+        frags(std::integral_constant<int, 0>{}, sbase, sb32);
         static_for<0, 4>([&](auto kc_) {
             constexpr int kc = decltype(kc_)::value;
             if constexpr (kc + 1 < 4) frags(std::integral_constant<int, kc + 1>{}, sbase, sb32);
-            else if constexpr (EARLY) frags(std::integral_constant<int, 0>{}, smem + buf1 * STAGE, sb32n);     // the next step's first chunk
-            dma(kc_, nbuf);
+            issue_part(nbuf, kc);
             __builtin_amdgcn_sched_barrier(0);                   // (keeps these loads in front of this MFMA group)
-            constexpr int YOUNGER = (kc + 1 < 4 || EARLY) ? (NRD < 15 ? NRD : 15) : 0;     // the reads of the following chunk, issued after the ones used now
+            constexpr int YOUNGER = kc + 1 < 4 ? (NRD < 15 ? NRD : 15) : 0;     // the reads of the following chunk, issued after the ones used now
             if constexpr (!F32) {
 #pragma unroll
-                for (int i = 0; i < TM; i += HR ? 2 : 1) {
+                for (int i = 0; i < TM; ++i) {
                     if constexpr (TRA) fa[kc & 1][i] = tr16_wait<YOUNGER>(alo[kc & 1][i], ahi[kc & 1][i]);
                     else ds128_wait<YOUNGER>(fa[kc & 1][i]);
                 }
 #pragma unroll
-                for (int i = 0; i < TN; i += HR ? 2 : 1) {
+                for (int i = 0; i < TN; ++i) {
                     if constexpr (TRB) fb[kc & 1][i] = tr16_wait<YOUNGER>(blo[kc & 1][i], bhi[kc & 1][i]);
                     else ds128_wait<YOUNGER>(fb[kc & 1][i]);
                 }
@@ -1960,56 +1738,12 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
                     for (int b = 0; b < TN; ++b)
-#ifdef MCG_PROBE_NOMFMA
-                        asm volatile("" :: "v"(fa[kc & 1][HR ? (a & ~1) : a]), "v"(fb[kc & 1][HR ? (b & ~1) : b]));
-#else
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kc & 1][HR ? (a & ~1) : a], fb[kc & 1][HR ? (b & ~1) : b], acc[a][b], 0, 0, 0);
-#endif
-            }
-            if constexpr (EARLY && kc == 1) {
-                __builtin_amdgcn_sched_barrier(0);
-                wait_vmcnt<0>();                                 // this wave's pieces of the NEXT step (issued a step ago)
-                __builtin_amdgcn_s_barrier();                    // ... everyone's; and everyone has finished reading the previous step's buffer
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kc & 1][a], fb[kc & 1][b], acc[a][b], 0, 0, 0);
             }
         });
-        dma_tail(nbuf);
         }
         }
         buf = buf1;
-#ifdef MCG_STAMPS
-        MCG_T(tv3);
-        av_vm += tv1 - tv0; av_bar += tv2 - tv1; av_body += tv3 - tv2; av_steps += 1;
-#endif
-    }
-#ifdef MCG_STAMPS
-    unsigned long long tv_end = 0;
-    MCG_T(tv_end);
-#endif
-    if constexpr (EARLY) {           // the fragments read ahead for a step that does not exist: their registers stay reserved until they have landed
-        if constexpr (M16) {
-#pragma unroll
-            for (int i = 0; i < TM16; ++i) ds128_wait<0>(fa16[0][i]);
-#pragma unroll
-            for (int j = 0; j < HB; ++j) {
-                if constexpr (TRB_) fb16[0][j] = tr16_wait<0>(blo16[0][j], bhi16[0][j]);
-                else ds128_wait<0>(fb16[0][j]);
-                if constexpr (DIST2) {
-                    if constexpr (TRB_) fb16[1][j] = tr16_wait<0>(blo16[1][j], bhi16[1][j]);
-                    else ds128_wait<0>(fb16[1][j]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                if constexpr (TRA_) fa[0][i] = tr16_wait<0>(alo[0][i], ahi[0][i]);
-                else ds128_wait<0>(fa[0][i]);
-            }
-#pragma unroll
-            for (int i = 0; i < TN; ++i) {
-                if constexpr (TRB_) fb[0][i] = tr16_wait<0>(blo[0][i], bhi[0][i]);
-                else ds128_wait<0>(fb[0][i]);
-            }
-        }
     }
     wait_vmcnt<0>();                                             // the (dummy) loads still in flight write LDS: drain them before the
     __syncthreads();                                             // epilogue reuses the buffers
@@ -2021,15 +1755,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[a][b][r] = acc4[2 * a + (r >> 3)][2 * b + ((r >> 2) & 1)][r & 3];
     }
-#ifdef MCG_PROBE_NOEPI           // (tools/probe_variant.py: what a block costs without its epilogue; one element keeps the MFMAs alive)
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) asm volatile("" :: "v"(acc[a][b][r]));     // (every accumulator stays live: no MFMA is removed)
-    return;
-#endif
 
     if constexpr (P::HAS_ROW_OFF) {
         rowwise_epilogue<P, BN, WM, WN, TM, TN, EPI, STAGES * STAGE, 1, M16>(p, acc, smem, m0, n0, wm0, wn0, bx, bz, tid);
@@ -2044,18 +1769,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
                     else p.store(m0 + wm0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, n0 + wn0 + b * 32 + li, acc[a][b][r]);
                 }
     }
-#ifdef MCG_STAMPS
-    {
-        unsigned long long tv_done = 0;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the stores have left: the epilogue's own time)
-        MCG_T(tv_done);
-        if (lane == 0) {
-            atomicAdd(&g_stamp[0], av_vm); atomicAdd(&g_stamp[1], av_bar); atomicAdd(&g_stamp[2], av_body);
-            atomicAdd(&g_stamp[3], tv_loop - tv_start); atomicAdd(&g_stamp[4], 1ull); atomicAdd(&g_stamp[5], tv_done - tv_end);
-            atomicAdd(&g_stamp[6], av_steps); atomicAdd(&g_stamp[7], tv_done - tv_start);
-        }
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2120,9 +1833,6 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
         if (SPLIT && ((cp ^ kx) >> 1) == 3) poff[j] = OOB;                   // the zero plane: not fetched, never multiplied
     }
     auto issue_patch = [&](int s, int j0, int j1) {
-#ifdef MCG_PP_NOLOADS            // (timing ablations MCG_PP_*: tools/ab_patch.sh; results are garbage)
-        return;
-#endif
         const int a = a_lo + s / CC, cc = s - (s / CC) * CC;
         const u32 so = (u32)(((n * g.To + (t - a)) * g.Ho * g.Wo * g.Co + cc * 64) * 2);
         unsigned char* dst = patch + (s & 1) * PATCH + wave * 1024;
@@ -2133,9 +1843,6 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
     // ---- filter slices: thread = (co row tid / 8, chunk tid % 8) of a [64 co][64 ci] slice
     const u32 boff = (SPLIT && (tid >> 7) == 3) ? OOB : (u32)(((tid >> 3) * g.taps * g.Ci + (((tid & 7) ^ sw_cols(tid >> 3, 8)) << 3)) * 2);
     auto issue_b1 = [&](int G, int ph) {                         // stage G = 8 s + q, q = (pw, bh, bw): its slice of class row ph
-#ifdef MCG_PP_NOLOADS
-        return;
-#endif
         const int s = G >> 3, q = G & 7, pw = q >> 2, bh = (q >> 1) & 1, bw = q & 1;
         const int a = a_lo + s / CC, cc = s - (s / CC) * CC;
         unsigned char* dst = bst + (G & 3) * BSTG + wave * 1024;
@@ -2173,59 +1880,31 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
     // Pipeline: a stage = one (pw, bh, bw) of a super-step = one filter slice per wave set, 16 MFMAs per wave.  The filter stages run
     // THREE ahead in a ring of four (counted vmcnt: a wave issues 2 filter pieces per stage, plus one of the next patch's six pieces
     // in stages 0..5 -- waiting until at most 4 loads are outstanding retires everything but the two youngest stages' filter pieces).
-    // MERGE (round 5, -DMCG_PATCH_MERGE=1): ONE barrier per pair of stages (bw = 0, 1) -- the ring as two 32-KB halves, the pair two
-    // ahead loaded while a pair is multiplied (G + 2 instead of G + 3), `vmcnt(0)` in front of the barrier: a stage is 16 MFMAs per
-    // wave, half a GEMM K-step, and the barrier costs ~180 cycles of it (tools/mini_gemm_probe.hip)
-    constexpr bool MERGE = MCG_PATCH_MERGE != 0;
+    // (round 5: one barrier per pair of stages was measured slower, profiles/NOTES_r05.md)
     issue_patch(0, 0, 6);
     const int total = 8 * S;
     issue_b(0);
     if (1 < total) issue_b(1); else { issue_b(0); }               // (the count of outstanding loads must not depend on S)
-    if constexpr (!MERGE) { if (2 < total) issue_b(2); else { issue_b(0); } }
+    if (2 < total) issue_b(2); else { issue_b(0); }
     for (int s = 0; s < S; ++s) {
         const unsigned char* pb = patch + (s & 1) * PATCH;
         static_for<0, 8>([&](auto q_) {
             constexpr int q = decltype(q_)::value, pw = q >> 2, bh = (q >> 1) & 1, bw = q & 1;
             const int G = 8 * s + q;
-            if constexpr (!MERGE || bw == 0) {
-#ifndef MCG_PP_NOVMWAIT          // (ablation: loads issued but never waited for -- what a longer look-ahead could gain at most)
-                if constexpr (MERGE) wait_vmcnt<0>(); else wait_vmcnt<4>();
-#endif
-#ifndef MCG_PP_NOBAR
-                __builtin_amdgcn_s_barrier();
-#endif
-            }
+            wait_vmcnt<4>();
+            __builtin_amdgcn_s_barrier();
             // This stage's loads -- one piece of the next patch (stages 0..5), the two filter pieces of stage G + 3 -- are NOT issued
             // here in a burst: every LDS-DMA instruction holds its wave's issue for 60-180 cycles, and behind the barrier all eight
             // waves would sit in that burst together with the matrix pipes idle.  They go between the MFMA groups below (same order
             // of issue, so the vmcnt arithmetic is unchanged): the MFMAs of a group run while the wave issues the next load.
-            const int Gn = MERGE ? (G + 2 < total ? G + 2 : G)    // (past the end: the stage's own slices again -- the same bytes)
-                                 : (G + 3 < total ? G + 3 : G);   // (past the end: a harmless reload into the slot read one stage ago)
-#ifdef MCG_PATCH_BURST       // (timing A/B: round 3's placement)
-            if (q < 6 && s + 1 < S) issue_patch(s + 1, q, q + 1);
-            issue_b(Gn);
-#endif
-            // PSKEW (round 5, as SKEW in gemm_bf16_v2_kernel): the two waves of a SIMD (set cg = 0 / 1) issue the stage's three pieces
-            // at opposite ends of the stage -- set 1 in a burst behind the barrier while set 0 multiplies, set 0 behind its last MFMA
-            // group while set 1 multiplies -- instead of both spreading them between the same MFMA groups in lockstep
-            constexpr bool PSKEW = MCG_V2_SKEW != 0;
-            auto burst = [&]() {
-                if (q < 6 && s + 1 < S) issue_patch(s + 1, q, q + 1);
-                issue_b1(Gn, 0);
-                issue_b1(Gn, 1);
-            };
+            // (round 5: the two wave sets issuing them at opposite ends of the stage was measured slower, profiles/NOTES_r05.md)
+            const int Gn = G + 3 < total ? G + 3 : G;              // (past the end: a harmless reload into the slot read one stage ago)
             auto spread = [&](int part) {
-#ifndef MCG_PATCH_BURST
-                if constexpr (PSKEW) return;
                 if (part == 0) { if (q < 6 && s + 1 < S) issue_patch(s + 1, q, q + 1); }
                 else if (part == 1) issue_b1(Gn, 0);
                 else if (part == 2) issue_b1(Gn, 1);
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             };
-#ifndef MCG_PATCH_BURST
-            if constexpr (PSKEW) { if (cg == 1) burst(); __builtin_amdgcn_sched_barrier(0); }
-#endif
             const unsigned char* bb = bst + (G & 3) * BSTG + cg * 8192;       // this set's slice (ph = cg)
             int p0 = prow[0], p1 = prow[1];
             asm volatile("" : "+v"(p0), "+v"(p1));               // (keeps the operand addresses of a super-step from being hoisted out of
@@ -2265,9 +1944,6 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
                             acc[pw][a][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[pa][a], sb[pb_][i], acc[pw][a][i], 0, 0, 0);
                     if constexpr (c < 3) spread(c);
                 });
-#ifndef MCG_PATCH_BURST
-                if constexpr (PSKEW) { __builtin_amdgcn_sched_barrier(0); if (cg == 0) burst(); }
-#endif
                 return;
             }
             // Fragments two chunks deep, EVERY read in asm and counted here (see ds128_issue): chunk kc + 1's six reads (2 A, 4 B) are
@@ -2298,27 +1974,9 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
                         acc[pw][a][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kc & 1][a], fb[i], acc[pw][a][i], 0, 0, 0);
                 if constexpr (kc < 3) spread(kc);
             });
-#ifndef MCG_PATCH_BURST
-            if constexpr (PSKEW) { __builtin_amdgcn_sched_barrier(0); if (cg == 0) burst(); }
-#endif
         });
     }
     wait_vmcnt<0>();
-#ifdef MCG_PP_NOEPI
-    {
-        float keep = 0.f;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) keep += acc[c][a][b][r];
-        if (keep == 123.456f) p.x[0] = keep;
-        return;
-    }
-#endif
     // ---- epilogue: the two sets store their class (ph = cg, pw) side by side through the row-wise store
     static_for<0, 2>([&](auto pw_) {
         constexpr int pw = decltype(pw_)::value;
@@ -2342,6 +2000,8 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
 //   wo, i.e. 32 consecutive hidx of ONE parity plane -- consecutive 16-byte slots, conflict-free.
 //   MFMA k pairing: lane half lh takes tap kw = 2j + lh (A: its pixel's 4 channels, B: w[co][a][kh][2j + lh][0..3]).
 // 512 threads = 8 waves (4 x 2), wave tile 64 pixels x 32 channels.
+// (round 6: the two waves of a SIMD half a frame step apart, one multiplying while the other runs its epilogue, were measured
+//  slower, profiles/NOTES_r06.md section 2 (b))
 // ------------------------------------------------------------------------------------------
 struct C4FpropP {
     Geom g; Epi e;
@@ -2450,150 +2110,6 @@ __global__ __launch_bounds__(512) void fprop_c4_kernel(C4FpropP p) {
         }
     }
 }
-
-// ------------------------------------------------------------------------------------------
-// fprop_c4_kernel with its two halves of a frame step OVERLAPPED (round 6; 3-D layers with <= 3 data channels: D_V's dc1).
-// In fprop_c4_kernel the eight waves of a block multiply together, then run their epilogues together (row decode, leaky_relu, the
-// in-kernel Philox noise, 32 stores per lane), then meet at two barriers: while the epilogues run the matrix pipe idles -- measured
-// at 64 clips: 0.225 ms for the plain store, 0.27-0.29 ms with the first layer's activation + noise epilogue, against 0.133 ms of
-// MFMA work.  Here the two waves that share a SIMD (waves w and w + 4: a workgroup's waves go to the SIMDs cyclically) run HALF A
-// STEP APART: in every half-step one of them multiplies (192 MFMAs, the matrix pipe to itself) and the other runs the epilogue of
-// the step it multiplied in the previous half.  What makes room for it:
-//   * the filters live in REGISTERS (a lane's B operands: 4 x 4 x 2 taps x 3 channels = 96 values of its output channel), so LDS
-//     holds only the patch ring -- 98 KB -- and the K loop reads LDS for the A operand alone;
-//   * the ring has kt + 1 slabs: frame k + kt is loaded (global -> registers) in the first half of step k, stored in the second
-//     half into the slot of frame k - 1, whose last reader (group 1, second half of step k - 1) is a barrier behind; its first
-//     reader (group 0, first half of step k + 1) a barrier ahead.  One barrier per half-step.
-//   * A fragments are read one (frame, kh, tap pair) group ahead of the MFMAs that use them: with ONE multiplying wave per SIMD
-//     nobody else hides the LDS latency.
-// Same arithmetic, same order of additions as fprop_c4_kernel<KT, WO, EPI, 3>: bit-identical results
-// (tests/test_gpu_ops.py::test_overlapped_first_layer_forward_equals_the_weight_stationary_kernel passes with -DMCG_C4_AB=1).
-// MEASURED (MI355X, D_V dc1 at 64 clips, plain store, alternating launches on one box, profiles/r06_c4_overlap_ab.txt): 0.247-0.249 ms
-// against 0.222-0.228 ms for fprop_c4_kernel -- SLOWER.  194 VGPRs, no spills, 192 MFMAs per half-step in groups of six behind
-// one-group-ahead LDS reads: the schedule is the intended one.  What it shows: on the fp32 MFMA the epilogue's VALU instructions do
-// not run beside another wave's MFMAs -- the v_mfma_f32_32x32x2_f32 stream and the VALU share the SIMD's issue (what the fp32 GEMM
-// core's loaders showed in round 1) -- so a step costs MFMA cycles + epilogue VALU cycles however the waves are phased, and the
-// single multiplying wave per SIMD additionally exposes LDS latency that two interleaved waves hide.  Off (MCG_C4_AB = 0).
-// ------------------------------------------------------------------------------------------
-#if MCG_C4_AB
-template <int WO, int EPI>
-__global__ __launch_bounds__(512) void fprop_c4_ab_kernel(C4FpropP p) {
-    constexpr int KT = 4, RING = KT + 1, BM = 256, BN = 64, K = KT * 64;
-    constexpr int R = BM / WO, PR = 2 * R + 2, WI = 2 * WO;
-    constexpr int PLANE = (WO + 2) * 16, ROW = 2 * PLANE, SLAB = PR * ROW;             // bytes (layout of fprop_c4_kernel)
-    constexpr int ENT = 2 * (WO + 2), NLD = (PR * ENT + 511) / 512;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* pl = smem;                                  // RING * SLAB
-    const Geom& g = p.g;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, lh = lane >> 5;
-    const int grp = wave >> 2;                                 // 0: multiplies in the even half-steps, 1: in the odd ones
-    const int hblocks = g.Ho / R;
-    const int n = blockIdx.x / hblocks, ho0 = (blockIdx.x - n * hblocks) * R;
-    const __amdgpu_buffer_rsrc_t xr = make_srd(p.x, g.x_bytes);
-
-    // ---- this lane's B operands (output channel wn * 32 + li; lane half lh takes the taps kw = 2 j2 + lh) -> registers
-    const int wm = wave >> 1, wn = wave & 1;                   // (the wave grid fused_epilogue<.., 4, 2, ..> assumes)
-    float wr[KT][4][2][3];
-    {
-        const float* wp = p.w + (long long)(wn * 32 + li) * K + lh * 4;
-#pragma unroll
-        for (int a = 0; a < KT; ++a)
-#pragma unroll
-            for (int kh = 0; kh < 4; ++kh)
-#pragma unroll
-                for (int j2 = 0; j2 < 2; ++j2) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(wp + ((a * 4 + kh) * 4 + 2 * j2) * 4);
-                    wr[a][kh][j2][0] = v[0]; wr[a][kh][j2][1] = v[1]; wr[a][kh][j2][2] = v[2];
-                }
-    }
-    // ---- patch slabs, as fprop_c4_kernel: entry e of patch row pr is input pixel (hi, wi) = (2 ho0 - 1 + pr, e - 1)
-    u32 goff[NLD]; int loff[NLD];
-#pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-        const int idx = tid + 512 * j, pr = idx / ENT, en = idx - pr * ENT;
-        const int hi = 2 * ho0 - 1 + pr, wi = en - 1;
-        const bool ok = pr < PR && (unsigned)hi < (unsigned)g.Hi && (unsigned)wi < (unsigned)WI;
-        goff[j] = ok ? (u32)(((long long)n * g.Ti * g.Hi + hi) * WI + wi) * 16u : OOB;
-        loff[j] = pr < PR ? pr * ROW + (en & 1) * PLANE + (en >> 1) * 16 : -1;
-    }
-    const u32 fbytes = (u32)g.Hi * WI * 16u;
-    f32x4 stage[NLD];
-    auto slab_load = [&](int t) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) stage[j] = bload(xr, goff[j] == OOB ? OOB : goff[j] + (u32)t * fbytes);
-    };
-    auto slab_store = [&](int slot) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j)
-            if (loff[j] >= 0) *reinterpret_cast<f32x4*>(pl + slot * SLAB + loff[j]) = stage[j];
-    };
-#pragma unroll
-    for (int t = 0; t < KT; ++t) { slab_load(t); slab_store(t); }
-    __syncthreads();
-
-    int abase[2];
-#pragma unroll
-    for (int sidx = 0; sidx < 2; ++sidx) {
-        const int r = wm * 64 + sidx * 32 + li, hol = r / WO, wo = r - hol * WO;
-        abase[sidx] = (2 * hol) * ROW + lh * PLANE + wo * 16;
-    }
-
-    f32x16 acc[2][1];
-#pragma unroll
-    for (int sidx = 0; sidx < 2; ++sidx)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[sidx][0][r] = 0.f;
-    const int To = g.To;
-    // half-step h: step k = h >> 1.  Group 0 multiplies step k in h = 2 k and stores it in h = 2 k + 1; group 1 multiplies step k in
-    // h = 2 k + 1 and stores it in h = 2 k + 2 (the last half-step, h = 2 To, only drains group 1).
-    for (int h = 0; h <= 2 * To; ++h) {
-        const int k = h >> 1;
-        const bool even = (h & 1) == 0;
-        const bool more = k + KT < g.Ti;                       // (k + KT < Ti implies k < To)
-        if (even && more) slab_load(k + KT);                   // lands under this half-step's work ...
-        if (!even && more) { int sl = k + KT; sl -= (sl / RING) * RING; slab_store(sl); }      // ... and goes into frame k - 1's slot a barrier later
-        if (((h + grp) & 1) == 0) {
-            const int km = (h - grp) >> 1;                     // the step this wave multiplies now
-            if (km < To) {
-#pragma unroll
-                for (int sidx = 0; sidx < 2; ++sidx)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[sidx][0][r] = 0.f;
-                const int s0 = km - (km / RING) * RING;
-                int sb[KT];
-#pragma unroll
-                for (int a = 0; a < KT; ++a) { int sl = s0 + a; sl = sl >= RING ? sl - RING : sl; sb[a] = sl * SLAB; }
-                f32x4 av[2][2];                                // [buffer][sidx]: group gi + 1 is read under the MFMAs of group gi
-#pragma unroll
-                for (int sidx = 0; sidx < 2; ++sidx) av[0][sidx] = *reinterpret_cast<const f32x4*>(pl + sb[0] + abase[sidx]);
-#pragma unroll
-                for (int gi = 0; gi < KT * 8; ++gi) {          // gi = (a * 4 + kh) * 2 + j2
-                    const int a = gi >> 3, kh = (gi >> 1) & 3, j2 = gi & 1;
-                    if (gi + 1 < KT * 8) {
-                        const int a1 = (gi + 1) >> 3, kh1 = ((gi + 1) >> 1) & 3, j21 = (gi + 1) & 1;
-#pragma unroll
-                        for (int sidx = 0; sidx < 2; ++sidx)
-                            av[(gi + 1) & 1][sidx] = *reinterpret_cast<const f32x4*>(pl + sb[a1] + abase[sidx] + kh1 * ROW + j21 * 16);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-#pragma unroll
-                        for (int sidx = 0; sidx < 2; ++sidx)
-                            acc[sidx][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[gi & 1][sidx][c], wr[a][kh][j2][c], acc[sidx][0], 0, 0, 0);
-                }
-            }
-        } else {
-            const int ke = (h - grp - 1) >> 1;                 // the step this wave multiplied in the previous half-step
-            if (ke >= 0 && ke < To) {
-                const int m0 = ((n * To + ke) * g.Ho + ho0) * WO;
-                fused_epilogue<C4FpropP, BM, BN, 4, 2, 2, 1, EPI>(p, acc, m0, 0, m0 / BM, 0, tid, reinterpret_cast<float*>(smem));
-            }
-        }
-        __syncthreads();
-    }
-}
-#endif  // MCG_C4_AB
 
 // The same kernel on the bf16 MFMA (v_mfma_f32_32x32x16_bf16) for networks in bf16 mode: x and w (fp32 in memory: the
 // first layer's tensors stay fp32) are rounded to bf16 on their way into LDS.  One MFMA covers the 4 kw x 4 channels
@@ -2895,10 +2411,7 @@ __global__ __launch_bounds__(512) void dgrad_c4_mfma_kernel(C4DgradP p) {
 // lane c4 with the 4 channels of output pixel (class = c4>>2, position = c4&3): one 16-byte store.
 // All KT*16 taps x 64 x 4 weights sit in LDS as [tap][j][c4] float4 (conflict-free ds_read_b128).
 // ------------------------------------------------------------------------------------------
-#ifndef MCG_C4_RUNS
-#define MCG_C4_RUNS 4
-#endif
-constexpr int C4_RUNS_PER_WAVE = MCG_C4_RUNS;
+constexpr int C4_RUNS_PER_WAVE = 4;
 
 template <int KT>
 __global__ __launch_bounds__(NTHREADS) void dgrad_c4_kernel(Geom g, const float* __restrict__ y, const float* __restrict__ w,
@@ -3021,36 +2534,6 @@ int launch_fprop_c4(const Geom& g, const float* x, const float* w, const float* 
     return MCG_OK;
 }
 
-#if MCG_C4_AB
-// fprop_c4_ab_kernel (the overlapped form): 3-D layers of the padded RGB clip on the fp32 MFMA, plain store or the first layer's epilogue
-// (neither has per-channel sums: fused_epilogue then runs without a block barrier, which the two wave groups could not share)
-bool c4_fprop_ab_ok(const Geom& g, const Epi& e) {
-    return c4_fprop_ok(g, e) && g.kt == 4 && g.cv <= 3 && g.prec == MCG_PREC_F32 && (e.mode == 0 || e.mode == EPI_ACT) && !e.out16;
-}
-
-template <int WO>
-int launch_fprop_c4_ab(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, hipStream_t s) {
-    C4FpropP p;
-    p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
-    p.M = g.N * g.To * g.Ho * g.Wo;
-    constexpr int R = 256 / WO;
-    const size_t lds = (size_t)5 * (2 * R + 2) * 2 * (WO + 2) * 16;
-    static std::once_flag once[2];
-    hipError_t attr = hipSuccess;
-    const dim3 grid(g.N * (g.Ho / R));
-    if (e.mode & EPI_ACT) {
-        std::call_once(once[0], [&] { attr = hipFuncSetAttribute((const void*)fprop_c4_ab_kernel<WO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-        if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-        hipLaunchKernelGGL((fprop_c4_ab_kernel<WO, 3>), grid, dim3(512), lds, s, p);
-    } else {
-        std::call_once(once[1], [&] { attr = hipFuncSetAttribute((const void*)fprop_c4_ab_kernel<WO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-        if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-        hipLaunchKernelGGL((fprop_c4_ab_kernel<WO, 1>), grid, dim3(512), lds, s, p);
-    }
-    return MCG_OK;
-}
-#endif  // MCG_C4_AB
-
 // the MFMA col2im input-gradient kernel of the Ci = 4 layers: what it covers
 bool c4_dgrad_mfma_ok(const Geom& g, const Epi& e, const float* bias, int act, int accumulate) {
     const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
@@ -3061,10 +2544,7 @@ bool c4_dgrad_mfma_ok(const Geom& g, const Epi& e, const float* bias, int act, i
            !e.mode && !e.out16 && !bias && act == MCG_ACT_NONE && !accumulate;
 }
 
-#ifndef MCG_C4_DGRAD_BLOCKS
-#define MCG_C4_DGRAD_BLOCKS 1024
-#endif
-constexpr int C4_DGRAD_MAX_BLOCKS = MCG_C4_DGRAD_BLOCKS;      // blocks of the persistent first-layer input-gradient kernel (4 per CU; each walks tiles)
+constexpr int C4_DGRAD_MAX_BLOCKS = 1024;      // blocks of the persistent first-layer input-gradient kernel (4 per CU; each walks tiles)
 template <int KT, int WO, bool BF, bool Y16 = false>
 int launch_dgrad_c4_mfma(const Geom& g, const float* y, const float* w, float* x, hipStream_t s) {
     C4DgradP p;
@@ -3290,19 +2770,14 @@ __global__ __launch_bounds__(512) void wgrad_c4_kernel(C4WgradP p) {
 // NT / BM: threads and output pixels per step.  512 / 256 is one block per CU (131 KB of LDS); 256 / 128 (68 KB) puts TWO blocks on a CU:
 // each block's loads of the next step (its waves wait for them at the LDS store behind the MFMAs) then overlap the other block's MFMAs
 // (measured on D_V's dc1 at 512 clips: no faster by itself -- 0.454 -> 0.456 ms; what moved the kernel is in NOTES_r06 section 7).
-#ifndef MCG_WC4_YS               // LDS row strides of wgrad_c4_bf16_kernel (tuning switches): y tile rows, extra bytes per patch row
-#define MCG_WC4_YS 160
-#endif
-#ifndef MCG_WC4_ROWPAD
-#define MCG_WC4_ROWPAD 0
-#endif
+constexpr int WC4_YS = 160;      // LDS row stride (bytes) of wgrad_c4_bf16_kernel's y tile
 template <int KT, int WO, int NT, int BM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_c4_bf16_kernel(C4WgradP p) {     // (two waves per SIMD: <= 256 registers)
     constexpr int K = KT * 64;
     constexpr int R = BM / WO, PR = 2 * R + 2, WI = 2 * WO;
-    constexpr int ENT = WI + 4, ROW = ENT * 8 + MCG_WC4_ROWPAD, SLAB = PR * ROW;     // bytes (a pixel = 4 bf16), as fprop_c4_bf16_kernel + row padding
+    constexpr int ENT = WI + 4, ROW = ENT * 8, SLAB = PR * ROW;     // bytes (a pixel = 4 bf16), as fprop_c4_bf16_kernel
     constexpr int NLD = (PR * ENT + NT - 1) / NT, RING = KT + 1, NY = BM * 8 / NT;     // slab entries / 16-byte y chunks per thread
-    constexpr int YS = MCG_WC4_YS, YT = BM * YS;                                            // y tile: row stride, bytes per buffer
+    constexpr int YS = WC4_YS, YT = BM * YS;                                            // y tile: row stride, bytes per buffer
     constexpr int NB = KT * 2, NBW = KT == 4 ? 4 : 2, WC = NB / NBW, PG = (NT / 64) / WC, KGW = (BM / 16) / PG;     // N blocks; per wave; wave columns; pixel groups; K groups per wave and step
     constexpr int NC = NB * 32;                                                      // columns (tap, ci) incl. the padded channel
     static_assert(64 * NC * 4 <= RING * SLAB + 2 * YT, "the reduction buffer reuses the tiles");
@@ -3466,16 +2941,16 @@ int launch_wgrad_c4_bf16(const Geom& g, const float* x, const float* y, float* d
     C4WgradP p;
     p.g = g; p.x = x; p.y = y; p.dw = dw;
     constexpr int R = BM / WO;
-    const size_t lds = (size_t)(KT + 1) * (2 * R + 2) * ((2 * WO + 4) * 8 + MCG_WC4_ROWPAD) + 2 * BM * MCG_WC4_YS;
+    const size_t lds = (size_t)(KT + 1) * (2 * R + 2) * (2 * WO + 4) * 8 + 2 * BM * WC4_YS;
     static std::once_flag once;
     hipError_t attr = hipSuccess;
     std::call_once(once, [&] { attr = hipFuncSetAttribute((const void*)wgrad_c4_bf16_kernel<KT, WO, NT, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
     if (attr != hipSuccess) return MCG_ERR_LAUNCH;
     // (row block, batch item) pairs over ~2 rounds of blocks; with fewer the frames of an item are split (as launch_wgrad_c4)
-#ifndef MCG_WC4_TARGET           // blocks of the 3-D form: 512 = ONE round at two per CU (every block ends in 64 x kt * 48 float atomics onto the same
-#define MCG_WC4_TARGET 512       // dw: measured at 512 clips 0.458-0.472 ms with 1024 blocks, 0.397-0.406 with 512, 0.412-0.420 with 256)
-#endif
-    const int hblocks = g.Ho / R, target = SMALL ? MCG_WC4_TARGET : 512;
+    // 512 blocks: ONE round of the 3-D form at two per CU (every block ends in 64 x kt * 48 float atomics onto the same dw: measured
+    // at 512 clips 0.458-0.472 ms with 1024 blocks, 0.397-0.406 with 512, 0.412-0.420 with 256)
+    constexpr int WC4_TARGET = 512;
+    const int hblocks = g.Ho / R, target = WC4_TARGET;
     p.nsplit = g.N; p.tsplit = 1;
     if (hblocks * p.nsplit > target) p.nsplit = target / hblocks > 0 ? target / hblocks : 1;
     while (hblocks * p.nsplit * p.tsplit < target / 2 && 2 * p.tsplit * 2 <= g.To) p.tsplit *= 2;
@@ -3638,11 +3113,7 @@ int launch_dgrad(const Geom& g, const float* y, const float* w, const float* bia
     splits = (p.K + p.kchunk - 1) / p.kchunk;
     if (splits > 1 && !acc && hipMemsetAsync(x, 0, (size_t)g.N * frame * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;
     p.gxm = (p.M + BM - 1) / BM; p.gyn = (g.Ci + BN - 1) / BN; p.tiles8 = (p.gxm * p.gyn + 7) / 8;
-#ifndef MCG_NO_CLASS_ADJ
     dim3 grid(8 * p.tiles8 * 4 * splits, 1, 1);
-#else
-    dim3 grid(p.gxm, p.gyn, 4 * splits);
-#endif
     const int cls = e.mode ? epi_class(e.mode) : 0;                      // (class 3 is fprop only: make_epi)
     if (PM == 2 && cls > 1) return MCG_ERR_UNSUPPORTED;
     if (cls == 2 && (e.out16 || e.bn_y16)) return MCG_ERR_UNSUPPORTED;
@@ -3827,9 +3298,6 @@ int launch_dgrad_patch(const Geom& g, const float* y, const float* w, const floa
 }
 
 // tile / K-depth / MFMA-type dispatch of the launch_* templates
-#ifdef MCG_FAST_BUILD       // compile-time experiments: one tile, one K depth, fp32 only
-#define MCG_TILES(fn, t, BK, BF, ...) do { st = fn<128, 128, 32, 0>(__VA_ARGS__); } while (0)
-#else
 #define MCG_TILES(fn, t, BK, BF, ...)                                   \
     do {                                                                \
         if ((t) == 1) st = fn<128, 128, BK, BF>(__VA_ARGS__);           \
@@ -3838,7 +3306,6 @@ int launch_dgrad_patch(const Geom& g, const float* y, const float* w, const floa
         else if ((t) == 5) st = fn<64, 256, (BF) ? BK : 32, BF>(__VA_ARGS__);   /* would not fit the 64 KiB of static LDS     */ \
         else st = fn<64, 64, BK, BF>(__VA_ARGS__);                      \
     } while (0)
-#endif
 #define MCG_DISPATCH(fn, t, bk64, pm, ...)                              \
     do {                                                                \
         if ((pm) == 2)      { if (bk64) MCG_TILES(fn, t, 64, 2, __VA_ARGS__); else MCG_TILES(fn, t, 32, 2, __VA_ARGS__); }      \
@@ -3853,12 +3320,6 @@ std::once_flag g_c4_lds_once;      // dgrad_c4_kernel<4> needs the 64 KiB dynami
 
 }  // namespace
 
-#if defined(MCG_STAMPS) && (!defined(MCG_TU) || MCG_TU == 3)
-extern "C" void mcg_debug_stamps(unsigned long long* out, int reset) {
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 8);
-    if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z)); }
-}
-#endif
 
 namespace {
 
@@ -3941,10 +3402,6 @@ int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, cons
         if (g.prec == MCG_PREC_BF16) {
             if (g.kt == 4) st = g.Wo == 32 ? launch_fprop_c4_bf16<4, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4_bf16<4, 16>(g, x, w, bias, y, e, s);
             else st = g.Wo == 32 ? launch_fprop_c4_bf16<1, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4_bf16<1, 16>(g, x, w, bias, y, e, s);
-#if MCG_C4_AB
-        } else if (t == 0 && c4_fprop_ab_ok(g, e)) {               // round 6 experiment: multiply and epilogue phases overlapped (tile code 6 keeps fprop_c4_kernel)
-            st = g.Wo == 32 ? launch_fprop_c4_ab<32>(g, x, w, bias, y, e, s) : launch_fprop_c4_ab<16>(g, x, w, bias, y, e, s);
-#endif
         } else {
             if (g.kt == 4) st = g.Wo == 32 ? launch_fprop_c4<4, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4<4, 16>(g, x, w, bias, y, e, s);
             else st = g.Wo == 32 ? launch_fprop_c4<1, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4<1, 16>(g, x, w, bias, y, e, s);

@@ -12,10 +12,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int NT = 256;
-#ifndef MCG_MAX_PART
-#define MCG_MAX_PART 512
-#endif
-constexpr int MAX_PART = MCG_MAX_PART;        // max partial-reduction blocks (workspace sizing)
+constexpr int MAX_PART = 512;        // max partial-reduction blocks (workspace sizing)
 constexpr float LRELU_SLOPE = 0.2f;  // model/net.py:149-155,190-196
 
 int launch_status() { return hipGetLastError() == hipSuccess ? MCG_OK : MCG_ERR_LAUNCH; }
@@ -523,12 +520,10 @@ __global__ __launch_bounds__(NT) void bn_act_bwd_apply8_kernel(long long n8, int
     }
 }
 
-#ifndef MCG_EW_GRID
-#define MCG_EW_GRID 2048
-#endif
+constexpr int EW_GRID = 2048;        // max blocks of an element-wise pass (grid-stride loops)
 int ew_grid(long long n4) {
     long long b = (n4 + NT - 1) / NT;
-    if (b > MCG_EW_GRID) b = MCG_EW_GRID;
+    if (b > EW_GRID) b = EW_GRID;
     if (b < 1) b = 1;
     return (int)b;
 }

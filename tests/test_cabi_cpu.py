@@ -41,8 +41,8 @@ def test_library_exports_every_declared_symbol(hl):
 
 
 def test_library_exports_nothing_the_header_does_not_declare(hl):
-    """the dynamic symbol table holds exactly the declared mcg_* entry points (+ the diagnostic builds' mcg_debug_stamps, absent from
-    the shipped build): helpers shared between the library's translation units have hidden visibility (round 5's review)."""
+    """the dynamic symbol table holds exactly the declared mcg_* entry points: helpers shared between the library's translation
+    units have hidden visibility (round 5's review)."""
     import subprocess
     import mocogan_chainer_amd as build
     tool = '/opt/rocm/lib/llvm/bin/llvm-readelf'

@@ -531,12 +531,11 @@ def test_fprop_epilogue_statistics_and_first_layer(hl, case, tile):
 
 
 @pytest.mark.parametrize("case", [(2, 6, 64, 4), (4, 5, 32, 4), (2, 4, 64, 4), (3, 9, 32, 4)])        # N, Ti, H, kt: Wo = 32 / 16; To = 3, 2, 1, 6
-def test_overlapped_first_layer_forward_equals_the_weight_stationary_kernel(hl, case):
-    """Round 6: fprop_c4_ab_kernel (tile code 0 on the 3-D first layer in a -DMCG_C4_AB=1 build: two wave groups half a frame step
-    apart, filters in registers, a ring of kt + 1 slabs -- measured slower and switched off, see the kernel's comment) against
-    fprop_c4_kernel (tile code 6) -- the same additions in the same order: BIT-identical; in the shipped build both codes run
-    fprop_c4_kernel and the test pins that kernel -- and against the float64 oracle, for the plain store, the first layer's leaky_relu + injected-noise + sign-bit epilogue and
-    its in-kernel Philox form (model/net.py:148-149,189-190), one and two noise groups."""
+def test_weight_stationary_first_layer_forward_via_tile_codes_0_and_6(hl, case):
+    """The first layer's weight-stationary forward (fprop_c4_kernel), reached through tile code 0 (the library's choice) and tile
+    code 6: the two codes dispatch to the same kernel, so every launch is BIT-identical between them.  Against the float64 oracle:
+    the plain store, the leaky_relu + injected-noise epilogue and its sign bits (model/net.py:148-149,189-190); the in-kernel
+    Philox form and two noise groups through the equality of the two codes."""
     N, Ti, H, kt = case
     Ci, Co = 3, 64
     rng = np.random.RandomState(900 + Ti * H)
