@@ -7,14 +7,20 @@ three-iteration check, and the single-channel (Moving-MNIST shape) networks.
   against oracle.functions.conv3d_* (reference arithmetic: model/net.py:133-136,174-178, 45-48);
 * free running: three update_core iterations in which the device keeps its OWN parameters and Adam state, weights
   rel-L2 <= 1e-4 against the oracle (SURVEY 8c; reference model/updater.py:111-113);
-* C = 1: BASELINE configs[0] names 16x1x64x64 clips."""
+* C = 1: BASELINE configs[0] names 16x1x64x64 clips (SURVEY Q12);
+* production-size parity (second half of the module): every conv launch of the benchmarked step at batch 32 / 128 / 256 with the
+  shipped table's tile code, the fused epilogues and the small kernels at their real row counts, element by element against float64
+  on the device (tests/ref64.py), global rel-L2 and the worst 256-row x 64-column block; figures in profiles/production_parity.md."""
 import json
 import os
+import sys
+import time
 
 import numpy as np
 import pytest
 import torch
 
+import ref64
 from oracle import functions as F
 from oracle import net as onet
 from oracle import updater as oupd
@@ -253,3 +259,1011 @@ def test_single_channel_networks_and_step(pkg):
                 assert rel_l2(got[k], refg[k]) < gtol, (name, k, ref['min_margin'])
     errs = {name: _params_rel_l2(net, p) for name, net, p in (('G', G, gen), ('D_I', DI, di), ('D_V', DV, dv))}
     assert all(e < (1e-4 if tight else 1e-2) for e in errs.values()), errs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Production-batch parity: every conv launch of the benchmarked step, with the shipped table's tile code, element by
+# element against float64 (tests/ref64.py: tap-wise, on the device, none of the package's kernels involved)
+# ------------------------------------------------------------------------------------------------------------------
+BF16_STORE_EPS = 2.0 ** -9     # allowed on top for a launch that stores bf16: round to nearest is off by 2^-8 of the value at most and
+                               # by 2^-8 / sqrt(3) x (the mean position in the binade) = 1.7e-3 rms -- below 2^-9 = 1.95e-3
+PARITY_CONFIGS = [("f32", 32), ("f32x3", 32), ("bf16", 32), ("f32x3", 128), ("bf16", 256)]
+PARITY_IDS = ["f32-b32", "f32x3-b32-headline", "bf16-b32", "f32x3-b128-configs4-share", "bf16-b256-configs2"]
+CONV_KINDS = ("fprop", "dgrad", "wgrad", "split-fprop", "split-dgrad", "split-wgrad")
+
+
+def _step_layers(batch):
+    """the geometries ONE iteration at this per-GPU batch launches (tests/test_gpu_properties.py): D on 2 * batch clips (real and
+    fake as one call) and on batch alone (G's loss), G on 16 * batch frames.  -> (name, N, T, H, Ci, Co, kt, ci_real)"""
+    tools = os.path.join(ROOT, 'tools')
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import bench_layers
+    seen, out = set(), []
+    for lay_ in bench_layers.layers(batch) + [l for l in bench_layers.layers(2 * batch) if l[0].startswith('D_')]:
+        if lay_[1:7] not in seen:
+            seen.add(lay_[1:7])
+            out.append(lay_)
+    return out
+
+
+def _shipped_table():
+    return {tuple(k): int(v) for k, v in json.load(open(os.path.join(ROOT, 'mocogan-chainer_amd', 'tuned_tiles_mi355x.json')))}
+
+
+def _family_precisions(family, batch):
+    """the mcg_conv_geom.precision values a network of this configuration launches (table keys: index 9).  An 'f32x3' network
+    runs the fp32 kernels on its 4-channel layers and wherever the table's split-<pass> entry says 0; the fp32 entries at batch
+    32 belong to the f32 configuration, at batch 128 no other configuration launches them."""
+    if family == "f32":
+        return {0}
+    if family == "f32x3":
+        return {3} if batch == 32 else {0, 3}
+    return {1, 2, 4}
+
+
+def _in_scope(table, family, batch):
+    geoms = {(l[1], l[2], l[3], l[3], l[4], l[5], l[6]) for l in _step_layers(batch)}
+    precs = _family_precisions(family, batch)
+    out = []
+    for key in table:
+        if key[0] not in CONV_KINDS or tuple(key[1:8]) not in geoms or key[8] not in (0, batch):
+            continue                                                # (x_perm_n = n: G.dc5 writing n clips -- another batch's entry otherwise)
+        if key[0].startswith('split-'):
+            if family == "f32x3":
+                out.append(key)
+        elif key[9] in precs:
+            out.append(key)
+    return out
+
+
+def _parity_table_row(row):
+    """MCG_PARITY_TABLE=<file>: the figures as markdown rows (tools/parity_report.py turns them into profiles/production_parity.md)"""
+    path = os.environ.get('MCG_PARITY_TABLE')
+    if path:
+        with open(path, 'a') as f:
+            f.write("| " + " | ".join(str(c) for c in row) + " |\n")
+
+
+class _Parity:
+    """one configuration's bookkeeping: table lookups, figures, refusals.  A key counts as USED only once a launch made with it has
+    been compared with float64 (judge); a lookup whose launch is refused or skipped is dropped."""
+
+    def __init__(self, hl, cfg_id, table):
+        self.hl, self.cfg, self.table = hl, cfg_id, table
+        self.used, self.missing, self.failed = set(), [], []
+        self.checked = self.refused = 0
+        self.relaxed = []
+        self._pending = []
+
+    def code(self, kind, g, extra=()):
+        key = self.hl._geom_key(kind, g, extra)
+        self._pending.append(key)
+        if key not in self.table:
+            if key not in self.missing:
+                self.missing.append(key)
+            return 0                                                # (reported below; never tuned here)
+        return self.table[key]
+
+    def drop(self):
+        self._pending = []
+
+    def geom(self, g, code):
+        gg = type(g).from_buffer_copy(g)
+        gg.tile = code
+        return gg
+
+    def judge(self, layer, kind, form, code, got, ref, tol, cols=None, f32_err=None, note=""):
+        """tol: the project's tolerance for the quantity (+ the bf16 store's 2^-9 where the launch stores bf16).  If the launch
+        misses it while its error is spread evenly (worst block within 4 x the global figure), what plain float32 gives on the same
+        data is measured (f32_err: the tap-wise loops in float32 against float64) and max(tol, 4 x that) allowed -- the factor for
+        a different summation order; never a bound from the kernel's own output."""
+        rep = ref64.compare(got, ref, cols=cols)
+        bound = tol
+        if not rep.ok(tol) and rep.block <= ref64.BLOCK_FACTOR * rep.rel and f32_err is not None:
+            e32 = f32_err()
+            bound = max(tol, 4 * e32)
+            self.relaxed.append((layer, kind, form, code, rep.rel, e32, bound))
+            note += " [float32 loops on the same data: %.2e -> bound %.2e]" % (e32, bound)
+        ok = rep.ok(bound)
+        print("%-26s %-12s %-6s %-6s code %-5d %s%s%s" % (self.cfg, layer, kind, form, code, rep, note, "" if ok else "   <-- FAILS (bound %.2e)" % bound))
+        _parity_table_row((self.cfg, layer, kind + note.split(' [')[0], form, code, "%.2e" % rep.rel, "%.2e" % rep.block))
+        self.checked += 1
+        self.used.update(self._pending)
+        self._pending = []
+        if not ok:
+            self.failed.append("%s %s %s code %d: %s (bound %.2e, blocks %.2e)" % (layer, kind, form, code, rep, bound, ref64.BLOCK_FACTOR * bound))
+
+
+def _seeded(gen, shape, scale=1.0, bf16_values=False, zero_last=False):
+    t = torch.randn(shape, device='cuda', generator=gen)
+    if scale != 1.0:
+        t *= scale
+    if bf16_values:
+        t = t.to(torch.bfloat16).float()                            # bf16-representable: products exact, the result fp32 accumulation only
+    if zero_last:
+        t[..., 3] = 0                                               # the clip's padded channel
+    return t
+
+
+def _sign_words(sign):
+    """bool [M][C] (C a multiple of 32) -> the int32 words of a sign-bit mask, bit c & 31 of word c >> 5"""
+    M, C = sign.shape
+    words = (sign.view(M, C // 32, 32).long() << torch.arange(32, device=sign.device)).sum(-1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+
+
+class _LayerCase:
+    """One layer of one configuration: seeded operands on the device, their float64 results, and one method per launch form.
+    Every method looks the launch's tile code up in the table (unless one is given), launches, and has P.judge compare."""
+
+    def __init__(self, P, hl, gen, layer, exact):
+        self.P, self.hl, self.gen, self.exact = P, hl, gen, exact
+        name, N, T, H, Ci, Co, kt, ci_real = layer
+        self.name, self.dims, self.ci_real = "%s@%d" % (name, N), (N, T, H, Ci, Co, kt), ci_real
+        c4 = Ci == 4
+        self.x = _seeded(gen, (N, T, H, H, Ci), bf16_values=exact, zero_last=c4)
+        self.w = _seeded(gen, (Co, kt, 4, 4, Ci), scale=(kt * 16 * ci_real) ** -0.5, bf16_values=exact, zero_last=c4)
+        self.b = _seeded(gen, (Co,), scale=0.3)
+        self.bx = _seeded(gen, (Ci,), scale=0.3)                    # the bias of the deconvolution (conv-form dgrad)
+        self.g0 = hl.make_geom(N, T, H, H, Ci, Co, kt, ci_valid=ci_real)
+        self.gy = _seeded(gen, (N, self.g0.To, self.g0.Ho, self.g0.Wo, Co), bf16_values=exact)
+        self.y_ref = ref64.fprop(self.x, self.w, self.b)
+        self.gx_ref = ref64.dgrad(self.gy, self.w, T, H, H)
+        self.dw_ref2 = 2 * ref64.wgrad(self.x, self.gy, kt)
+        self._ops, self._f32 = {}, {}
+
+    def ops(self, form):
+        """(x side, filter as fprop / wgrad read it, filter as dgrad reads it, y side) in the operand form of the precision"""
+        if form not in self._ops:
+            bf = torch.bfloat16
+            N, T, H, Ci, Co, kt = self.dims
+            if form == "bf16s":
+                w16 = self.w.to(bf)
+                self._ops[form] = (self.x.to(bf), w16, w16, self.gy.to(bf))
+            elif form == "bf16y":
+                self._ops[form] = (self.x, self.w, self.w, self.gy.to(bf))
+            elif form == "f32x3":
+                sp = self.hl.split_planes
+                self._ops[form] = (sp(self.x), sp(self.w), sp(self.w, run=16 * kt * 16 * Ci), sp(self.gy))
+            else:
+                self._ops[form] = (self.x, self.w, self.w, self.gy)
+        return self._ops[form]
+
+    def f32_err(self, kind):
+        """what the tap-wise loops give in plain float32 on this layer's data (rel-L2 against float64), computed on demand"""
+        def run():
+            if kind not in self._f32:
+                N, T, H, Ci, Co, kt = self.dims
+                f32 = torch.float32
+                if kind == "fprop":
+                    r = ref64.compare(ref64.fprop(self.x, self.w, self.b, dtype=f32), self.y_ref)
+                elif kind == "dgrad":
+                    r = ref64.compare(ref64.dgrad(self.gy, self.w, T, H, H, dtype=f32), self.gx_ref)
+                else:
+                    r = ref64.compare(2 * ref64.wgrad(self.x, self.gy, kt, dtype=f32), self.dw_ref2, cols=kt * 16 * Ci)
+                self._f32[kind] = r.rel
+            return self._f32[kind]
+        return run
+
+    def fprop(self, g, form, out16=False, code=None, note=""):
+        hl, P = self.hl, self.P
+        xs, wf, _, _ = self.ops(form)
+        y = torch.full(self.y_ref.shape, 3.0, device='cuda', dtype=torch.bfloat16 if out16 else torch.float32)
+        if code is None:
+            code = P.code("fprop", g, hl._ep_key(g, None, y))
+        hl.conv_fprop(P.geom(g, code), xs, wf, self.b, y)
+        P.judge(self.name, "fprop", form, code, y, self.y_ref, FWD_TOL + (BF16_STORE_EPS if out16 else 0), f32_err=self.f32_err("fprop"),
+                note=note or (" (bf16 store)" if out16 else ""))
+        return code
+
+    def dgrad(self, g, form, out16=False, code=None, note=""):
+        hl, P = self.hl, self.P
+        _, _, wd, ys = self.ops(form)
+        gx = torch.full(self.x.shape, 7.0, device='cuda', dtype=torch.bfloat16 if out16 else torch.float32)
+        if code is None:
+            code = P.code("dgrad", g, (hl.ACT_NONE, 0) + hl._ep_key(g, None, gx))
+        hl.conv_dgrad(P.geom(g, code), ys, wd, None, gx)
+        P.judge(self.name, "dgrad", form, code, gx, self.gx_ref, BWD_TOL + (BF16_STORE_EPS if out16 else 0), f32_err=self.f32_err("dgrad"),
+                note=note or (" (bf16 store)" if out16 else ""))
+        return code
+
+    def wgrad(self, g, form):
+        hl, P = self.hl, self.P
+        xs, _, _, ys = self.ops(form)
+        dw = torch.zeros_like(self.w)
+        code = P.code("wgrad", g)
+        hl.conv_wgrad(P.geom(g, code), xs, ys, dw)
+        hl.conv_wgrad(P.geom(g, code), xs, ys, dw)                  # accumulates
+        kt, Ci = self.dims[5], self.dims[3]
+        P.judge(self.name, "wgrad", form, code, dw, self.dw_ref2, BWD_TOL, cols=kt * 16 * Ci, f32_err=self.f32_err("wgrad"), note=" (x2)")
+
+    # ---- the launch forms a bf16 network keys separately: fused epilogue and output type ('ep', sums, mask-in, bf16 store) ----
+    def _stats_of_partials(self, part, ep, ref, Cn, groups, out16, what):
+        """bn_stats_from_partials' mean / inv_std of every group against float64 statistics of the reference (after the same rounding
+        where the launch stores bf16: the sums are those of the values as stored), 1e-5"""
+        hl = self.hl
+        M = ref.numel() // Cn
+        mg = M // groups
+        one, zero = torch.ones(Cn, device='cuda'), torch.zeros(Cn, device='cuda')
+        ws = torch.empty(hl.bn_workspace_floats(max(Cn, 64)), device='cuda')
+        for gi in range(groups):
+            r = ref.reshape(M, Cn)[gi * mg:(gi + 1) * mg]
+            if out16:
+                r = r.to(torch.bfloat16).double()
+            stats = torch.full((4 * Cn,), float('nan'), device='cuda')
+            hl.bn_stats_from_partials(mg, Cn, part[gi * 2 * Cn:], ep.n_slots, ep.slot_stride, one, zero, stats, None, None, ws)
+            e_m, e_s = _t_rel(stats[:Cn], r.mean(0)), _t_rel(stats[Cn:2 * Cn], (r.var(0, unbiased=False) + 2e-5).rsqrt())
+            print("%-26s %-12s %s group %d/%d slots %d: mean %.1e inv_std %.1e" % (self.P.cfg, self.name, what, gi, groups, ep.n_slots, e_m, e_s))
+            if not (e_m < 1e-5 and e_s < 1e-5):
+                self.P.failed.append("%s %s group %d/%d: statistics from the partial sums: mean %.2e inv_std %.2e" % (self.name, what, gi, groups, e_m, e_s))
+
+    def epilogue_form(self, g, kind, sums, mask, out16, groups):
+        """one launch in the form ('ep', sums, mask, out16) of the table, as the networks make it: SUMS_STATS (fprop with D's groups;
+        conv-form dgrad of G with the deconvolution's bias), sign bits in with or without the column sums (dgrad of dc2)"""
+        hl, P = self.hl, self.P
+        N, T, H, Ci, Co, kt = self.dims
+        xs, wf, wd, ys = self.ops("bf16s")
+        extra = ('ep', sums, mask, int(out16))
+        dt = torch.bfloat16 if out16 else torch.float32
+        eps16 = BF16_STORE_EPS if out16 else 0
+        if kind == "fprop" and (sums, mask) == (hl.SUMS_STATS, 0):
+            code = P.code("fprop", g, extra)
+            part = torch.full((hl.epilogue_part_floats(g, "fprop", groups),), float('nan'), device='cuda')
+            ep = hl.epilogue(sums=hl.SUMS_STATS, groups=groups, part=part, out_bf16=out16)
+            y = torch.full(self.y_ref.shape, 3.0, device='cuda', dtype=dt)
+            fused = hl.conv_fprop(P.geom(g, code), xs, wf, self.b, y, ep=ep)        # (False: the code splits K, the plain launch ran)
+            what = "fprop statistics epilogue, %d group%s%s%s" % (groups, "s"[:groups - 1], ", bf16 store" if out16 else "", "" if fused else ", K split: not fused")
+            P.judge(self.name, "fprop", "bf16s", code, y, self.y_ref, FWD_TOL + eps16, note=" (%s)" % what)
+            if fused:
+                self._stats_of_partials(part, ep, self.y_ref, Co, groups, out16, what)
+        elif kind == "dgrad" and (sums, mask) == (hl.SUMS_STATS, 0):
+            code = P.code("dgrad", g, (hl.ACT_NONE, 0) + extra)
+            part = torch.full((hl.epilogue_part_floats(g, "dgrad", 1),), float('nan'), device='cuda')
+            ep = hl.epilogue(sums=hl.SUMS_STATS, groups=1, part=part, out_bf16=out16)
+            out = torch.full(self.x.shape, 7.0, device='cuda', dtype=dt)
+            ref = self.gx_ref + self.bx.double()
+            fused = hl.conv_dgrad(P.geom(g, code), ys, wd, self.bx, out, ep=ep)
+            what = "dgrad + bias, statistics epilogue%s%s" % (", bf16 store" if out16 else "", "" if fused else ", K split: not fused")
+            P.judge(self.name, "dgrad", "bf16s", code, out, ref, BWD_TOL + eps16, note=" (%s)" % what)
+            if fused:
+                self._stats_of_partials(part, ep, ref, Ci, 1, out16, what)
+        elif kind == "dgrad" and mask and sums in (hl.SUMS_NONE, hl.SUMS_COL):
+            code = P.code("dgrad", g, (hl.ACT_NONE, 0) + extra)
+            M = self.gx_ref.numel() // Ci
+            sign = torch.rand((M, Ci), device='cuda', generator=self.gen) > 0.4
+            part = torch.full((hl.epilogue_part_floats(g, "dgrad", 1),), float('nan'), device='cuda') if sums else None
+            maskd = _sign_words(sign)                               # (kept alive until the launch is queued: the epilogue holds its address)
+            ep = hl.epilogue(mask_in=maskd, sums=sums, groups=1, part=part, out_bf16=out16)
+            out = torch.full(self.x.shape, 7.0, device='cuda', dtype=dt)
+            assert hl.conv_dgrad(P.geom(g, code), ys, wd, None, out, ep=ep, must_fuse=True)     # (must_fuse drops a K split: code % 1000 runs)
+            slope = torch.where(sign, torch.ones((), dtype=torch.float64, device='cuda'), torch.full((), 0.2, dtype=torch.float64, device='cuda'))
+            want = self.gx_ref * slope.view(self.gx_ref.shape)
+            P.judge(self.name, "dgrad", "bf16s", code % 1000, out, want, BWD_TOL + eps16,
+                    note=" (sign bits in%s%s)" % (", column sums out" if sums else "", ", bf16 store" if out16 else ""))
+            if sums:
+                db = torch.ones(Ci, device='cuda')
+                hl.colsum_from_partials(Ci, part, ep.n_slots, ep.slot_stride, db, torch.empty(hl.bn_workspace_floats(max(Ci, 64)), device='cuda'))
+                col = want.reshape(M, Ci).sum(0)
+                e_c = float((db.double() - (1 + col)).abs().max())
+                print("%-26s %-12s bias gradient from the partial sums (%d slots): max abs error %.2e, max |sum| %.1f" % (P.cfg, self.name, ep.n_slots, e_c, float(col.abs().max())))
+                if not e_c < 1e-4 * max(1.0, float(col.abs().max())):
+                    P.failed.append("%s: bias gradient from the partial sums off by %.2e" % (self.name, e_c))
+        else:
+            raise AssertionError("the table holds a launch form this test does not know: %r" % ((kind,) + extra,))
+
+
+def _forms_of(family, c4):
+    if family == "f32":
+        return ["f32"]
+    if family == "f32x3":
+        return ["f32"] if c4 else ["f32x3", "f32"]
+    return ["bf16", "bf16y"] if c4 else ["bf16s", "bf16"]
+
+
+@pytest.mark.parametrize("family,batch", PARITY_CONFIGS, ids=PARITY_IDS)
+def test_production_batch_conv_launches_match_float64(pkg, family, batch):
+    """Every conv launch of one bench.py iteration at its production size -- D on 2 * batch and batch clips, G on 16 * batch frames,
+    true channel widths -- with the tile code the SHIPPED table holds for it (forced through mcg_conv_geom.tile: no tuning runs
+    here; a key the table lacks is reported and launched with code 0), against tests/ref64.py in float64 on the device.  Checked
+    per launch: global rel-L2 < FWD_TOL (fprop) / BWD_TOL (dgrad, wgrad), and the worst 256-row x 64-column block < 4 x that.
+
+    Forms: f32: fp32 operands.  f32x3: split operands wherever the form exists (and the fp32 form where the table's split-<pass>
+    entry is not 1, or -- at batch 128, which has no f32 configuration -- everywhere); general fp32 values, so that the mid and lo
+    planes carry data.  bf16: what a bf16 network launches (nets._stored16, nets.DisNet / GenNet): 'bf16s' on the wide layers with
+    the fp32 and the bf16 store, 'bf16' / 'bf16y' on the 4-channel layers, plus 'bf16' on the wide layers (the table's entries of
+    the A/B switch that keeps tensors fp32); the inputs are bf16-representable, so the products are exact, the result differs from
+    float64 by fp32 accumulation only and the launches are held to the fp32 tolerances.  A launch that STORES bf16 is allowed the
+    2^-9 of that store on top (rounding the reference instead would flip wherever the fp32 sum and the float64 sum straddle a bf16
+    boundary); where the table holds another tile code for the bf16 store than for the fp32 store, that code is also launched
+    with the fp32 store and held to the tight bound.
+    bf16 networks key a launch by its fused epilogue and output type as well: every such entry of the table for the layer
+    (statistics epilogue of fprop and of G's conv-form dgrad, sign bits in with and without the column sums) is launched in that
+    form (_LayerCase.epilogue_form), the convolution's output compared as above and the sums against float64 (1e-5 / 1e-4, the
+    bounds of the small-size epilogue tests).
+    fprop with a bias; dgrad plain, for D's first layers also accumulating (D_I.dc1: onto frame t of a non-zero clip gradient
+    through x_stride0, as step.py does), for G.dc5 also in clip order (x_perm_n) plain and with bias + tanh; wgrad twice into one dw.
+    At the end: EVERY fprop / dgrad / wgrad / split-* entry of the table whose geometry and precision this configuration launches
+    was taken by a launch that was compared with float64 -- no exemptions."""
+    hl, lay, _, _ = pkg
+    table = _shipped_table()
+    cfg_id = "%s-b%d" % (family, batch)
+    P = _Parity(hl, cfg_id, table)
+    hl.reset_tuning()
+    hl.use_pretuned_table()
+    assert hl.tile_choices() == table, "hiplib loads another table than the file this test reads"
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(9000 + batch + len(family))
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    t_start = time.time()
+    try:
+        for layer in _step_layers(batch):
+            name, N, T, H, Ci, Co, kt, ci_real = layer
+            c4 = Ci == 4
+            L = _LayerCase(P, hl, gen, layer, family == "bf16")
+            for form in _forms_of(family, c4):
+                g = hl.with_precision(L.g0, form)
+                split = form == "f32x3"
+                for kind in ("fprop", "dgrad", "wgrad"):
+                    P.drop()
+                    if form == "bf16y" and kind == "fprop":
+                        continue                                    # (the form names the y side as an INPUT: wgrad, dgrad)
+                    decided = None
+                    if family == "f32x3" and not c4 and hl.split_covers(kind, L.g0):
+                        decided = P.code('split-' + kind, L.g0)     # 1: the network launches the split form of this pass
+                    if split and not hl.split_covers(kind, L.g0):
+                        continue
+                    if form == "f32" and family == "f32x3" and batch == 32 and decided == 1:
+                        continue                                    # (the split form is what runs; the f32 configuration holds the fp32 launch)
+                    try:
+                        if kind == "wgrad":
+                            L.wgrad(g, form)
+                            continue
+                        launch = L.fprop if kind == "fprop" else L.dgrad
+                        c32 = launch(g, form)
+                        if form == "bf16s":
+                            c16 = launch(g, form, out16=True)
+                            if c16 != c32:                          # the bf16 store's tile code, stored in fp32: held to the tight bound
+                                launch(g, form, code=c16, note=" (the bf16 store's code, fp32 store)")
+                            groups = 2 if name.startswith("D_") and N == 2 * batch else 1
+                            for key in sorted(k for k in table if k[0] == kind and k[:10] == hl._geom_key(kind, g) and 'ep' in k):
+                                sums, mask, o16 = key[key.index('ep') + 1:]
+                                if sums or mask:
+                                    L.epilogue_form(g, kind, sums, mask, bool(o16), groups)
+                        if kind == "dgrad" and c4 and name.startswith("D_") and form != "bf16y":     # (a bf16 network accumulates from an fp32 y)
+                            _accumulating_first_layer_dgrad(P, hl, gen, L.name, g, L.ops(form)[3], L.ops(form)[2], L.gx_ref, L.f32_err("dgrad"), form)
+                        if kind == "dgrad" and c4 and name.startswith("G."):
+                            _clip_order_dgrad(P, hl, L.name, g, L.ops(form)[3], L.ops(form)[2], L.bx, L.gx_ref, batch, form, ci_real)
+                    except hl.McgError as e:
+                        # a geometry whose split form the library refuses in this pass: the network then runs the pass on the fp32
+                        # kernels (nets._c*); counted and bounded below, as in tests/test_gpu_properties.py.  Anything else is an error.
+                        assert split, (name, kind, form, str(e))
+                        P.refused += 1
+                        P.drop()
+                        print("%-26s %-12s %-6s %-6s refused: %s" % (cfg_id, L.name, kind, form, e))
+            del L
+            torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        secs, peak = time.time() - t_start, torch.cuda.max_memory_allocated() / 2.0 ** 30
+        print("%s: %d launches compared, %d split-form refusals, %.1f s, peak device memory %.1f GiB" % (cfg_id, P.checked, P.refused, secs, peak))
+        _parity_table_row((cfg_id, "(total)", "%d launches" % P.checked, "", "", "%.1f s" % secs, "%.1f GiB" % peak))
+        # (passes the step itself never launches at that N -- D's first-layer input gradient on 2 * batch clips, say -- are among them)
+        print("%s: %d launches had no table entry and ran with code 0: %s" % (cfg_id, len(P.missing), "; ".join(",".join(str(v) for v in k) for k in P.missing)))
+        for r in P.relaxed:
+            print("%s: bound from the float32 loops: %r" % (cfg_id, r))
+        assert not P.failed, "\n".join(P.failed)
+        assert P.checked >= 24 and P.refused <= P.checked // 3, (P.checked, P.refused)
+        scope = _in_scope(table, family, batch)
+        assert len(scope) >= 24, len(scope)
+        left = [k for k in scope if k not in P.used]
+        assert not left, "table entries of this configuration that no compared launch took:\n" + "\n".join(repr(k) for k in left)
+        print("%s: all %d entries of the table for this configuration were launched and compared with float64" % (cfg_id, len(scope)))
+    finally:
+        hl.reset_tuning()
+        torch.cuda.empty_cache()
+
+
+def _accumulating_first_layer_dgrad(P, hl, gen, name, g, gy, w, gx_ref, f32_err, form):
+    """dgrad with accumulate=True onto a non-zero tensor.  D_I.dc1 as step.py launches it: the frame gradient lands on frame t of
+    D_V's clip gradient [N][16][H][W][4] through x_stride0; the other frames stay bit for bit.  D_V.dc1: onto a dense tensor."""
+    N, H, C = g.N, g.Hi, g.Ci
+    code = P.code("dgrad", g, (hl.ACT_NONE, 1))
+    if g.kt == 1:
+        T, t = 16, 5
+        base = torch.randn((N, T, H, H, C), device='cuda', generator=gen)
+        base[..., 3] = 0
+        before = base.clone()
+        gg = hl.make_geom(N, 1, H, H, C, g.Co, 1, x_stride0=T * H * H * C, precision=g.precision, ci_valid=g.ci_valid)
+        hl.conv_dgrad(P.geom(gg, code), gy, w, None, base[:, t], accumulate=True)
+        P.judge(name, "dgrad", form, code, base[:, t:t + 1], before[:, t:t + 1].double() + gx_ref, BWD_TOL, f32_err=f32_err, note=" (+= frame view)")
+        keep = [i for i in range(T) if i != t]
+        assert torch.equal(base[:, keep], before[:, keep]), "accumulating into frame %d touched another frame" % t
+    else:
+        base = torch.randn(gx_ref.shape, device='cuda', generator=gen)
+        base[..., 3] = 0
+        before = base.clone()
+        hl.conv_dgrad(P.geom(g, code), gy, w, None, base, accumulate=True)
+        P.judge(name, "dgrad", form, code, base, before.double() + gx_ref, BWD_TOL, f32_err=f32_err, note=" (+=)")
+
+
+def _clip_order_dgrad(P, hl, name, g, gy, w, bias, gx_ref, n, form, ci_real):
+    """G's last deconvolution writes the clip tensor [n][T][H][W][4] directly (frame f = t * n + clip lands at clip, time t:
+    nets.GenNet._geom), plain and with bias + tanh in the store"""
+    F_, H, C = g.N, g.Hi, g.Ci
+    T = F_ // n
+    gg = hl.make_geom(F_, 1, H, H, C, g.Co, 1, x_stride0=T * H * H * C, x_perm_n=n, x_stride1=H * H * C, precision=g.precision, ci_valid=ci_real)
+    bias4 = torch.zeros(C, device='cuda')
+    bias4[:ci_real] = bias[:ci_real]
+    ref_clip = gx_ref.view(T, n, H, H, C).permute(1, 0, 2, 3, 4)
+    for act, ref in ((hl.ACT_NONE, ref_clip.contiguous()), (hl.ACT_TANH, torch.tanh(ref_clip + bias4.double()))):
+        if act and form == "bf16y":
+            continue                                                # (a bf16 y is read by the MFMA kernel, which carries no activation: nets.GenNet.forward)
+        out = torch.full((n, T, H, H, C), 7.0, device='cuda')
+        code = P.code("dgrad", gg, (act, 0))
+        hl.conv_dgrad(P.geom(gg, code), gy, w, bias4 if act else None, out, act=act)
+        P.judge(name, "dgrad", form, code, out, ref, BWD_TOL, note=" (clip order%s)" % (", bias + tanh" if act else ""))
+        del out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The small kernels at the sizes the benchmarked step gives them (tests/test_gpu_ops.py holds them to the same bounds at a few
+# thousand rows: one trip of their grid-stride loops, partial sums far from the MAX_PART cap)
+# ------------------------------------------------------------------------------------------------------------------
+def _t_rel(got, ref):
+    """rel-L2 of device tensors, in float64 on the device"""
+    ref = ref.double()
+    return float(torch.linalg.vector_norm(got.double().reshape(ref.shape) - ref) / torch.linalg.vector_norm(ref).clamp_min(1e-300))
+
+
+def _off_the_kink(y, gamma, beta, bf16_values):
+    """y [M][C] with the few elements whose BatchNorm output gamma * x_hat + beta lies within KINK of zero moved by 0.05: among 1e8
+    values some hundred lie within fp32 rounding of the activation's kink, where the fp32 and the float64 sign legitimately differ
+    -- each such element would move its channel's dbeta / dgamma by 1e-3 of their size.  The inputs avoid the kink instead of the
+    comparison excusing it; returns (y, float64 x_hat, inv_std, BatchNorm output)."""
+    for _ in range(4):
+        y64 = y.double()
+        mean = y64.mean(0)
+        inv_std = (y64.var(0, unbiased=False) + 2e-5).rsqrt()
+        x_hat = (y64 - mean) * inv_std
+        bn = gamma.double() * x_hat + beta.double()
+        near = bn.abs() < KINK
+        if not bool(near.any()):
+            return y, x_hat, inv_std, bn
+        y = torch.where(near, y + 0.05, y)
+        if bf16_values:
+            y = y.to(torch.bfloat16).float()
+    raise AssertionError("could not move the BatchNorm inputs off the kink")
+
+
+# (name, rows M, channels C, activation): BatchNorm inputs of the step -- D_V.dc2 / dc3 outputs at 64 and 512 clips, G.dc4's at 512 frames
+BN_REAL_SHAPES = [("D_V.dc2@64", 64 * 10 * 16 * 16, 128, 2), ("D_V.dc2@512", 512 * 10 * 16 * 16, 128, 2),
+                  ("D_V.dc3@64", 64 * 7 * 8 * 8, 256, 2), ("D_V.dc3@512", 512 * 7 * 8 * 8, 256, 2),
+                  ("G.dc4@512", 512 * 32 * 32, 64, 1)]
+KINK = 1e-5                     # as test_fprop_epilogue_statistics_and_first_layer: away from the kink the sign is unambiguous
+
+
+@pytest.mark.parametrize("io", ["f32", "bf16"])
+@pytest.mark.parametrize("shape", BN_REAL_SHAPES, ids=[s[0] for s in BN_REAL_SHAPES])
+def test_batchnorm_passes_at_production_rows(pkg, shape, io):
+    """bn_stats / bn_act_fwd / bn_act_bwd / colsum_acc at the (rows, channels) of the real step against float64 torch on the
+    device, bounds of tests/test_gpu_ops.py::test_batchnorm_activation_fwd_bwd (statistics 1e-5, forward FWD_TOL, backward
+    BWD_TOL, column sums 1e-5), the element-wise outputs also block by block (ref64.compare).
+    io = bf16: the element types a bf16 network passes -- y and the incoming gradient bf16 in memory (bf16-representable values,
+    so nothing is lost reading them), outputs fp32 (same bounds) and bf16 (the store's 2^-9 on top).
+    The inputs keep every BatchNorm output at least 1e-5 away from the activation's kink (_off_the_kink)."""
+    hl = pkg[0]
+    name, M, C, act = shape
+    b16 = io == "bf16"
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(M % 100003 + C)
+    y = torch.randn((M, C), device='cuda', generator=gen) * 1.7 + 0.3
+    g_out = torch.randn((M, C), device='cuda', generator=gen)
+    if b16:
+        y, g_out = y.to(torch.bfloat16).float(), g_out.to(torch.bfloat16).float()
+    noise = 0.2 * torch.randn((M, C), device='cuda', generator=gen)
+    gamma = 1 + 0.1 * torch.randn(C, device='cuda', generator=gen)
+    beta = 0.1 * torch.randn(C, device='cuda', generator=gen)
+    # float64 reference (oracle.functions.bn_train_fwd / bn_train_bwd: biased variance, eps added before both uses)
+    y, x_hat, inv_std, bn = _off_the_kink(y, gamma, beta, b16)
+    y64 = y.double()
+    mean = y64.mean(0)
+    var = y64.var(0, unbiased=False) + 2e-5
+    out_ref = (torch.where(bn >= 0, bn, 0.2 * bn) if act == 2 else bn.clamp_min(0)) + noise.double()
+    am_ref = 0.1 * mean
+    av_ref = 0.9 + 0.1 * (M / (M - 1.0)) * var
+    ws = torch.empty(hl.bn_workspace_floats(C), device='cuda')
+    stats = torch.full((4 * C,), float('nan'), device='cuda')
+    am, av = torch.zeros(C, device='cuda'), torch.ones(C, device='cuda')
+    hl.bn_stats(M, C, y, gamma, beta, stats, am, av, ws)
+    figs = {"mean": _t_rel(stats[:C], mean), "inv_std": _t_rel(stats[C:2 * C], inv_std), "avg_mean": _t_rel(am, am_ref), "avg_var": _t_rel(av, av_ref)}
+    print(name, io, "statistics", {k: "%.1e" % v for k, v in figs.items()})
+    assert all(v < 1e-5 for v in figs.values()), figs
+    y_in, g_in = (y.to(torch.bfloat16), g_out.to(torch.bfloat16)) if b16 else (y, g_out)
+    for out_dt in ((torch.float32, torch.bfloat16) if b16 else (torch.float32,)):
+        o16 = out_dt == torch.bfloat16
+        out = torch.full((M, C), 3.0, device='cuda', dtype=out_dt)
+        hl.bn_act_fwd(M, C, y_in, stats[2 * C:], act, out, addend=noise)
+        rep = ref64.compare(out, out_ref)
+        print(name, io, "bn_act_fwd -> %s:" % out_dt, rep)
+        assert rep.ok(FWD_TOL + (BF16_STORE_EPS if o16 else 0)), str(rep)
+        del out
+    # backward: Q5 -- the updated gamma; the mask is the sign of the BatchNorm output
+    ga_new = gamma * 1.01
+    g64 = g_out.double()
+    g_bn = torch.where(bn >= 0, g64, 0.2 * g64) if act == 2 else torch.where(bn > 0, g64, torch.zeros_like(g64))
+    gb_ref = g_bn.sum(0)
+    gg_ref = (g_bn * x_hat).sum(0)
+    gx_ref = (ga_new.double() * inv_std) * (g_bn - (x_hat * gg_ref + gb_ref) / M)
+    del g_bn, x_hat, out_ref
+    for out_dt in ((torch.float32, torch.bfloat16) if b16 else (torch.float32,)):
+        o16 = out_dt == torch.bfloat16
+        gx = torch.full((M, C), 7.0, device='cuda', dtype=out_dt)
+        dg, db = torch.ones(C, device='cuda'), torch.ones(C, device='cuda')
+        hl.bn_act_bwd(M, C, g_in, y_in, stats, ga_new, act, gx, dg, db, ws)
+        rep = ref64.compare(gx, gx_ref)
+        e_g, e_b = _t_rel(dg, gg_ref + 1), _t_rel(db, gb_ref + 1)
+        print(name, io, "bn_act_bwd -> %s:" % out_dt, rep, "dgamma %.1e dbeta %.1e" % (e_g, e_b))
+        assert rep.ok(BWD_TOL + (BF16_STORE_EPS if o16 else 0)), str(rep)
+        assert e_g < BWD_TOL and e_b < BWD_TOL, (e_g, e_b)
+        del gx
+    # the form without BatchNorm (D's first layer: leaky ReLU on y itself -- its sign is exact) and the column sums
+    gx = torch.full((M, C), 7.0, device='cuda')
+    hl.bn_act_bwd(M, C, g_in, y_in, None, None, hl.ACT_LRELU, gx, None, None, ws)
+    rep = ref64.compare(gx, torch.where(y64 >= 0, g64, 0.2 * g64))
+    assert rep.ok(1e-6), str(rep)
+    cs = torch.ones(C, device='cuda')
+    hl.colsum_acc(M, C, g_out, cs, ws)
+    e_c = _t_rel(cs, g64.sum(0) + 1)
+    print(name, io, "no-BN backward:", rep, "colsum_acc %.1e" % e_c)
+    assert e_c < 1e-5, e_c
+
+
+@pytest.mark.parametrize("N", [32, 256, 512, 600])
+@pytest.mark.parametrize("C,with_ce", [(1, False), (7, False), (7, True)])
+def test_losses_at_production_batches(pkg, N, C, with_ce):
+    """loss_dis / loss_gen at the step's N (32; 256 and 512: the bf16 step, several trips of the kernels' n += NT loop) and at one
+    N that is no multiple of the block (600), normal and infogan; the oracle and bounds of tests/test_gpu_ops.py::test_losses"""
+    hl = pkg[0]
+    rng = np.random.RandomState(C * 1000 + N)
+    model = 'infogan' if C == 7 else 'normal'
+    yr, yf = rng.randn(N, C, 1, 1, 1) * 3, rng.randn(N, C, 1, 1, 1) * 3
+    tr, tf = rng.randint(0, 6, N), rng.randint(0, 6, N)
+    l_ref, gr_ref, gf_ref = oupd.loss_dis(model, with_ce, yr, yf, tr, tf)
+    loss = torch.empty(1, device="cuda")
+    gr, gf = torch.full((N, C), 3.0, device="cuda"), torch.full((N, C), 3.0, device="cuda")
+    hl.loss_dis(N, C, dev(yr.reshape(N, C)), dev(yf.reshape(N, C)), dev(tr, torch.int32), dev(tf, torch.int32), with_ce, loss, gr, gf)
+    assert abs(float(loss) - l_ref) < 1e-5
+    assert rel_l2(gr, gr_ref.reshape(N, C)) < 1e-5 and rel_l2(gf, gf_ref.reshape(N, C)) < 1e-5
+    if C == 7 and not with_ce:
+        return
+    yi = rng.randn(N, C, 1, 1) * 3
+    l_ref, gi_ref, gv_ref = oupd.loss_gen(model, yi, yf, tf)
+    gi, gv = torch.full((N, C), 3.0, device="cuda"), torch.full((N, C), 3.0, device="cuda")
+    hl.loss_gen(N, C, dev(yi.reshape(N, C)), dev(yf.reshape(N, C)), dev(tf, torch.int32), C == 7, loss, gi, gv)
+    assert abs(float(loss) - l_ref) < 1e-5
+    assert rel_l2(gi, gi_ref.reshape(N, C)) < 1e-5 and rel_l2(gv, gv_ref.reshape(N, C)) < 1e-5
+
+
+@pytest.mark.parametrize("N,dim_zl", [(32, 0), (32, 6), (256, 0), (256, 6)])
+def test_gru_sequence_at_production_batches(pkg, N, dim_zl):
+    """gru_seq_fwd / gru_seq_bwd (the reference's dim_zm = 10) at the step's batch sizes; oracle and bounds of
+    tests/test_gpu_ops.py::test_gru_sequence"""
+    hl, lay = pkg[0], pkg[1]
+    rng = np.random.RandomState(N + dim_zl)
+    T, dc, dz = 16, 50, 10
+    p = onet.init_generator(rng, dim_zl=dim_zl, dim_zm=dz, n_filters=2, dtype=F64)
+    gp = {k: (v + 0.1 * rng.randn(*v.shape)) for k, v in p.items() if k.startswith('g0/')}
+    draw = onet.gen_draw(rng, N, dim_zl=dim_zl, dim_zm=dz, dtype=F64)
+    gpo = {k[3:]: v for k, v in gp.items()}
+    zl = np.eye(dim_zl)[draw['labels']] if dim_zl else None
+    h, hs, caches = draw['h0'], [], []
+    for t in range(T):
+        et = draw['e'][t] if zl is None else np.concatenate((zl, draw['e'][t]), 1)
+        h, c = F.gru_step_fwd(gpo, h, et)
+        hs.append(h), caches.append(c)
+    z_ref = np.concatenate((np.tile(draw['zc'], (T, 1, 1)), np.stack(hs)), 2).reshape(T * N, dc + dz)
+    flat = lay.gru_to_dev({k: dev(v) for k, v in gp.items()})
+    labels = dev(draw['labels'], torch.int32) if dim_zl else None
+    z = torch.full((T * N, dc + dz), 3.0, device="cuda")
+    saved = torch.empty((T, N, 4 * dz), device="cuda")
+    hl.gru_seq_fwd(N, T, dz, dim_zl, dc, flat, dev(draw['h0']), dev(draw['e']), labels, dev(draw['zc']), z, saved)
+    assert rel_l2(z, z_ref) < FWD_TOL
+    gz = rng.randn(T * N, dc + dz)
+    grads = {k: np.zeros_like(v) for k, v in gpo.items()}
+    gh = np.zeros((N, dz))
+    for t in reversed(range(T)):
+        gh = gh + gz.reshape(T, N, -1)[t][:, dc:]
+        gh, _ = F.gru_step_bwd(gpo, caches[t], gh, grads)
+    dflat = torch.zeros_like(flat)
+    hl.gru_seq_bwd(N, T, dz, dim_zl, dc, flat, dev(draw['e']), labels, saved, dev(gz), dflat)
+    got = lay.gru_from_dev(dflat, dz, dim_zl, prefix='')
+    for k in grads:
+        assert rel_l2(got[k], grads[k]) < BWD_TOL, k
+
+
+@pytest.mark.parametrize("n", [8388608, 8388611])
+def test_adam_at_the_largest_tensor(pkg, n):
+    """adam_wd on 8.4 M elements (D_V.dc4's filter: 512 x 4 x 4 x 4 x 256) and on a count that is no multiple of any vector
+    width, three steps; the oracle and bound of tests/test_gpu_ops.py::test_adam_weight_decay"""
+    hl = pkg[0]
+    rng = np.random.RandomState(9)
+    p = {'x/W': rng.randn(n).astype(np.float32)}
+    st = oupd.new_adam_state(p)
+    pd, md, vd = dev(p['x/W']), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    for t in (1, 2, 3):
+        g = (rng.randn(n) * 10.0 ** rng.uniform(-9, 0, n)).astype(np.float32)
+        oupd.adam_wd_update(p, {'x/W': g}, st)
+        lr_t = oupd.ADAM_ALPHA * np.sqrt(1 - oupd.ADAM_BETA2 ** t) / (1 - oupd.ADAM_BETA1 ** t)
+        hl.adam_wd(pd, dev(g), md, vd, lr_t, oupd.ADAM_BETA1, oupd.ADAM_BETA2, oupd.ADAM_EPS, oupd.WEIGHT_DECAY)
+        assert np.abs(pd.cpu().numpy() - p['x/W']).max() < 1e-6, t
+
+
+def test_clip_bytes_at_256_clips(pkg):
+    """pack_clip_u8 and clip_to_u8 on 256 clips of 16 x 64 x 64 x 3 (the bf16 step's batch): exact, as at small size
+    (datasets.py:95: (x - 128) / 128; generate_samples.py:39: ((x / 2 + 0.5) * 255) truncated)"""
+    hl = pkg[0]
+    N, T, H, C, Cp = 256, 16, 64, 3, 4
+    rng = np.random.RandomState(256)
+    u8 = rng.randint(0, 256, (N, T, H, H, C), dtype=np.uint8)
+    u8.reshape(-1)[:512] = np.repeat(np.arange(256, dtype=np.uint8), 2)        # every byte value is there
+    out = torch.full((N, T, H, H, Cp), 9.0, device="cuda")
+    hl.pack_clip_u8(N, C, Cp, T, H * H, torch.tensor(u8, device="cuda"), out)
+    got = out.cpu().numpy()
+    want = (u8.astype(np.float32) - 128.) / 128.
+    assert np.array_equal(got[..., :C], want) and not got[..., C:].any()
+    # and back: the packed clip's bytes ((k - 128) / 128 / 2 + 0.5) * 255, and uniform values with the byte boundaries among them
+    x = rng.uniform(-1, 1, (N, T, H * H, Cp)).astype(np.float32)
+    k = np.arange(256, dtype=np.float64)
+    edge = (((k / 255.0) - 0.5) * 2.0).astype(np.float32)
+    edges = np.clip(np.concatenate([edge, np.nextafter(edge, np.float32(2)), np.nextafter(edge, np.float32(-2)),
+                                    np.array([1.0, -1.0, 0.0, -0.0], np.float32)]), -1.0, 1.0).astype(np.float32)
+    x.reshape(-1)[:edges.size] = edges
+    x.reshape(-1)[-edges.size:] = edges                              # (in the last block of the grid too)
+    for src in (got.reshape(N, T, H * H, Cp), x):
+        want_b = ((src[..., :C] / 2. + 0.5) * 255).astype(np.uint8)
+        ob = torch.zeros((N, T, H * H, C), device="cuda", dtype=torch.uint8)
+        hl.clip_to_u8(N, C, Cp, T, H * H, dev(src), ob)
+        assert np.array_equal(ob.cpu().numpy(), want_b)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Fused epilogues at production size, each against float64 computed from the ref64 result
+# ------------------------------------------------------------------------------------------------------------------
+def _bench_layers(B):
+    tools = os.path.join(ROOT, 'tools')
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import bench_layers
+    return bench_layers.layers(B)
+
+
+def _operands(hl, form, x, w, gy, kt, Ci):
+    """(x side, filter as fprop / wgrad read it, filter as dgrad reads it, y side) in the operand form of the precision"""
+    bf = torch.bfloat16
+    if form == "bf16s":
+        return x.to(bf), w.to(bf), w.to(bf), gy.to(bf)
+    if form == "f32x3":
+        return hl.split_planes(x), hl.split_planes(w), hl.split_planes(w, run=16 * kt * 16 * Ci), hl.split_planes(gy)
+    return x, w, w, gy
+
+
+STATS_CASES = [("D", 64), ("D", 512), ("G", 512), ("G", 4096)]
+
+
+@pytest.mark.parametrize("net,N", STATS_CASES, ids=["%s-N%d" % c for c in STATS_CASES])
+def test_production_batch_statistics_epilogue(pkg, net, N):
+    """SUMS_STATS at production size: fprop of D_V / D_I dc2..dc4 on 64 and 512 clips with one and two statistics groups, dgrad of
+    G's dc2..dc4 (conv form, with the deconvolution's bias) on 512 and 4096 frames -- the launches whose per-tile partial sums go
+    through fold_partials_kernel (more than 96 slots; asserted for every fused launch of D_V.dc2, D_I.dc2, G.dc2 and G.dc4).  Tile code: the table's for the launch form
+    (bf16 networks key it by epilogue and output type), K split dropped or the stand-alone bn_stats taken exactly as
+    hiplib.conv_fprop / nets do.  The conv output as in the plain-launch test; bn_stats_from_partials' mean / inv_std / running
+    averages against float64 statistics of the REFERENCE, 1e-5 (test_fprop_epilogue_statistics_and_first_layer's bound).
+    Forms: 64 clips / 512 frames (batch 32): f32, f32x3, bf16s; 512 clips / 4096 frames (batch 256): bf16s; bf16s with the fp32 and
+    the bf16 store.  With the bf16 store the sums are those of the values as STORED (tests/test_gpu_ops.py::test_bf16_gemm_outputs),
+    so the float64 statistics are taken of the reference after the same rounding: the rounding noise of 1e3 .. 1e6 stored values
+    does not average out of a mean to 1e-5 (measured against the unrounded reference: 1e-5 .. 2e-4)."""
+    hl = pkg[0]
+    table = _shipped_table()
+    P = _Parity(hl, "stats-%s-N%d" % (net, N), table)
+    hl.reset_tuning()
+    hl.use_pretuned_table()
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(7000 + N)
+    small = (net, N) in (("D", 64), ("G", 512))
+    kind = "fprop" if net == "D" else "dgrad"
+    layers = [l for l in _bench_layers(N if net == "D" else N // 16) if l[0].startswith(net) and l[0][-1] in "234" and l[4] > 4]
+    assert len(layers) == (6 if net == "D" else 3)
+    slots, bad = {}, []
+    try:
+        for name, n_, T, H, Ci, Co, kt, _ in layers:
+            assert n_ == N
+            g0 = hl.make_geom(N, T, H, H, Ci, Co, kt)
+            Cn = Co if kind == "fprop" else Ci                      # channels of the launch's output
+            for form in (["f32", "f32x3", "bf16s"] if small else ["bf16s"]):
+                exact = form == "bf16s"
+                if form == "f32x3" and not hl.split_covers(kind, g0):
+                    continue
+                x = _seeded(gen, (N, T, H, H, Ci), bf16_values=exact)
+                gy = _seeded(gen, (N, g0.To, g0.Ho, g0.Wo, Co), bf16_values=exact)
+                w = _seeded(gen, (Co, kt, 4, 4, Ci), scale=(kt * 16 * Ci) ** -0.5 if kind == "fprop" else (kt * 4 * Co) ** -0.5, bf16_values=exact)
+                bias = _seeded(gen, (Cn,), scale=0.3)
+                ref = ref64.fprop(x, w, bias) if kind == "fprop" else ref64.dgrad(gy, w, T, H, H) + bias.double()
+                xs, wf, wd, ys = _operands(hl, form, x, w, gy, kt, Ci)
+                g = hl.with_precision(g0, form)
+                M = ref.numel() // Cn
+                gamma, beta = 1 + 0.1 * _seeded(gen, (Cn,)), 0.1 * _seeded(gen, (Cn,))
+                ws = torch.empty(hl.bn_workspace_floats(max(Cn, 64)), device='cuda')
+                for groups in ((1, 2) if net == "D" else (1,)):
+                    mg = M // groups
+                    for out16 in ((False, True) if form == "bf16s" else (False,)):
+                        epk = ('ep', hl.SUMS_STATS, 0, int(out16)) if form == "bf16s" else ()
+                        code = P.code(kind, g, ((hl.ACT_NONE, 0) if kind == "dgrad" else ()) + epk)
+                        if code >= 1000 and out16:
+                            continue                                # (a split-K tile stores fp32: the networks ask fprop_tile / dgrad_tile first)
+                        part = torch.full((hl.epilogue_part_floats(g, kind, groups),), float('nan'), device='cuda')
+                        ep = hl.epilogue(sums=hl.SUMS_STATS, groups=groups, part=part, out_bf16=out16)
+                        out = torch.full(ref.shape, 3.0, device='cuda', dtype=torch.bfloat16 if out16 else torch.float32)
+                        if kind == "fprop":
+                            fused = hl.conv_fprop(P.geom(g, code), xs, wf, bias, out, ep=ep)
+                        else:
+                            fused = hl.conv_dgrad(P.geom(g, code), ys, wd, bias, out, ep=ep)
+                        tol = (FWD_TOL if kind == "fprop" else BWD_TOL) + (BF16_STORE_EPS if out16 else 0)
+                        P.judge(name, kind, form, code, out, ref, tol, note=" (statistics epilogue, %d group%s%s%s)" % (
+                            groups, "s"[:groups - 1], ", bf16 store" if out16 else "", "" if fused else "; K split: stand-alone bn_stats"))
+                        if fused:
+                            slots.setdefault(name, []).append(ep.n_slots)
+                            assert ep.slot_stride == groups * 2 * Cn
+                        for gi in range(groups):
+                            r = ref.reshape(M, Cn)[gi * mg:(gi + 1) * mg]
+                            if out16:
+                                r = r.to(torch.bfloat16).double()   # the sums are those of the values as STORED: the same rounding of the reference
+                            mean, var = r.mean(0), r.var(0, unbiased=False) + 2e-5
+                            stats = torch.full((4 * Cn,), float('nan'), device='cuda')
+                            am, av = torch.zeros(Cn, device='cuda'), torch.ones(Cn, device='cuda')
+                            if fused:
+                                hl.bn_stats_from_partials(mg, Cn, part[gi * 2 * Cn:], ep.n_slots, ep.slot_stride, gamma, beta, stats, am, av, ws)
+                            else:
+                                hl.bn_stats(mg, Cn, out.reshape(M, Cn)[gi * mg:(gi + 1) * mg], gamma, beta, stats, am, av, ws)
+                            figs = (_t_rel(stats[:Cn], mean), _t_rel(stats[Cn:2 * Cn], var.rsqrt()), _t_rel(am, 0.1 * mean),
+                                    _t_rel(av, 0.9 + 0.1 * (mg / (mg - 1.0)) * var))
+                            line = "%s %s %s code %d groups %d/%d bf16-store %d slots %d: mean %.1e inv_std %.1e avg_mean %.1e avg_var %.1e" % (
+                                (name, kind, form, code, gi, groups, out16, ep.n_slots if fused else 0) + figs)
+                            print(line)
+                            if not all(f < 1e-5 for f in figs):
+                                bad.append(line)
+                        del out, part
+                del x, gy, w, ref, xs, wf, wd, ys
+                torch.cuda.empty_cache()
+        print({k: sorted(set(v)) for k, v in slots.items()})
+        assert not P.failed, "\n".join(P.failed)
+        assert not bad, "\n".join(bad)
+        for fold in (["D_V.dc2", "D_I.dc2"] if net == "D" else ["G.dc2", "G.dc4"]):
+            assert slots.get(fold) and min(slots[fold]) > 96, "the fold path (more than 96 slots) did not run for %s: %r" % (fold, slots.get(fold))
+    finally:
+        hl.reset_tuning()
+        torch.cuda.empty_cache()
+
+
+def _mask_bits_dev(mask, C):
+    cols = torch.arange(C, device=mask.device)
+    return ((mask[:, cols >> 5] >> (cols & 31)) & 1).bool()
+
+
+FIRST_CASES = [("D_V.dc1", 64, "f32"), ("D_I.dc1", 64, "f32"), ("D_V.dc1", 64, "bf16"), ("D_I.dc1", 64, "bf16"),
+               ("D_V.dc1", 512, "bf16"), ("D_I.dc1", 512, "bf16")]
+
+
+@pytest.mark.parametrize("layer,N,family", FIRST_CASES, ids=["%s-N%d-%s" % c for c in FIRST_CASES])
+def test_production_batch_first_layer_epilogue(pkg, layer, N, family):
+    """D's first layer as the networks launch it (nets.DisNet.forward_groups): leaky_relu + injected noise + sign bits in the
+    epilogue, one and two groups; f32 networks with the fp32 store and with the split store of 'f32x3' (MCG_IO_OUT_SPLIT: the sum
+    of the three terms is compared), bf16 networks ('bf16' launch on the fp32 clip) with the bf16 store (2^-9 on top).  Against
+    leaky_relu(ref64.fprop) + noise at FWD_TOL, worst block 4 x; sign bits equal wherever |pre-activation| > 1e-5.
+    Then the in-kernel Philox form against the injected form fed by hl.randn_rowquad of the same (seed, stream ids): this last
+    step is a SELF-CONSISTENCY check -- the stream itself is pinned to the NumPy oracle at small size
+    (test_fprop_epilogue_statistics_and_first_layer: in-kernel < 2e-5, randn_rowquad < 4e-6 of the oracle; here their sum)."""
+    hl = pkg[0]
+    table = _shipped_table()
+    P = _Parity(hl, "first-%s-N%d" % (family, N), table)
+    hl.reset_tuning()
+    hl.use_pretuned_table()
+    name, _, T, H, Ci, Co, kt, ci_real = [l for l in _bench_layers(N) if l[0] == layer][0]
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(6000 + N + kt)
+    exact = family == "bf16"
+    try:
+        x = _seeded(gen, (N, T, H, H, Ci), bf16_values=exact, zero_last=True)
+        w = _seeded(gen, (Co, kt, 4, 4, Ci), scale=(kt * 16 * 3) ** -0.5, bf16_values=exact, zero_last=True)
+        b = _seeded(gen, (Co,), scale=0.3)
+        g = hl.make_geom(N, T, H, H, Ci, Co, kt, precision=family, ci_valid=ci_real)
+        pre = ref64.fprop(x, w, b)
+        M = pre.numel() // Co
+        sure = (pre.abs() > KINK).reshape(M, Co)
+        act_ref = torch.where(pre >= 0, pre, 0.2 * pre)
+        code = P.code("fprop", g)
+        stores = ["fp32", "split"] if family == "f32" else ["bf16"]
+        for groups in (1, 2):
+            ng, mg = N // groups, M // groups
+            streams = [5, 9][:groups]
+            z = torch.empty((M, Co), device='cuda')
+            for gi in range(groups):
+                hl.randn_rowquad(z[gi * mg:(gi + 1) * mg], Co, 0.2, 77, streams[gi])
+            zt = z.view(pre.shape)
+            want = act_ref + zt.double()
+            for store in stores:
+                outs = []
+                for kw in (dict(addend=[zt[i * ng:(i + 1) * ng] for i in range(groups)]), dict(sigma=0.2, seed=77, stream_id=streams)):
+                    mask = torch.zeros((M, (Co + 31) // 32), dtype=torch.int32, device='cuda')
+                    shape = tuple(pre.shape[:-1]) + ((4 * Co,) if store == "split" else (Co,))
+                    out = torch.full(shape, 3.0, device='cuda', dtype=torch.float32 if store == "fp32" else torch.bfloat16)
+                    ep = hl.epilogue(act=hl.ACT_LRELU, groups=groups, mask_out=mask, out_bf16=store == "bf16", out_split=store == "split", **kw)
+                    assert hl.conv_fprop(P.geom(g, code), x, w, b, out, ep=ep, must_fuse=True)
+                    val = out.view(M, Co // 16, 4, 16)[:, :, :3].double().sum(2).view(pre.shape) if store == "split" else out
+                    outs.append(val)
+                    if 'addend' in kw:
+                        P.judge(name, "fprop", family, code, val, want, FWD_TOL + (BF16_STORE_EPS if store == "bf16" else 0),
+                                note=" (lrelu + noise + sign bits, %d group%s, %s store)" % (groups, "s"[:groups - 1], store))
+                        bits = _mask_bits_dev(mask, Co)
+                        wrong = int(((bits != (pre.reshape(M, Co) >= 0)) & sure).sum())
+                        assert wrong == 0, "%d sign bits differ away from the kink (%s, %d groups, %s store)" % (wrong, name, groups, store)
+                    else:
+                        assert torch.equal(mask, mask_injected), "the sign bits depend on where the noise comes from"
+                    mask_injected = mask
+                # self-consistency: in-kernel Philox == injected randn_rowquad of the same streams
+                d = float((outs[1].double() - outs[0].double()).abs().max())
+                lim = 2.4e-5 if store != "bf16" else 2.4e-5 + 2.0 ** -7 * float(want.abs().max())    # (a bf16 store: one step of 2^-7 apart at most)
+                print("%s N=%d %s groups %d %s store: max |in-kernel Philox - injected randn_rowquad| %.2e" % (name, N, family, groups, store, d))
+                assert d < lim, (d, lim)
+                del outs
+        assert not P.failed, "\n".join(P.failed)
+    finally:
+        hl.reset_tuning()
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("form", ["f32", "bf16s"])
+@pytest.mark.parametrize("layer", ["D_V.dc2", "D_V.dc3", "D_V.dc4"])
+def test_production_batch_dgrad_backward_epilogues(pkg, layer, form):
+    """The two backward epilogues of dgrad (tests/test_gpu_ops.py::test_dgrad_epilogue_sums_and_mask (b) and (c)) on D_V.dc2..dc4
+    at 64 clips, references in float64 torch from ref64.dgrad:
+    (b) SUMS_BN_BWD, one and two groups: the produced gradient as in the plain-launch test; bn_act_bwd_from_partials' gx, dgamma,
+        dbeta against the float64 BatchNorm + leaky_relu backward of the REFERENCE gradient (BWD_TOL, the bounds of
+        test_batchnorm_activation_fwd_bwd).
+        A table code that splits K is not fused (hiplib.conv_dgrad) and a kernel that cannot carry the sums refuses: the plain
+        launch and the stand-alone bn_act_bwd then, as the network does.  bf16s: the LDS-DMA tiles 7 / 8 / 10 as well.
+        The BatchNorm inputs keep every output 1e-5 away from the kink (_off_the_kink).
+    (c) leaky_relu's backward from stored sign bits + column sums (must_fuse, K split dropped): gx BWD_TOL, the bias gradient
+        through colsum_from_partials 1e-4 of max(1, max |sum|) as at small size."""
+    hl = pkg[0]
+    N = 64
+    table = _shipped_table()
+    P = _Parity(hl, "bwd-ep-%s-N%d" % (form, N), table)
+    hl.reset_tuning()
+    hl.use_pretuned_table()
+    name, _, T, H, Ci, Co, kt, _ = [l for l in _bench_layers(N) if l[0] == layer][0]
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(5000 + Ci)
+    exact = form == "bf16s"
+    try:
+        g = hl.make_geom(N, T, H, H, Ci, Co, kt, precision=form)
+        gy = _seeded(gen, (N, g.To, g.Ho, g.Wo, Co), bf16_values=exact)
+        w = _seeded(gen, (Co, kt, 4, 4, Ci), scale=(kt * 4 * Co) ** -0.5, bf16_values=exact)
+        gx_ref = ref64.dgrad(gy, w, T, H, H)
+        wd, ys = (w.to(torch.bfloat16), gy.to(torch.bfloat16)) if exact else (w, gy)
+        M = gx_ref.numel() // Ci
+        ybn = _seeded(gen, (M, Ci)) * 1.3 + 0.2
+        if exact:
+            ybn = ybn.to(torch.bfloat16).float()
+        gam, bet = 1 + 0.1 * _seeded(gen, (Ci,)), 0.1 * _seeded(gen, (Ci,))
+        ws = torch.empty(hl.bn_workspace_floats(max(Ci, 64)), device='cuda')
+        epk = (lambda sums, mask: ('ep', sums, mask, 0)) if exact else (lambda sums, mask: ())
+        fused_codes = set()
+        table_code = P.code("dgrad", g, (hl.ACT_NONE, 0) + epk(hl.SUMS_BN_BWD, 0))
+        # bf16 tensors: only the LDS-DMA tiles carry these sums (tests/test_gpu_ops.py::test_lds_dma_kernels_carry_batchnorm_backward_sums);
+        # the shipped table holds no entry for the form (bench.py's tuner times it on first use), so they are named here
+        for groups, code in [(gr, c) for gr in (1, 2) for c in ([table_code] + ([7, 8, 10] if exact else []))]:
+            mg = M // groups
+            st, refs = [], []
+            for gi in range(groups):
+                sl = slice(gi * mg, (gi + 1) * mg)
+                ybn[sl], x_hat, inv_std, bn = _off_the_kink(ybn[sl], gam, bet, exact)
+                refs.append((x_hat, inv_std, bn))
+                s_ = torch.empty(4 * Ci, device='cuda')
+                hl.bn_stats(mg, Ci, ybn[sl], gam, bet, s_, None, None, ws)
+                st.append(s_)
+            ybn_in = ybn.to(torch.bfloat16) if exact else ybn          # (a bf16 network keeps the pre-BatchNorm values in bf16)
+            part = torch.full((hl.epilogue_part_floats(g, "dgrad", groups),), float('nan'), device='cuda')
+            ep = hl.epilogue(sums=hl.SUMS_BN_BWD, groups=groups, part=part, bn_y=ybn_in.view(gx_ref.shape), bn_stats=st, bn_act=hl.ACT_LRELU)
+            gx = torch.full(gx_ref.shape, 7.0, device='cuda')
+            try:
+                fused = hl.conv_dgrad(P.geom(g, code), ys, wd, None, gx, ep=ep)
+            except hl.McgError as e:
+                # a kernel that cannot carry the sums refuses before anything is queued; the network then launches the plain
+                # convolution and the stand-alone pass (nets._Net._with_bwd_sums) -- and so does this test, for the table's code
+                print("%s %s code %d: the sums epilogue is refused (%s)" % (name, form, code, e))
+                # the LDS-DMA tiles carry the sums around bf16 tensors (test_lds_dma_kernels_carry_batchnorm_backward_sums): no refusal there
+                assert code == table_code, "tile %d refused the BatchNorm-backward sums on %s: %s" % (code, name, e)
+                fused = False
+                hl.conv_dgrad(P.geom(g, code), ys, wd, None, gx)
+            if fused:
+                fused_codes.add(code)
+            P.judge(name, "dgrad", form, code, gx, gx_ref, BWD_TOL, note=" (BatchNorm-backward sums, %d group%s%s)" % (
+                groups, "s"[:groups - 1], "" if fused else "; not fused: stand-alone pass"))
+            for gi in range(groups):
+                sl = slice(gi * mg, (gi + 1) * mg)
+                g64 = gx_ref.reshape(M, Ci)[sl]
+                x_hat, inv_std, bn = refs[gi]
+                g_bn = torch.where(bn >= 0, g64, 0.2 * g64)
+                gb_ref, gg_ref = g_bn.sum(0), (g_bn * x_hat).sum(0)
+                want = (gam.double() * inv_std) * (g_bn - (x_hat * gg_ref + gb_ref) / mg)
+                got, dg, db = torch.full((mg, Ci), 7.0, device='cuda'), torch.ones(Ci, device='cuda'), torch.ones(Ci, device='cuda')
+                if fused:
+                    hl.bn_act_bwd_from_partials(mg, Ci, gx.view(M, Ci)[sl], ybn_in[sl], st[gi], gam, hl.ACT_LRELU, part[gi * 2 * Ci:], ep.n_slots, ep.slot_stride,
+                                                got, dg, db, ws)
+                else:
+                    hl.bn_act_bwd(mg, Ci, gx.view(M, Ci)[sl], ybn_in[sl], st[gi], gam, hl.ACT_LRELU, got, dg, db, ws)
+                rep = ref64.compare(got, want)
+                e_g, e_b = _t_rel(dg, gg_ref + 1), _t_rel(db, gb_ref + 1)
+                print("%s %s code %d groups %d/%d slots %d: BatchNorm backward from the partial sums: %s; dgamma %.1e dbeta %.1e" % (
+                    name, form, code, gi, groups, ep.n_slots if fused else 0, rep, e_g, e_b))
+                assert rep.ok(BWD_TOL), str(rep)
+                assert e_g < BWD_TOL and e_b < BWD_TOL, (e_g, e_b)
+                del g_bn, want, got
+            del gx, part, refs
+        assert fused_codes >= ({7, 8, 10} if exact else {table_code}), "launches that carried the BatchNorm-backward sums: %r" % sorted(fused_codes)
+        # (c) sign bits in, column sums out
+        sign = torch.rand((M, Ci), device='cuda', generator=gen) > 0.4
+        words = (sign.view(M, Ci // 32, 32).long() << torch.arange(32, device='cuda')).sum(-1)
+        maskd = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+        code = P.code("dgrad", g, (hl.ACT_NONE, 0) + epk(hl.SUMS_COL, 1))
+        part = torch.full((hl.epilogue_part_floats(g, "dgrad", 1),), float('nan'), device='cuda')
+        ep = hl.epilogue(mask_in=maskd, sums=hl.SUMS_COL, groups=1, part=part)
+        gx = torch.full(gx_ref.shape, 7.0, device='cuda')
+        assert hl.conv_dgrad(P.geom(g, code), ys, wd, None, gx, ep=ep, must_fuse=True)
+        want = gx_ref * torch.where(sign, 1.0, 0.2).double().view(gx_ref.shape)
+        P.judge(name, "dgrad", form, code % 1000, gx, want, BWD_TOL, note=" (sign bits in, column sums out)")
+        db = torch.ones(Ci, device='cuda')
+        hl.colsum_from_partials(Ci, part, ep.n_slots, ep.slot_stride, db, ws)
+        col = want.reshape(M, Ci).sum(0)
+        e_c = float((db.double() - (1 + col)).abs().max())
+        print("%s %s slots %d: bias gradient from the partial sums: max abs error %.2e, max |sum| %.1f" % (name, form, ep.n_slots, e_c, float(col.abs().max())))
+        assert e_c < 1e-4 * max(1.0, float(col.abs().max())), e_c
+        assert not P.failed, "\n".join(P.failed)
+    finally:
+        hl.reset_tuning()
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("layer", ["G.dc2", "G.dc3", "G.dc4"])
+def test_production_batch_relu_store(pkg, layer):
+    """The sampling path's deconvolution with ReLU in the store (hiplib.conv_dgrad_relu: the table's code for the geometry, K
+    split dropped) at 4096 frames -- sample_many's chunks are smaller -- on bf16-stored operands with the bf16 store a bf16
+    generator takes (2^-9 on top of BWD_TOL) and with the fp32 store (BWD_TOL), against max(ref64.dgrad + bias, 0)."""
+    hl = pkg[0]
+    N = 4096
+    hl.reset_tuning()
+    hl.use_pretuned_table()
+    name, _, T, H, Ci, Co, kt, _ = [l for l in _bench_layers(N // 16) if l[0] == layer][0]
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(4000 + Ci)
+    try:
+        g = hl.make_geom(N, 1, H, H, Ci, Co, 1, precision='bf16s')
+        gy = (_seeded(gen, (N, 1, H // 2, H // 2, Co)).clamp_min(0) * 0.7).to(torch.bfloat16)      # (a ReLU output, as in the network)
+        w = _seeded(gen, (Co, 1, 4, 4, Ci), scale=(4 * Co) ** -0.5).to(torch.bfloat16)
+        bias = _seeded(gen, (Ci,), scale=0.3)
+        ref = (ref64.dgrad(gy, w, 1, H, H) + bias.double()).clamp_min(0)
+        for dt in (torch.bfloat16, torch.float32):
+            out = torch.full(ref.shape, -3.0, device='cuda', dtype=dt)
+            hl.conv_dgrad_relu(g, gy, w, bias, out)
+            rep = ref64.compare(out, ref)
+            code = hl.table_tile("dgrad", g, (hl.ACT_NONE, 0) + hl._ep_key(g, None, out)) % 1000
+            print("%s N=%d relu store %s code %d: %s" % (name, N, dt, code, rep))
+            _parity_table_row(("relu-store-N%d" % N, name, "dgrad + relu (%s store)" % ("bf16" if dt == torch.bfloat16 else "fp32"), "bf16s", code, "%.2e" % rep.rel, "%.2e" % rep.block))
+            assert rep.ok(BWD_TOL + (BF16_STORE_EPS if dt == torch.bfloat16 else 0)), str(rep)
+            assert float(out.float().min()) >= 0.0 and float((out == 0).float().mean()) > 0.05      # ReLU really clipped something
+            del out
+    finally:
+        hl.reset_tuning()
+        torch.cuda.empty_cache()

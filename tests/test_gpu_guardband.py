@@ -66,7 +66,7 @@ def _bf16_round(a):
 
 
 GUARD_CASES = [
-    # N, Ti, H, Ci, Co, kt
+    # N, Ti, H (or (H, W)), Ci, Co, kt
     (2, 4, 8, 64, 160, 4),      # round 3's red case: Mpix = 32 < BK, Co not a multiple of the tile
     (2, 7, 16, 8, 64, 4),       # narrow 3-D layer
     (2, 5, 16, 3, 64, 4),       # the clip: 3 channels padded to 4
@@ -78,19 +78,27 @@ GUARD_CASES = [
     (2, 7, 32, 64, 128, 4),     # D_V dc2's geometry: the patch-stationary input gradient
     (5, 1, 8, 128, 512, 1),     # four N tiles
     (3, 5, 16, 128, 128, 4),    # 128 channels on both sides, ragged 256-row tiles, 3-D
+    (2, 5, (64, 32), 3, 64, 4), # H != W (given as a pair): the clip with Wo = 16 and four row bands per frame of the first-layer kernels
+    (2, 4, (8, 32), 64, 128, 4),    # H < W on a wide layer
 ]
 TILES = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 101, 203, 1103, 2203, 1007, 2010]
 _refs = {}
+
+
+def _frame(H):
+    """(H, W) of a case: square unless the case gives a pair"""
+    return H if isinstance(H, tuple) else (H, H)
 
 
 def _case_data(case):
     """seeded bf16-representable inputs (every precision then computes the same exact products) and the oracle's results"""
     if case not in _refs:
         N, Ti, H, Ci, Co, kt = case
+        H, Wd = _frame(H)
         rng = np.random.RandomState(4000 + GUARD_CASES.index(case))
-        x = _bf16_round(rng.uniform(-1, 1, (N, Ci, Ti, H, H)))
+        x = _bf16_round(rng.uniform(-1, 1, (N, Ci, Ti, H, Wd)))
         W = _bf16_round(rng.randn(Co, Ci, kt, 4, 4) * 0.1)
-        gy = _bf16_round(rng.randn(N, Co, Ti - kt + 1, H // 2, H // 2))
+        gy = _bf16_round(rng.randn(N, Co, Ti - kt + 1, H // 2, Wd // 2))
         y_ref = F.conv3d_fwd(x, W, None, (1, 2, 2), (0, 1, 1))
         gx_ref, gW_ref, _ = F.conv3d_bwd(x, W, gy, (1, 2, 2), (0, 1, 1))
         _refs[case] = (x, W, gy, y_ref, gx_ref, gW_ref)
@@ -113,6 +121,7 @@ def _operands(hl, prec, xd, wd, gyd, kt, Ci):
 @pytest.mark.parametrize("prec", ['f32', 'bf16', 'bf16s', 'f32x3', 'bf16y'])
 def test_conv_launches_stay_inside_their_tensors(hl, arena, case, prec):
     N, Ti, H, Ci, Co, kt = case
+    H, Wd = _frame(H)
     lay = L()
     x, W, gy, y_ref, gx_ref, gW_ref = _case_data(case)
     xd0, wd0, gyd0 = lay.act_to_dev(dev(x)), lay.conv_w_to_dev(dev(W)), lay.act_to_dev(dev(gy))
@@ -129,7 +138,7 @@ def test_conv_launches_stay_inside_their_tensors(hl, arena, case, prec):
         arena.reset()
         xa, wa, wda, ga = (arena.put(t) for t in ops0)
         snap = [t.clone() for t in (xa, wa, wda, ga)]
-        g = hl.make_geom(N, Ti, H, H, Cip, Co, kt, precision=prec, ci_valid=Ci if Cip != Ci else 0)
+        g = hl.make_geom(N, Ti, H, Wd, Cip, Co, kt, precision=prec, ci_valid=Ci if Cip != Ci else 0)
         g.tile = tile
         kept = []                                          # (name, tensor in the arena, copy taken right after its launch)
 
@@ -159,12 +168,12 @@ def test_conv_launches_stay_inside_their_tensors(hl, arena, case, prec):
             pass
         # ---- input gradient ----
         try:
-            gxd = arena.empty((N, Ti, H, H, Cip))
+            gxd = arena.empty((N, Ti, H, Wd, Cip))
             hl.conv_dgrad(g, ga, wda, None, gxd)
             after('dgrad', gxd, (lambda t: lay.act_from_dev(t, Ci), gx_ref), BWD_TOL)
             if Cip != Ci:
                 assert float(gxd[..., Ci:].abs().max()) == 0.0
-            gx2 = arena.empty((N, Ti, H, H, Cip))
+            gx2 = arena.empty((N, Ti, H, Wd, Cip))
             hl.conv_dgrad(g, ga, wda, None, gx2)
             arena.check()
             if tile < 1000:

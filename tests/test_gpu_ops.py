@@ -94,6 +94,96 @@ def test_conv_three_passes(hl, case, tile):
         hl.set_tile_override(0)
 
 
+RECT_FRAMES = [(16, 64), (64, 16), (8, 32), (128, 32), (64, 32)]       # (Hi, Wi)
+RECT_LAYERS = {                                                          # N, Ti, Ci, Co, kt
+    "first-3d": (2, 5, 3, 64, 4),      # Ci = 3 -> 4, Co = 64: the first-layer kernels (tile 0 and 6) where Wo is 16 or 32
+    "first-2d": (3, 1, 3, 64, 1),
+    "wide": (2, 5, 64, 128, 4),
+}
+SPECIALISED_TILES = (6, 7, 8, 10)      # kernels with limits of their own: a refusal (MCG_ERR_UNSUPPORTED) is an answer, a wrong number is not
+
+
+def _form_exists(layer, prec):
+    """bf16s: a 16-byte slot of a bf16 tensor is 8 channels; f32x3: the split form needs groups of 16 channels"""
+    _, _, Ci, Co, _ = RECT_LAYERS[layer]
+    Cip = (Ci + 3) // 4 * 4
+    return not (prec == "f32x3" and (Cip % 16 or Co % 16)) and not (prec == "bf16s" and (Cip % 8 or Co % 8))
+
+
+RECT_CASES = [(f, l, p) for f in RECT_FRAMES for l in sorted(RECT_LAYERS) for p in ("f32", "bf16", "bf16s", "f32x3") if _form_exists(l, p)]
+
+
+@pytest.mark.parametrize("frame,layer,prec", RECT_CASES, ids=["%dx%d-%s-%s" % (f + (l, p)) for f, l, p in RECT_CASES])
+def test_conv_three_passes_on_rectangular_frames(hl, frame, layer, prec):
+    """mcg_conv_geom takes Hi and Wi separately; every other geometry in the tests is square, so a swapped lgHo / lgWo or a
+    row-band halo of the WO = 16 first-layer instantiations (more than one band per frame only when Ho > 8) would go unseen.
+    Hi != Wi both ways, Wo = 8 / 16 / 32, Ho from 4 to 64; the tile list of test_conv_three_passes plus the specialised kernels'
+    codes; three passes against tests/ref64.py in float64 at the tolerances of test_conv_three_passes (bf16 / bf16s on
+    bf16-representable inputs, as test_conv_three_passes_bf16_mfma (1)); the precisions are those whose form exists for the layer
+    (RECT_CASES).  The generic tiles and tile 0 must run everywhere, tile 6 wherever the first-layer kernels' predicate admits the
+    frame; only the specialised kernels may answer a geometry outside their limits with a refusal."""
+    import ref64
+    Hi, Wi = frame
+    N, Ti, Ci, Co, kt = RECT_LAYERS[layer]
+    Cip = (Ci + 3) // 4 * 4
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(Hi * 1000 + Wi + Ci + kt)
+    exact = prec in ("bf16", "bf16s")
+    rnd = lambda shape, s=1.0: (lambda t: t.to(torch.bfloat16).float() if exact else t)(torch.randn(shape, device="cuda", generator=gen) * s)
+    x, w, b = rnd((N, Ti, Hi, Wi, Cip)), rnd((Co, kt, 4, 4, Cip), 0.1), torch.randn(Co, device="cuda", generator=gen)
+    if Cip != Ci:
+        x[..., Ci:] = 0
+        w[..., Ci:] = 0
+    g0 = hl.make_geom(N, Ti, Hi, Wi, Cip, Co, kt, precision=prec, ci_valid=Ci if Cip != Ci else 0)
+    gy = rnd((N, g0.To, g0.Ho, g0.Wo, Co))
+    y_ref, gx_ref, dw_ref = ref64.fprop(x, w, b), ref64.dgrad(gy, w, Ti, Hi, Wi), ref64.wgrad(x, gy, kt)
+    if prec == "bf16s":
+        xs, wf, wd, ys = x.to(torch.bfloat16), w.to(torch.bfloat16), w.to(torch.bfloat16), gy.to(torch.bfloat16)
+    elif prec == "f32x3":
+        xs, wf, wd, ys = hl.split_planes(x), hl.split_planes(w), hl.split_planes(w, run=16 * kt * 16 * Cip), hl.split_planes(gy)
+    else:
+        xs, wf, wd, ys = x, w, w, gy
+    tiles = [0, 7, 8, 10] if prec == "f32x3" else [0, 1, 2, 3, 4, 5, 101, 103, 201, 202, 203] + ([6] if Cip == 4 else [7, 8, 10])
+    bad, ran, refused = [], [], []
+    for tile in tiles:
+        g = hl.with_precision(g0, prec)
+        g.tile = tile
+        for kind in ("fprop", "dgrad", "wgrad"):
+            try:
+                if kind == "fprop":
+                    out = torch.full(y_ref.shape, 3.0, device="cuda")
+                    hl.conv_fprop(g, xs, wf, b, out)
+                    rep, tol = ref64.compare(out, y_ref), FWD_TOL
+                elif kind == "dgrad":
+                    out = torch.full(gx_ref.shape, 7.0, device="cuda")
+                    hl.conv_dgrad(g, ys, wd, None, out)
+                    rep, tol = ref64.compare(out, gx_ref), BWD_TOL
+                    if Cip != Ci and float(out[..., Ci:].abs().max()) != 0.0:
+                        bad.append("dgrad tile %d: the padded channel is not zero" % tile)
+                else:
+                    out = torch.zeros_like(w)
+                    hl.conv_wgrad(g, xs, ys, out)
+                    hl.conv_wgrad(g, xs, ys, out)                    # accumulates
+                    rep, tol = ref64.compare(out, 2 * dw_ref, cols=kt * 16 * Cip), BWD_TOL
+            except hl.McgError as e:
+                if tile not in SPECIALISED_TILES:
+                    bad.append("%s tile %d refused: %s" % (kind, tile, e))
+                refused.append((kind, tile))
+                continue
+            ran.append((kind, tile))
+            if not rep.rel < tol:
+                bad.append("%s tile %d: %s" % (kind, tile, rep))
+    print("%dx%d %s %s: ran %d launches, refused %s" % (Hi, Wi, layer, prec, len(ran), refused))
+    assert not bad, "\n".join(bad)
+    assert all((k, 0) in ran for k in ("fprop", "dgrad", "wgrad"))
+    if Cip == 4 and g0.Wo in (16, 32) and g0.Ho % (128 // g0.Wo) == 0:
+        # the frames the first-layer kernels' dispatch predicate admits (Wo 16 or 32, Ho a multiple of the 128 / Wo row band;
+        # several bands per frame at 128x32 and 64x32): tile 6 must really run them -- forward and input gradient in both forms,
+        # the weight gradient on fp32 operands (its bf16 form is 'bf16y': tests/test_gpu_guardband.py's 64x32 row)
+        must = [("fprop", 6), ("dgrad", 6)] + ([("wgrad", 6)] if prec == "f32" else [])
+        assert all(m in ran for m in must), "the first-layer kernels (tile 6) did not run: %r refused" % refused
+
+
 def _bf16_round(a):
     """round-to-nearest-even to bf16, returned as float64 (what v_cvt_pk_bf16_f32 does to an fp32 operand)"""
     return torch.tensor(np.asarray(a, np.float32)).to(torch.bfloat16).double().numpy()

@@ -41,6 +41,8 @@ def grads_close(grads, ref, tol=1e-8):
     ((1, 2, 2), (0, 1, 1), (2, 3, 7, 12, 12), (4, 4, 4)),
     ((1, 3, 3), (0, 0, 0), (2, 5, 4, 4, 4), (4, 4, 4)),
     ((1, 2, 2), (0, 1, 1), (3, 4, 1, 8, 8), (1, 4, 4)),
+    ((1, 2, 2), (0, 1, 1), (2, 3, 5, 16, 8), (4, 4, 4)),            # rectangular frames, H > W and H < W
+    ((1, 2, 2), (0, 1, 1), (3, 4, 1, 4, 32), (1, 4, 4)),
 ])
 def test_conv3d(stride, pad, shape, k):
     rng = np.random.RandomState(0)
