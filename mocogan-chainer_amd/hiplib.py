@@ -7,6 +7,7 @@ missing or a status is non-zero this module raises.
 import ctypes as C
 import json
 import os
+import warnings
 
 import torch
 
@@ -239,20 +240,50 @@ split_launches = 0          # conv launches in the MCG_PREC_SPLIT form so far (t
 split_only_outputs = 0      # element-wise launches that wrote their output in the split layout only
 
 
-def _launch(kind, fn, *args):
-    if args[0].precision == PREC_SPLIT:
-        global split_launches
-        split_launches += 1
+def _timed(call, *keys):
+    """call(), bracketed by two events on the current stream that are filed under every key while timing_begin() is on"""
     if _timing is None:
-        return fn(*args)
+        return call()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    r = fn(*args)
+    r = call()
     e1.record()
-    _timing.setdefault(_tag + "." + kind, []).append((e0, e1))
-    g = args[0]                                             # per-geometry detail: "<tag>.<pass> N T H Ci Co"
-    _timing.setdefault("%s.%s N=%d T=%d H=%d Ci=%d Co=%d" % (_tag, kind, g.N, g.Ti, g.Hi, g.Ci, g.Co), []).append((e0, e1))
+    for k in keys:
+        _timing.setdefault(k, []).append((e0, e1))
     return r
+
+
+def _best_ms(call):
+    """How the tuners time a candidate: one warm-up call (its McgError reaches the caller: an impossible candidate), then the best
+    of three timings of two calls each, in ms.  Tuning launches are not part of any measurement: timing is suspended meanwhile."""
+    global _timing
+    saved, _timing = _timing, None
+    try:
+        call()
+        best = None
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            call()
+            e1.record()
+            e1.synchronize()
+            ms = e0.elapsed_time(e1)
+            best = ms if best is None or ms < best else best
+        return best
+    finally:
+        _timing = saved
+
+
+def _launch(kind, fn, *args):
+    g = args[0]
+    if g.precision == PREC_SPLIT:
+        global split_launches
+        split_launches += 1
+    if _timing is None:                                         # (the per-geometry key is only built when it is used)
+        return fn(*args)
+    return _timed(lambda: fn(*args), _tag + "." + kind,        # per-geometry detail: "<tag>.<pass> N T H Ci Co"
+                  "%s.%s N=%d T=%d H=%d Ci=%d Co=%d" % (_tag, kind, g.N, g.Ti, g.Hi, g.Ci, g.Co))
 
 
 # ------------------------------------------------------------------------------------------
@@ -281,21 +312,32 @@ def set_autotune(on, use_pretuned=True):
     geometries at batch 32 per GPU (tuned_tiles_mi355x.json); anything else is still tuned on first use."""
     global _autotune
     _autotune = bool(on)
-    if use_pretuned and os.path.exists(_PRETUNED) and os.environ.get('MCG_NO_PRETUNED') != '1':
-        for k, v in json.load(open(_PRETUNED)):
-            # tuner off (train.py --autotune 0): the tile heuristic replaces the table's tile codes, but WHICH FORM a launch of an
-            # 'f32x3' network takes (split on the bf16 pipe / fp32 MFMA) has no heuristic -- those entries are loaded either way,
-            # otherwise such a network would silently run every GEMM on the fp32 kernels (round 4's advice)
-            if on or str(k[0]).startswith('split-'):
-                _tile_cache.setdefault(tuple(k), int(v))
+    if use_pretuned:
+        # tuner off (train.py --autotune 0): the tile heuristic replaces the table's tile codes, but WHICH FORM a launch of an
+        # 'f32x3' network takes (split on the bf16 pipe / fp32 MFMA) has no heuristic -- those entries are loaded either way,
+        # otherwise such a network would silently run every GEMM on the fp32 kernels (round 4's advice)
+        use_pretuned_table(only_split=not on)
 
 
-def use_pretuned_table():
+def autotune_on():
+    return _autotune
+
+
+def _merge_table(entries, overwrite, only_split=False):
+    """[[key, tile code], ...] (save_tile_choices' form) into the table; overwrite: an entry replaces the one the table holds"""
+    for k, v in entries:
+        if overwrite:
+            _tile_cache[tuple(k)] = int(v)
+        elif not only_split or str(k[0]).startswith('split-'):
+            _tile_cache.setdefault(tuple(k), int(v))
+
+
+def use_pretuned_table(only_split=False):
     """Load the shipped table WITHOUT switching the tuner on: what the sampling path reads (conv_dgrad_relu's tile codes, the split /
     fp32 decisions of 'f32x3'); launches that tune ignore tile codes while the tuner is off, so nothing else changes."""
     if os.path.exists(_PRETUNED) and os.environ.get('MCG_NO_PRETUNED') != '1':
-        for k, v in json.load(open(_PRETUNED)):
-            _tile_cache.setdefault(tuple(k), int(v))
+        with open(_PRETUNED) as f:
+            _merge_table(json.load(f), overwrite=False, only_split=only_split)
 
 
 def reset_tuning():
@@ -316,15 +358,19 @@ def tile_choices():
 def save_tile_choices(path):
     """Persist the tuned choices (JSON) so that a later process -- or a profiler pass that must not see the
     tuning launches -- can start from them."""
-    import json
     with open(path, 'w') as f:
         json.dump([[list(k), v] for k, v in _tile_cache.items()], f)
 
 
 def load_tile_choices(path):
-    import json
-    for k, v in json.load(open(path)):
-        _tile_cache[tuple(k)] = int(v)
+    with open(path) as f:
+        _merge_table(json.load(f), overwrite=True)
+
+
+def replace_tile_choices(entries):
+    """the table becomes exactly `entries` ([[key, tile code], ...]): every data-parallel rank takes rank 0's choices"""
+    _tile_cache.clear()
+    _merge_table(entries, overwrite=True)
 
 
 def with_precision(g, precision):
@@ -384,31 +430,13 @@ def split_pays(kind, g, run_plain, run_split):
         global _warned_undecided_split
         if not _warned_undecided_split:
             _warned_undecided_split = True
-            import warnings
             warnings.warn("precision 'f32x3': the tile tuner is off and the table holds no decision for %s N=%d T=%d H=%d Ci=%d Co=%d -- "
                           "this launch (and every other undecided one) runs the fp32-MFMA form; hiplib.set_autotune(True), "
                           "MCG_SPLIT=always or a loaded tile table decide it" % (kind, g.N, g.Ti, g.Hi, g.Ci, g.Co))
         return False
     if c is None:
-        global _timing
-        saved, _timing = _timing, None
-        try:
-            best = {}
-            for name, fn in (('plain', run_plain), ('split', run_split)):
-                fn()
-                for _ in range(3):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    fn()
-                    fn()
-                    e1.record()
-                    e1.synchronize()
-                    ms = e0.elapsed_time(e1)
-                    best[name] = ms if name not in best else min(best[name], ms)
-            c = int(best['split'] < 0.97 * best['plain'])
-        finally:
-            _timing = saved
-        _tile_cache[key] = c
+        plain_ms = _best_ms(run_plain)
+        _tile_cache[key] = c = int(_best_ms(run_split) < 0.97 * plain_ms)
     return bool(c)
 
 
@@ -425,67 +453,48 @@ def _tuned(kind, g, extra, out_side, run_on):
     key = _geom_key(kind, g, extra)
     code = _tile_cache.get(key)
     if code is None:
-        global _timing
-        saved, _timing = _timing, None                      # tuning launches are not part of any measurement
-        cur = torch.cuda.current_stream()
         best, code = None, 0
         gg = ConvGeom.from_buffer_copy(g)
         scratch = _scratch_like(g, out_side)
-
-        def run(geom):
-            run_on(geom, scratch)
-        try:
-            cands = TILE_CANDIDATES
-            if (kind == "dgrad" and 4 < g.Ci <= 64) or (kind == "fprop" and g.Co <= 64 and g.Ci > 4):
-                cands = cands + (4,)                                # 256 x 64: the widest tile a 64-column output admits
-            if kind == "wgrad" and g.Ci == 4:
-                cands = cands + (6,)                                # patch-in-LDS kernel (also what tile 0 selects when it applies)
-            out_elems = g.N * g.To * g.Ho * g.Wo * g.Co if kind == "fprop" else g.N * g.Ti * g.Hi * g.Wi * g.Ci
-            if kind in ("fprop", "dgrad") and g.Ci > 4 and out_elems <= (1 << (23 if kind == "fprop" else 25)):
-                cands = cands + FPROP_SPLIT_CANDIDATES          # <= 1024 tiles of 64x64: K splits can fill the CUs
-            if g.precision == PREC_BF16_STORE and g.Ci >= 64 and g.Co >= 64:
-                # the LDS-DMA kernels (the library refuses what they do not cover).  fp32 networks can run them too (tile codes
-                # 7 / 8 by request), but measured on the MI355X they do not beat the register-staged fp32 kernels: 110-127
-                # against 128-134 TFLOP/s on the big layers, and one 256-row block per CU quantises badly at batch 32
-                if not (kind == "dgrad" and g.Ci == 64):        # (64 output columns per parity class: the 256x64 tile never wins)
-                    cands = cands + V2_CANDIDATES
-                    if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
-                        cands = cands + WGRAD_SPLIT_CANDIDATES
-                else:
-                    cands = cands + (10,)                       # ... but 256x64 with two buffers lets two blocks share a CU
-                    if g.Ho == 16 and g.Wo == 16:
-                        cands = cands + (9,)                    # ... and the patch-stationary kernel, four classes per block, is made for it
-            if g.precision == PREC_F32 and g.Ci >= 64 and g.Co >= 64 and kind != "dgrad" or (g.precision == PREC_F32 and kind == "dgrad" and g.Ci >= 128 and g.Co >= 64):
-                cands = cands + (10,)                           # the LDS-DMA kernel on fp32 operands, 128x128, two blocks per CU
-            if g.precision == PREC_SPLIT:
-                # (the LDS-DMA kernels are the only ones that multiply split operands; one 256-row block per CU: late layers need K splits)
-                cands = V2_CANDIDATES + ((1007, 2007, 1010, 2010) if kind in ("fprop", "dgrad") and out_elems <= (1 << 25) else ())
+        cands = TILE_CANDIDATES
+        if (kind == "dgrad" and 4 < g.Ci <= 64) or (kind == "fprop" and g.Co <= 64 and g.Ci > 4):
+            cands = cands + (4,)                                # 256 x 64: the widest tile a 64-column output admits
+        if kind == "wgrad" and g.Ci == 4:
+            cands = cands + (6,)                                # patch-in-LDS kernel (also what tile 0 selects when it applies)
+        out_elems = g.N * g.To * g.Ho * g.Wo * g.Co if kind == "fprop" else g.N * g.Ti * g.Hi * g.Wi * g.Ci
+        if kind in ("fprop", "dgrad") and g.Ci > 4 and out_elems <= (1 << (23 if kind == "fprop" else 25)):
+            cands = cands + FPROP_SPLIT_CANDIDATES          # <= 1024 tiles of 64x64: K splits can fill the CUs
+        if g.precision == PREC_BF16_STORE and g.Ci >= 64 and g.Co >= 64:
+            # the LDS-DMA kernels (the library refuses what they do not cover).  fp32 networks can run them too (tile codes
+            # 7 / 8 by request), but measured on the MI355X they do not beat the register-staged fp32 kernels: 110-127
+            # against 128-134 TFLOP/s on the big layers, and one 256-row block per CU quantises badly at batch 32
+            if not (kind == "dgrad" and g.Ci == 64):        # (64 output columns per parity class: the 256x64 tile never wins)
+                cands = cands + V2_CANDIDATES
                 if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
-                    # few (Co, tap x Ci) tiles -- the 2-D layers: many pixel splits then add onto the same small dw with float
-                    # atomics; + 2000 halves / + 1000 doubles the number of splits (round 6)
                     cands = cands + WGRAD_SPLIT_CANDIDATES
-                if kind == "dgrad" and g.Ci == 64 and g.Ho == 16 and g.Wo == 16:
-                    cands = cands + (9,)                        # the patch-stationary kernel (four parity classes per block)
-            for cand in cands:
-                gg.tile = cand
-                try:
-                    run(gg)                                 # warm-up (and rejects impossible candidates)
-                except McgError:
-                    continue
-                ms = None
-                for _ in range(3):                          # best of three timings of two launches each
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(cur)
-                    run(gg)
-                    run(gg)
-                    e1.record(cur)
-                    e1.synchronize()
-                    t = e0.elapsed_time(e1)
-                    ms = t if ms is None or t < ms else ms
-                if best is None or ms < best:
-                    best, code = ms, cand
-        finally:
-            _timing = saved
+            else:
+                cands = cands + (10,)                       # ... but 256x64 with two buffers lets two blocks share a CU
+                if g.Ho == 16 and g.Wo == 16:
+                    cands = cands + (9,)                    # ... and the patch-stationary kernel, four classes per block, is made for it
+        if g.precision == PREC_F32 and g.Ci >= 64 and g.Co >= 64 and kind != "dgrad" or (g.precision == PREC_F32 and kind == "dgrad" and g.Ci >= 128 and g.Co >= 64):
+            cands = cands + (10,)                           # the LDS-DMA kernel on fp32 operands, 128x128, two blocks per CU
+        if g.precision == PREC_SPLIT:
+            # (the LDS-DMA kernels are the only ones that multiply split operands; one 256-row block per CU: late layers need K splits)
+            cands = V2_CANDIDATES + ((1007, 2007, 1010, 2010) if kind in ("fprop", "dgrad") and out_elems <= (1 << 25) else ())
+            if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
+                # few (Co, tap x Ci) tiles -- the 2-D layers: many pixel splits then add onto the same small dw with float
+                # atomics; + 2000 halves / + 1000 doubles the number of splits (round 6)
+                cands = cands + WGRAD_SPLIT_CANDIDATES
+            if kind == "dgrad" and g.Ci == 64 and g.Ho == 16 and g.Wo == 16:
+                cands = cands + (9,)                        # the patch-stationary kernel (four parity classes per block)
+        for cand in cands:
+            gg.tile = cand
+            try:
+                ms = _best_ms(lambda: run_on(gg, scratch))      # (the warm-up rejects impossible candidates)
+            except McgError:
+                continue
+            if best is None or ms < best:
+                best, code = ms, cand
         _tile_cache[key] = code
     if not code:
         return g
@@ -902,14 +911,8 @@ def split_planes_multi(items):
     for q, (src, run, dst) in zip(segs, items):
         assert src.is_contiguous() and dst.is_contiguous() and dst.dtype == torch.bfloat16 and dst.numel() == 4 * src.numel()
         q.src, q.dst, q.n, q.run = src.data_ptr(), dst.data_ptr(), src.numel(), int(run)
-    e0 = None
-    if _timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _check(load().mcg_split_planes_multi(len(items), C.cast(segs, C.c_void_p), _stream()), "mcg_split_planes_multi")
-    if e0 is not None:
-        e1.record()
-        _timing.setdefault(_tag + ".split", []).append((e0, e1))
+    _timed(lambda: _check(load().mcg_split_planes_multi(len(items), C.cast(segs, C.c_void_p), _stream()), "mcg_split_planes_multi"),
+           _tag + ".split")
 
 
 def split_planes(src, run=16, out=None):
@@ -920,14 +923,8 @@ def split_planes(src, run=16, out=None):
     if out is None:
         out = torch.empty(src.shape[:-1] + (4 * src.shape[-1],), device=src.device, dtype=torch.bfloat16)
     assert out.numel() == 4 * n and out.dtype == torch.bfloat16
-    e0 = None
-    if _timing is not None:                                      # (bench.py's roofline leg charges the pass to the network's GEMMs)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _check(load().mcg_split_planes(n, int(run), _p(src), _p(out, torch.bfloat16), _stream()), "mcg_split_planes")
-    if e0 is not None:
-        e1.record()
-        _timing.setdefault(_tag + ".split", []).append((e0, e1))
+    _timed(lambda: _check(load().mcg_split_planes(n, int(run), _p(src), _p(out, torch.bfloat16), _stream()), "mcg_split_planes"),
+           _tag + ".split")                                      # (bench.py's roofline leg charges the pass to the network's GEMMs)
     return out
 
 

@@ -98,6 +98,40 @@ def _np_to(t, device):
     return torch.as_tensor(np.asarray(t), dtype=torch.float32).to(device)
 
 
+class Operand:
+    """A GEMM operand as the networks see it: the plain tensor, its split form ('f32x3': hl.split_planes' layout) once one exists, and
+    whether the split form is the ONLY one written.  The producer of a split-only operand relied on _Net._split_only; its plain
+    tensor stays allocated -- shape, dtype, slicing -- but was never written, and `.t` refuses to hand it out: a reader cannot
+    consult the table again and read it, whatever happened between producer and reader (another geometry key for a selected
+    group, a cleared or replaced table, MCG_SPLIT changing)."""
+    __slots__ = ('_t', '_s', 'split_only')
+
+    def __init__(self, t, split=None, split_only=False):
+        assert split is not None or not split_only
+        self._t, self._s, self.split_only = t, split, split_only
+
+    @property
+    def t(self):
+        assert not self.split_only, "an operand written in the split form only has no plain tensor to read"
+        return self._t
+
+    @property
+    def dtype(self):
+        return self._t.dtype
+
+    def empty_like(self, dtype):
+        return torch.empty_like(self._t, dtype=dtype)
+
+    def split(self):
+        """the split form, made once: forward keeps what the weight gradient reads again"""
+        if self._s is None:
+            self._s = hl.split_planes(self.t)
+        return self._s
+
+    def __getitem__(self, rows):
+        return Operand(self._t[rows], None if self._s is None else self._s[rows], self.split_only)
+
+
 class _Net:
     """Shared parameter plumbing.  ``ref_shapes`` maps Chainer keys to Chainer shapes."""
 
@@ -134,27 +168,27 @@ class _Net:
     def _wsplit(self, name, form):
         """the split form of a filter: 'f' as the forward GEMM of a convolution reads it (groups of 16 input channels), 'd' as the
         input-gradient GEMM does (planes of 16 filters).  Rebuilt when the parameters have changed since (FlatParams.version)."""
-        cache = self.__dict__.setdefault('_wsplits', {})
+        cache = self._wsplits
         ent = cache.get((name, form))
         if ent is None or ent[0] != self.fp.version:
             w = self.fp.param(name)
             run = 16 if form == 'f' else 16 * (w.numel() // w.shape[0])
             out = hl.split_planes(w, run=run, out=ent[1] if ent else None)
             cache[(name, form)] = ent = (self.fp.version, out)
-        self.__dict__.setdefault('_wsplit_used', set()).add((name, form))     # read since the last refresh: worth refreshing again
+        self._wsplit_used.add((name, form))     # read since the last refresh: worth refreshing again
         return ent[1]
 
     def refresh_wsplits(self):
         """Right after this network's Adam update ('f32x3' networks): every (filter, form) pair its launches have used so far is
         re-split in ONE launch (mcg_split_planes_multi) instead of one launch per pair on first use -- 15 launches per iteration
         became 2-3.  Pairs not yet in the cache (the first iteration) are still split on first use by _wsplit."""
-        cache = self.__dict__.get('_wsplits')
+        cache = self._wsplits
         if not cache or self.precision != 'f32x3' or os.environ.get('MCG_WSPLIT_MULTI', '1') != '1':
             return
         # only the pairs a launch has READ since the last refresh: hl.split_pays' timed trial of a geometry where the split form
         # then lost also fills the cache, and such a filter would be re-split every iteration and never read (round 5's advice);
         # a pair that was not refreshed keeps its old version and is rebuilt by _wsplit if a launch ever asks for it again
-        used, self._wsplit_used = self.__dict__.get('_wsplit_used', set()), set()
+        used, self._wsplit_used = self._wsplit_used, set()
         items, keys = [], []
         for (name, form), (ver, out) in cache.items():
             if ver != self.fp.version and (name, form) in used:
@@ -173,23 +207,22 @@ class _Net:
         for key in keys:
             cache[key] = (self.fp.version, cache[key][1])
 
-    def _cfprop(self, g, x, wname, w, b, y, ep=None, must_fuse=False, xs=None, force=False):
-        """hl.conv_fprop of this network (w = the filter operand the caller would pass; xs: callable returning the split form of x).
-        force: x exists in its split form ONLY (its producer relied on _split_only): the split launch is the only correct one."""
-        if force:
-            assert self.precision == 'f32x3' and hl.split_covers('fprop', g) and xs is not None, "an operand written in the split form only needs the split launch"
-            return hl.conv_fprop(hl.with_precision(g, 'f32x3'), xs(), self._wsplit(wname, 'f'), b, y, ep=ep, must_fuse=must_fuse)
-        if self.precision == 'f32x3' and hl.split_covers('fprop', g):
-            gs = hl.with_precision(g, 'f32x3')
+    def _conv(self, kind, g, a, wname, w, b, out, ep=None, must_fuse=False):
+        """hl.conv_fprop / hl.conv_dgrad (kind 'fprop' | 'dgrad'; no activation, not accumulating: the launches that have a split
+        form) of this network on operand a; w = the filter the plain launch reads.  A split-only operand takes the split launch
+        (where none exists, Operand.t refuses the plain one), any other the form that pays (hl.split_pays).  Returns what the
+        launch returns: was the epilogue fused?"""
+        launch = hl.conv_fprop if kind == 'fprop' else hl.conv_dgrad
 
-            def plain():
-                return hl.conv_fprop(g, x, w, b, y, ep=ep, must_fuse=must_fuse)
+        def plain():
+            return launch(g, a.t, w, b, out, ep=ep, must_fuse=must_fuse)
+        if not (self.precision == 'f32x3' and hl.split_covers(kind, g)):
+            return plain()
+        gs = hl.with_precision(g, 'f32x3')
 
-            def split():
-                return hl.conv_fprop(gs, xs() if xs else hl.split_planes(x), self._wsplit(wname, 'f'), b, y, ep=ep, must_fuse=must_fuse)
-            if hl.split_pays('fprop', g, plain, split):
-                return split()
-        return hl.conv_fprop(g, x, w, b, y, ep=ep, must_fuse=must_fuse)
+        def split():
+            return launch(gs, a.split(), self._wsplit(wname, kind[0]), b, out, ep=ep, must_fuse=must_fuse)
+        return split() if a.split_only or hl.split_pays(kind, g, plain, split) else plain()
 
     def _fuse_bwd_sums(self, s16, kind, g):
         """should the GEMM (kind, g) that produces a gradient also produce the sums of the BatchNorm backward pass that reads it?"""
@@ -211,67 +244,39 @@ class _Net:
 
     def _split_only(self, *launches):
         """'f32x3': may the producer of a tensor write its split form ONLY?  Yes when every GEMM that reads it -- launches:
-        (pass, geometry) pairs -- is known to take the split form (hl.split_decided); the fp32 tensor then stays allocated (shapes,
-        slicing) but is never written nor read.  The caller RECORDS the decision (saved['only'] / a local flag) and passes it to
-        _cfprop / _cdgrad / _cwgrad as force=True: a reader never consults the table again, so nothing that happens between the
-        producer and the reader (another geometry key for a selected group, a cleared or replaced table, MCG_SPLIT changing) can make
-        it read the unwritten fp32 tensor."""
+        (pass, geometry) pairs -- is known to take the split form (hl.split_decided)."""
         return (self.precision == 'f32x3' and self.sync_bn is None and os.environ.get('MCG_SPLIT_ONLY', '1') == '1'
                 and all(hl.split_decided(kind, g) for kind, g in launches))
 
-    @staticmethod
-    def _sp(store, key, t):
-        """the split form of tensor t, made once per (store, key): forward keeps what the weight gradient reads again"""
-        if store is None:
-            return hl.split_planes(t)
-        s = store.get(key)
-        if s is None:
-            s = store[key] = hl.split_planes(t)
-        return s
+    def _operand(self, t, *readers):
+        """The operand an element-wise launch produces for the GEMMs `readers` ((pass, geometry) pairs; none: an fp32 operand) in
+        place of the plain tensor t -> (operand, the tensor the launch writes, its split_out flag).  'f32x3': when every reader
+        takes the split form the launch writes that form only; t keeps its allocation (shape, slicing) and is never written."""
+        if readers and self._split_only(*readers):
+            s = torch.empty(t.shape[:-1] + (4 * t.shape[-1],), device=t.device, dtype=torch.bfloat16)
+            return Operand(t, s, True), s, True
+        return Operand(t), t, False
 
-    def _cwgrad(self, g, x, y, dw, xs=None, ys=None, force=False):
-        """self._wgrad (dw += ...); xs / ys: callables returning the split form of x / y; force: as _cfprop (x or y has no fp32 form)"""
-        if force:
-            assert self.precision == 'f32x3' and hl.split_covers('wgrad', g) and xs is not None and ys is not None, \
-                "an operand written in the split form only needs the split launch"
-            return self._wgrad(hl.with_precision(g, 'f32x3'), xs(), ys(), dw)
-        if self.precision == 'f32x3' and hl.split_covers('wgrad', g):
-            gs = hl.with_precision(g, 'f32x3')
-            xs = xs or (lambda: hl.split_planes(x))
-            ys = ys or (lambda: hl.split_planes(y))
+    def _cwgrad(self, g, x, y, dw):
+        """self._wgrad (dw += ...) on operands x, y: the split launch when either exists in that form only, else the form that pays"""
+        if not (self.precision == 'f32x3' and hl.split_covers('wgrad', g)):
+            return self._wgrad(g, x.t, y.t, dw)
+        gs = hl.with_precision(g, 'f32x3')
 
-            def plain():
-                hl.conv_wgrad(g, x, y, self._wg_scratch(dw))
+        def plain():
+            hl.conv_wgrad(g, x.t, y.t, self._wg_scratch(dw))
 
-            def split():
-                hl.conv_wgrad(gs, xs(), ys(), self._wg_scratch(dw))
-            if hl.split_pays('wgrad', g, plain, split):
-                return self._wgrad(gs, xs(), ys(), dw)
-        return self._wgrad(g, x, y, dw)
+        def split():
+            hl.conv_wgrad(gs, x.split(), y.split(), self._wg_scratch(dw))
+        if x.split_only or y.split_only or hl.split_pays('wgrad', g, plain, split):
+            return self._wgrad(gs, x.split(), y.split(), dw)
+        return self._wgrad(g, x.t, y.t, dw)
 
     def _wg_scratch(self, dw):
         """a stand-in for dw while the two forms of a weight gradient are timed (the launch ADDS into its output)"""
-        sc = self.__dict__.get('_wgs')
-        if sc is None or sc.numel() < dw.numel():
-            sc = self.__dict__['_wgs'] = torch.zeros(dw.numel(), device=dw.device)
-        return sc[:dw.numel()].view(dw.shape)
-
-    def _cdgrad(self, g, y, wname, w, b, x, ep=None, must_fuse=False, ys=None, force=False):
-        """hl.conv_dgrad of this network (no activation, not accumulating: the launches that have a split form); force: as _cfprop"""
-        if force:
-            assert self.precision == 'f32x3' and hl.split_covers('dgrad', g) and ys is not None, "an operand written in the split form only needs the split launch"
-            return hl.conv_dgrad(hl.with_precision(g, 'f32x3'), ys(), self._wsplit(wname, 'd'), b, x, ep=ep, must_fuse=must_fuse)
-        if self.precision == 'f32x3' and hl.split_covers('dgrad', g):
-            gs = hl.with_precision(g, 'f32x3')
-
-            def plain():
-                return hl.conv_dgrad(g, y, w, b, x, ep=ep, must_fuse=must_fuse)
-
-            def split():
-                return hl.conv_dgrad(gs, ys() if ys else hl.split_planes(y), self._wsplit(wname, 'd'), b, x, ep=ep, must_fuse=must_fuse)
-            if hl.split_pays('dgrad', g, plain, split):
-                return split()
-        return hl.conv_dgrad(g, y, w, b, x, ep=ep, must_fuse=must_fuse)
+        if self._wgs is None or self._wgs.numel() < dw.numel():
+            self._wgs = torch.zeros(dw.numel(), device=dw.device)
+        return self._wgs[:dw.numel()].view(dw.shape)
 
     def _stored16(self, ci, co):
         """does a layer with these channel counts run on bf16-stored operands?"""
@@ -371,13 +376,64 @@ class _Net:
         self.fp = FlatParams(specs, self.device)
         self.t = 0                                             # Adam step counter of this net's optimizer
         self.ws = torch.empty(hl.bn_workspace_floats(1024), dtype=torch.float32, device=self.device)
-        self._part = None                                      # per-tile partial sums of fused conv epilogues (grown on demand)
+        self._reset_derived()
+
+    def _reset_derived(self):
+        """drops every buffer that is derived from the parameters or grown on demand: each is rebuilt, on the network's device, by
+        its first use"""
+        self._part = None                                      # per-tile partial sums of fused conv epilogues
+        self._wsplits = {}                                     # 'f32x3': {(filter, form): (FlatParams.version, split filter)}
+        self._wsplit_used = set()                              # ... and the pairs a launch has read since the last refresh_wsplits
+        self._wgs = None                                       # _wg_scratch
+        self._fold = self._fold16 = None                       # the sampling path: filters with BatchNorm folded in (+ bf16 shadow),
+        self._fold_splits = {}                                 # ... their split forms ('f32x3'),
+        self._sbuf = [None, None, None]                        # ... the ping-pong activation buffers and sample_many's bytes (_sview),
+        self._unit_ss = None                                   # ... the (1, 0) scale / shift of its ReLU pass
+        self._one_bias = None                                  # (1, dc5/b): scale / shift of the bias + tanh pass (_bias_tanh)
 
     def _part_buf(self, geom, kind, groups):
         n = hl.epilogue_part_floats(geom, kind, groups)
         if self._part is None or self._part.numel() < n:
             self._part = torch.empty(n, dtype=torch.float32, device=self.device)
         return self._part
+
+    # ---- BatchNorm: statistics / backward from the producing GEMM's partial sums, else by the stand-alone pass --------------------
+    def _bn_stats(self, name, key, m, c, y, pending, update_stats):
+        """Train-mode statistics [mean | istd | scale | shift] of BatchNorm `name` over y [m][c].  pending: (epilogue, partial sums)
+        the GEMM that produced y left, or None.  update_stats: the running averages advance -- read-modify-write state shared
+        by the two calls of an iteration, hence ordered between the chains (key)."""
+        stats = torch.empty(4 * c, device=self.device)
+        gamma, beta = self.fp.param(name + '/gamma'), self.fp.param(name + '/beta')
+        rm = self.running[name + '/avg_mean'] if update_stats else None
+        rv = self.running[name + '/avg_var'] if update_stats else None
+        if pending is not None:
+            ep, part = pending
+            self._ordered(key, lambda: hl.bn_stats_from_partials(m, c, part, ep.n_slots, ep.slot_stride, gamma, beta, stats, rm, rv, self.ws))
+        else:
+            self._ordered(key, lambda: hl.bn_stats(m, c, y, gamma, beta, stats, rm, rv, self.ws, sync=self.sync_bn))
+        if update_stats:
+            self.bn_count[name] += 1
+        return stats
+
+    def _bn_bwd(self, name, m, c, g, y, stats, act, pending, out, param_grads=True, split_out=False):
+        """Backward of act(BatchNorm `name`(y)) for the incoming gradient g, written to `out` (split_out: in the split layout).
+        pending: (epilogue, partial sums) when the GEMM that produced g left the per-channel sums, or None.  param_grads: gamma's
+        and beta's gradients are accumulated into the flat gradient."""
+        dg = self.fp.grad(name + '/gamma') if param_grads else None
+        db = self.fp.grad(name + '/beta') if param_grads else None
+        if pending is not None:
+            ep, part = pending
+            hl.bn_act_bwd_from_partials(m, c, g, y, stats, self.fp.param(name + '/gamma'), act, part, ep.n_slots, ep.slot_stride, out,
+                                        dg, db, self.ws, split_out=split_out)
+        else:
+            hl.bn_act_bwd(m, c, g, y, stats, self.fp.param(name + '/gamma'), act, out, dg, db, self.ws, sync=self.sync_bn,
+                          split_out=split_out)
+
+    def _test_scale_shift(self, name):
+        """fixed_batch_normalization (test mode, reference util.py:92): scale/shift from running stats."""
+        inv = torch.rsqrt(self.running[name + '/avg_var'] + 2e-5)
+        scale = self.fp.param(name + '/gamma') * inv
+        return torch.cat((scale, self.fp.param(name + '/beta') - self.running[name + '/avg_mean'] * scale))
 
     # ---- reference-layout import / export (also the .npz checkpoint format, train.py:139-144) ----
     def load_reference_params(self, params):
@@ -432,13 +488,10 @@ class _Net:
         if self.fp.p16 is not None:
             self.fp.p16 = self.fp.p16.to(device)
         self.fp.touch()
-        self.__dict__.pop('_wsplits', None)
-        for k in ('_fold', '_fold16', '_fold_splits', '_sbuf', '_unit_ss'):      # the sampling path's buffers are rebuilt on the new device
-            self.__dict__.pop(k, None)
         self.running = {k: v.to(device) for k, v in self.running.items()}
         self.ws = self.ws.to(device)
-        self._part = None
         self.device = device
+        self._reset_derived()
         return self
 
     def _bn_keys(self, name, c):
@@ -564,12 +617,12 @@ class DisNet(_Net):
 
         fuse_stats = train and 'stats' in FUSE and self.sync_bn is None
         fuse_dc1 = 'dc1' in FUSE
-        saved = {'n': n, 'G': G, 'a': {}, 'y': {}, 'stats': {}, 'mask1': None, 'split': {}, 'only': set()}
+        saved = {'n': n, 'G': G, 'a': {}, 'y': {}, 'stats': {}, 'mask1': None}
         t, h = self._extents(1)
-        a = torch.empty((N, t, h, h, self.cp0), device=dev)
+        x = torch.empty((N, t, h, h, self.cp0), device=dev)
         for gi, grp in enumerate(groups):
-            grp['first_input'](a[gi * n:(gi + 1) * n], noise_args(grp, 1))
-        saved['a'][1] = a
+            grp['first_input'](x[gi * n:(gi + 1) * n], noise_args(grp, 1))
+        a = saved['a'][1] = Operand(x)                           # (saved['a'][l]: the operand layer l's GEMMs read)
         for l in (1, 2, 3, 4):
             g = self._geom(l, N)
             co = self.chans[l]
@@ -579,16 +632,13 @@ class DisNet(_Net):
             if l == 1 and fuse_dc1:
                 # dc1 has no BatchNorm: leaky_relu + add_noise run in its epilogue (model/net.py:148-149,189-190); what
                 # backward needs of the pre-activation -- its sign -- is kept as one bit per element
-                a = torch.empty((N, g.To, g.Ho, g.Wo, co), device=dev, dtype=adt)
+                a2 = torch.empty((N, g.To, g.Ho, g.Wo, co), device=dev, dtype=adt)
                 mask = torch.empty((G * m, (co + 31) // 32), dtype=torch.int32, device=dev)
                 # 'f32x3' (round 6): when both GEMMs of layer 2 that read this tensor take the split form, the epilogue writes the
                 # three bf16 terms directly (MCG_IO_OUT_SPLIT) -- the fp32 tensor is never written, and the pass that read it back
                 # and split it (0.65 GB of traffic at 64 clips, the largest operand split of the iteration) is gone
-                a_split = None
                 g2 = self._geom(2, N)
-                if DC1_SPLIT_OUT and self._split_only(('fprop', g2), ('wgrad', g2)) and co % 16 == 0:
-                    a_split = saved['split'][2] = torch.empty(a.shape[:-1] + (4 * co,), device=dev, dtype=torch.bfloat16)
-                    saved['only'].add(2)                         # saved['a'][2] stays unwritten
+                a2, out, split_out = self._operand(a2, *((('fprop', g2), ('wgrad', g2)) if DC1_SPLIT_OUT and co % 16 == 0 else ()))
                 na = [noise_args(grp, 2) for grp in groups]
                 kw = {}
                 if na[0]:
@@ -598,66 +648,47 @@ class DisNet(_Net):
                     else:
                         assert all(x['seed'] == na[0]['seed'] for x in na)
                         kw = dict(sigma=na[0]['sigma'], seed=na[0]['seed'], stream_id=[x['stream_id'] for x in na])
-                hl.conv_fprop(g, saved['a'][1], w, b, a_split if a_split is not None else a, must_fuse=True,
+                hl.conv_fprop(g, a.t, w, b, out, must_fuse=True,
                               ep=hl.epilogue(act=hl.ACT_LRELU, groups=G, mask_out=mask, out_bf16=adt == torch.bfloat16,
-                                             out_split=a_split is not None, **kw))
-                saved['y'][1], saved['mask1'], saved['a'][2] = None, mask, a
+                                             out_split=split_out, **kw))
+                saved['y'][1], saved['mask1'] = None, mask
+                a = saved['a'][2] = a2
                 continue
             # bf16 networks: the pre-BatchNorm values are bf16 too (the element-wise passes that read them are HBM-bound)
             # -- unless the tuned tile splits K (partial tiles are added in fp32) or the statistics need the stand-alone pass
             y16 = (OUT16 and l >= 2 and self._s16(l) and self.sync_bn is None and (fuse_stats or not train)
-                   and hl.fprop_tile(g, a, w, b) < 1000)
+                   and hl.fprop_tile(g, a.t, w, b) < 1000)
             y = torch.empty((N, g.To, g.Ho, g.Wo, co), device=dev, dtype=torch.bfloat16 if y16 else torch.float32)
-            ep = None
+            pending = None                                       # (epilogue, partial sums) when the convolution carried the statistics
             if l >= 2 and fuse_stats:
                 part = self._part_buf(g, 'fprop', G)
                 ep = hl.epilogue(sums=hl.SUMS_STATS, groups=G, part=part, out_bf16=y16)
-                if not self._cfprop(g, a, 'dc%d/W' % l, w, b, y, ep=ep, xs=lambda: self._sp(saved['split'], l, saved['a'][l]), force=l in saved['only']):
-                    ep = None                                    # split-K tile: the stand-alone statistics pass below
+                if self._conv('fprop', g, a, 'dc%d/W' % l, w, b, y, ep=ep):
+                    pending = (ep, part)                         # (not with a split-K tile: the stand-alone statistics pass below)
             else:
-                self._cfprop(g, a, 'dc%d/W' % l, w, b, y, xs=lambda: self._sp(saved['split'], l, saved['a'][l]), force=l in saved['only'])
+                self._conv('fprop', g, a, 'dc%d/W' % l, w, b, y)
             saved['y'][l] = y
-            a = torch.empty_like(y, dtype=adt)
-            a_split = None                                       # 'f32x3': layer l + 1's GEMMs both read the split form -> written directly
-            if l < 4:
-                gn = self._geom(l + 1, N)
-                if self._split_only(('fprop', gn), ('wgrad', gn)):
-                    a_split = saved['split'][l + 1] = torch.empty(y.shape[:-1] + (4 * co,), device=dev, dtype=torch.bfloat16)
-                    saved['only'].add(l + 1)                     # saved['a'][l + 1] stays unwritten
+            # 'f32x3': layer l + 1's GEMMs both read the split form -> written directly
+            gn = self._geom(l + 1, N) if l < 4 else None
+            a, out, split_out = self._operand(torch.empty_like(y, dtype=adt), *((('fprop', gn), ('wgrad', gn)) if l < 4 else ()))
             if l >= 2:
                 saved['stats'][l] = []
             for gi, grp in enumerate(groups):
-                yg, ag = y[gi * n:(gi + 1) * n], a[gi * n:(gi + 1) * n]
+                rows = slice(gi * n, (gi + 1) * n)
                 ss = None
                 if l >= 2:
                     name = 'bn%d' % l
                     if train:
-                        stats = torch.empty(4 * co, device=dev)
-                        rm = self.running[name + '/avg_mean'] if update_stats else None
-                        rv = self.running[name + '/avg_var'] if update_stats else None
-                        # (the running averages are read-modify-write state shared by the two calls of an iteration: ordered)
-                        if ep is not None:
-                            self._ordered(('stats', l), lambda: hl.bn_stats_from_partials(
-                                m, co, part[gi * 2 * co:], ep.n_slots, ep.slot_stride, self.fp.param(name + '/gamma'),
-                                self.fp.param(name + '/beta'), stats, rm, rv, self.ws))
-                        else:
-                            self._ordered(('stats', l), lambda: hl.bn_stats(
-                                m, co, yg, self.fp.param(name + '/gamma'), self.fp.param(name + '/beta'), stats, rm, rv,
-                                self.ws, sync=self.sync_bn))
-                        if update_stats:
-                            self.bn_count[name] += 1
+                        stats = self._bn_stats(name, ('stats', l), m, co, y[rows], pending and (pending[0], pending[1][gi * 2 * co:]), update_stats)
                         saved['stats'][l].append(stats)
                         ss = stats[2 * co:]
                     else:
                         ss = self._test_scale_shift(name)
-                if a_split is not None:
-                    hl.bn_act_fwd(m, co, yg, ss, hl.ACT_LRELU, a_split[gi * n:(gi + 1) * n], split_out=True, **noise_args(grp, l + 1))
-                else:
-                    hl.bn_act_fwd(m, co, yg, ss, hl.ACT_LRELU, ag, **(noise_args(grp, l + 1) if l < 4 else {}))
+                hl.bn_act_fwd(m, co, y[rows], ss, hl.ACT_LRELU, out[rows], split_out=split_out, **(noise_args(grp, l + 1) if l < 4 else {}))
             saved['a'][l + 1] = a
-        k = a[0].numel()
+        k = a.t[0].numel()
         logits = torch.empty((N, self.out_channels), device=dev)
-        hl.fc_fprop(N, k, self.out_channels, a.view(N, k), self.fp.param('dc5/W').view(self.out_channels, k),
+        hl.fc_fprop(N, k, self.out_channels, a.t.view(N, k), self.fp.param('dc5/W').view(self.out_channels, k),
                     self.fp.param('dc5/b'), logits)
         return logits, saved
 
@@ -672,15 +703,9 @@ class DisNet(_Net):
         if mask is not None:
             rows = mask.shape[0] // saved['G']
             mask = mask[gi * rows:(gi + 1) * rows]
-        return {'n': n, 'G': 1, 'a': {l: v[sl] for l, v in saved['a'].items()}, 'split': {l: v[sl] for l, v in saved.get('split', {}).items()},
+        return {'n': n, 'G': 1, 'a': {l: v[sl] for l, v in saved['a'].items()},
                 'y': {l: (None if v is None else v[sl]) for l, v in saved['y'].items()},
-                'stats': {l: [v[gi]] for l, v in saved['stats'].items()}, 'mask1': mask, 'only': set(saved.get('only', ()))}
-
-    def _test_scale_shift(self, name):
-        """fixed_batch_normalization (test mode, reference util.py:92): scale/shift from running stats."""
-        inv = torch.rsqrt(self.running[name + '/avg_var'] + 2e-5)
-        scale = self.fp.param(name + '/gamma') * inv
-        return torch.cat((scale, self.fp.param(name + '/beta') - self.running[name + '/avg_mean'] * scale))
+                'stats': {l: [v[gi]] for l, v in saved['stats'].items()}, 'mask1': mask}
 
     # ---- backward --------------------------------------------------------------------------
     def grad_bucket_late(self):
@@ -701,7 +726,7 @@ class DisNet(_Net):
         fp = self.fp
         hl.set_tag(self.tag)
         assert gx is None or G == 1
-        a5 = saved['a'][5]
+        a5 = saved['a'][5].t
         k = a5[0].numel()
         co5 = self.out_channels
         if param_grads:
@@ -721,83 +746,66 @@ class DisNet(_Net):
                 name = 'bn%d' % l
                 gy = torch.empty_like(g, dtype=torch.bfloat16) if s16 else g       # bf16-stored operand of wgrad / dgrad, else in place
                 # 'f32x3': both GEMMs that read gy take the split form -> written in that form only (g keeps its shape, not its meaning)
-                gy_split = None
-                if self._split_only(('dgrad', geom), *((('wgrad', geom),) if param_grads else ())):
-                    gy_split = torch.empty(g.shape[:-1] + (4 * co,), device=g.device, dtype=torch.bfloat16)
+                go, out, split_out = self._operand(gy, ('dgrad', geom), *((('wgrad', geom),) if param_grads else ()))
                 for gi in range(G):
-                    gg, yg, go = g[gi * n:(gi + 1) * n], y[gi * n:(gi + 1) * n], gy[gi * n:(gi + 1) * n]
-                    if gy_split is not None:
-                        go = gy_split[gi * n:(gi + 1) * n]
-                    dg = fp.grad(name + '/gamma') if param_grads else None
-                    db = fp.grad(name + '/beta') if param_grads else None
+                    rows = slice(gi * n, (gi + 1) * n)
+                    pend = pending and (pending[0], pending[1][gi * 2 * co:])
+                    bwd = lambda: self._bn_bwd(name, m, co, g[rows], y[rows], saved['stats'][l][gi], hl.ACT_LRELU, pend, out[rows],
+                                               param_grads, split_out)
                     # (gamma's / beta's gradients are added by a read-modify-write kernel: ordered between the chains when they are asked for)
-                    if pending is not None:
-                        ep, part = pending
-                        bwd = lambda: hl.bn_act_bwd_from_partials(m, co, gg, yg, saved['stats'][l][gi], fp.param(name + '/gamma'), hl.ACT_LRELU,
-                                                                  part[gi * 2 * co:], ep.n_slots, ep.slot_stride, go, dg, db, self.ws,
-                                                                  split_out=gy_split is not None)
-                    else:
-                        bwd = lambda: hl.bn_act_bwd(m, co, gg, yg, saved['stats'][l][gi], fp.param(name + '/gamma'), hl.ACT_LRELU, go, dg, db,
-                                                    self.ws, sync=self.sync_bn, split_out=gy_split is not None)
                     if param_grads:
                         self._ordered(('g', l), bwd)
                     else:
                         bwd()
-                g = gy
-            elif mask1 is None:
-                for gi in range(G):
-                    gg, yg = g[gi * n:(gi + 1) * n], y[gi * n:(gi + 1) * n]
-                    hl.bn_act_bwd(m, co, gg, yg, None, None, hl.ACT_LRELU, gg, None, None, self.ws)
-            # (l == 1 with a stored mask: dc2's input-gradient GEMM applied leaky_relu's backward in its epilogue)
-            gsp = {}                                             # 'f32x3': the split form of g, shared by the two GEMMs that read it
-            g_only = l >= 2 and gy_split is not None             # ... which is the ONLY form of g that was written
-            if g_only:
-                gsp[0] = gy_split
-
-            def gys():
-                return self._sp(gsp, 0, g)
+            else:
+                if mask1 is None:
+                    for gi in range(G):
+                        gg, yg = g[gi * n:(gi + 1) * n], y[gi * n:(gi + 1) * n]
+                        hl.bn_act_bwd(m, co, gg, yg, None, None, hl.ACT_LRELU, gg, None, None, self.ws)
+                # (l == 1 with a stored mask: dc2's input-gradient GEMM applied leaky_relu's backward in its epilogue)
+                go = Operand(g)
+            # go: the gradient w.r.t. dc<l>'s output as the two GEMMs that read it take it (they share its split form)
             if param_grads:
                 if l == 1:
                     if pending is not None:
                         self._ordered(('g', 1), lambda: hl.colsum_from_partials(co, pending[1], pending[0].n_slots, pending[0].slot_stride,
                                                                                 fp.grad('dc1/b'), self.ws))
                     else:
-                        self._ordered(('g', 1), lambda: hl.colsum_acc(m * G, co, g, fp.grad('dc1/b'), self.ws))
+                        self._ordered(('g', 1), lambda: hl.colsum_acc(m * G, co, go.t, fp.grad('dc1/b'), self.ws))
                 # dc2..dc4 feed BatchNorm: sum_m gx == 0 exactly (see _Net.BIAS_NOTE), nothing to add
-                wgeom = hl.with_precision(geom, 'bf16y') if (l == 1 and g.dtype == torch.bfloat16) else geom      # (a bf16 y beside the fp32 clip)
-                self._cwgrad(wgeom, saved['a'][l], g, fp.grad('dc%d/W' % l), xs=lambda: self._sp(saved.get('split'), l, saved['a'][l]), ys=gys,
-                             force=g_only or l in saved.get('only', ()))
+                wgeom = hl.with_precision(geom, 'bf16y') if (l == 1 and go.dtype == torch.bfloat16) else geom      # (a bf16 y beside the fp32 clip)
+                self._cwgrad(wgeom, saved['a'][l], go, fp.grad('dc%d/W' % l))
                 if l == 4 and on_late_bucket is not None:
                     self._after_wgrads(on_late_bucket)
             pending = None
             if l > 1:
                 w = self._w('dc%d/W' % l, s16)
                 # bf16 networks: the gradient BatchNorm's backward of layer l - 1 reads is bf16 as well (see forward_groups)
-                g16 = OUT16 and l > 2 and s16 and self.sync_bn is None and hl.dgrad_tile(geom, g, w, None) < 1000
+                g16 = OUT16 and l > 2 and s16 and self.sync_bn is None and hl.dgrad_tile(geom, go.t, w, None) < 1000
                 if l == 2 and mask1 is not None and OUT16 and Y16 and s16 and self.precision == 'bf16':
                     # ... and so is dc1's output gradient (16x the clip's size): its readers -- dc1's weight gradient and the MFMA
                     # input-gradient kernel of the first layer -- take a bf16 y beside the fp32 clip ('bf16y' launches).  Not when
                     # this pass ACCUMULATES onto a frame of the clip gradient (D_I under G's loss: the VALU kernel reads fp32).
                     g1 = self._geom(1, N)
                     ok_gx = gx is None or (not gx_accumulate and hl.dgrad_c4_mfma_covers(hl.with_precision(gx_geom if gx_geom is not None else g1, 'bf16y')))
-                    g16 = ok_gx and g1.Co % 8 == 0 and hl.dgrad_tile(geom, g, w, None) < 1000
-                ga = torch.empty_like(saved['a'][l], dtype=torch.bfloat16 if g16 else torch.float32)
+                    g16 = ok_gx and g1.Co % 8 == 0 and hl.dgrad_tile(geom, go.t, w, None) < 1000
+                ga = saved['a'][l].empty_like(torch.bfloat16 if g16 else torch.float32)
                 if l == 2 and mask1 is not None:
                     part = self._part_buf(geom, 'dgrad', 1) if param_grads else None
                     ep = hl.epilogue(mask_in=mask1, sums=hl.SUMS_COL if param_grads else hl.SUMS_NONE, groups=1, part=part, out_bf16=g16)
-                    self._cdgrad(geom, g, 'dc%d/W' % l, w, None, ga, ep=ep, must_fuse=True, ys=gys, force=g_only)
+                    self._conv('dgrad', geom, go, 'dc%d/W' % l, w, None, ga, ep=ep, must_fuse=True)
                     pending = (ep, part) if param_grads else None
                 elif l > 2 and self._fuse_bwd_sums(s16, 'dgrad', geom):
                     part = self._part_buf(geom, 'dgrad', G)
                     ep = hl.epilogue(sums=hl.SUMS_BN_BWD, groups=G, part=part, bn_y=saved['y'][l - 1], bn_stats=saved['stats'][l - 1],
                                      bn_act=hl.ACT_LRELU, out_bf16=g16)
-                    if self._with_bwd_sums(lambda e: self._cdgrad(geom, g, 'dc%d/W' % l, w, None, ga, ep=e, ys=gys, force=g_only), ep):
+                    if self._with_bwd_sums(lambda e: self._conv('dgrad', geom, go, 'dc%d/W' % l, w, None, ga, ep=e), ep):
                         pending = (ep, part)
                 else:
-                    self._cdgrad(geom, g, 'dc%d/W' % l, w, None, ga, ys=gys, force=g_only)
+                    self._conv('dgrad', geom, go, 'dc%d/W' % l, w, None, ga)
                 g = ga
             elif gx is not None:
-                def write_gx(g=g, geom=geom):
+                def write_gx(g=go.t, geom=geom):
                     hl.set_tag(self.tag)
                     gg = gx_geom if gx_geom is not None else geom
                     if g.dtype == torch.bfloat16:
@@ -942,7 +950,7 @@ class GenNet(_Net):
         fp = self.fp
         train = config.train
         hl.set_tag('G')
-        saved = {'n': n, 'draw': draw, 'y': {}, 'a': {}, 'stats': {}, 'split': {}, 'only': set()}
+        saved = {'n': n, 'draw': draw, 'y': {}, 'a': {}, 'stats': {}}
         z = torch.empty((frames, dc + dz), device=dev)
         gsaved = torch.empty((T, n, 4 * dz), device=dev)
         hl.gru_seq_fwd(n, T, dz, dl, dc, fp.param('g0'), draw['h0'], draw['e'], draw['labels'], draw['zc'], z, gsaved)
@@ -959,73 +967,59 @@ class GenNet(_Net):
             m = y.numel() // co
             name = 'bn%d' % l
             if train:
-                stats = torch.empty(4 * co, device=dev)
-                rm = self.running[name + '/avg_mean'] if update_stats else None
-                rv = self.running[name + '/avg_var'] if update_stats else None
-                if pending is not None:
-                    ep, part = pending
-                    hl.bn_stats_from_partials(m, co, part, ep.n_slots, ep.slot_stride, fp.param(name + '/gamma'), fp.param(name + '/beta'),
-                                              stats, rm, rv, self.ws)
-                else:
-                    hl.bn_stats(m, co, y, fp.param(name + '/gamma'), fp.param(name + '/beta'), stats, rm, rv, self.ws, sync=self.sync_bn)
-                if update_stats:
-                    self.bn_count[name] += 1
-                saved['stats'][l] = stats
+                stats = saved['stats'][l] = self._bn_stats(name, ('stats', l), m, co, y, pending, update_stats)
                 ss = stats[2 * co:]
             else:
-                inv = torch.rsqrt(self.running[name + '/avg_var'] + 2e-5)
-                scale = fp.param(name + '/gamma') * inv
-                ss = torch.cat((scale, fp.param(name + '/beta') - self.running[name + '/avg_mean'] * scale))
+                ss = self._test_scale_shift(name)
             saved['y'][l] = y
             a16 = self._s16(l + 1)
             if l == 4 and OUT16 and Y16 and self.precision == 'bf16' and self._s16(4) and self.sync_bn is None:
                 # the last layer's input (64 channels, 16x the clip's size) is bf16 too when its readers take a bf16 y beside the
                 # fp32 clip: the MFMA kernel of the 4-channel layers forward, 'bf16y' weight gradient backward
                 a16 = hl.dgrad_c4_mfma_covers(hl.with_precision(self._geom(5, frames, clip_order_n=n), 'bf16y'))
-            a = torch.empty_like(y, dtype=torch.bfloat16 if a16 else torch.float32)   # the operand of layer l + 1's GEMMs
-            gn = self._geom(l + 1, frames) if l < 4 else None
-            if gn is not None and self._split_only(('dgrad', gn), ('wgrad', gn)):      # 'f32x3': both readers take the split form
-                saved['split'][l + 1] = torch.empty(y.shape[:-1] + (4 * co,), device=dev, dtype=torch.bfloat16)
-                saved['only'].add(l + 1)                         # saved['a'][l + 1] stays unwritten
-                hl.bn_act_fwd(m, co, y, ss, hl.ACT_RELU, saved['split'][l + 1], split_out=True)
-            else:
-                hl.bn_act_fwd(m, co, y, ss, hl.ACT_RELU, a)
+            # the operand of layer l + 1's GEMMs ('f32x3': in the split form only when both its readers take that form)
+            geom = self._geom(l + 1, frames) if l < 4 else None
+            a, out, split_out = self._operand(torch.empty_like(y, dtype=torch.bfloat16 if a16 else torch.float32),
+                                              *((('dgrad', geom), ('wgrad', geom)) if l < 4 else ()))
+            hl.bn_act_fwd(m, co, y, ss, hl.ACT_RELU, out, split_out=split_out)
             saved['a'][l + 1] = a
             h = 4 << l
             pending = None
             if l < 4:
                 y = torch.empty((frames, h, h, self.chans[l + 1]), device=dev)
-                geom = self._geom(l + 1, frames)
                 w, b = self._w('dc%d/W' % (l + 1), self._s16(l + 1)), fp.param('dc%d/b' % (l + 1))
                 y16 = (OUT16 and self._s16(l + 1) and self.sync_bn is None and (fuse_stats or not train)
-                       and hl.dgrad_tile(geom, a, w, b) < 1000)                    # (as DisNet.forward_groups)
+                       and hl.dgrad_tile(geom, a.t, w, b) < 1000)                  # (as DisNet.forward_groups)
                 if y16:
                     y = torch.empty_like(y, dtype=torch.bfloat16)
                 if fuse_stats:
                     part = self._part_buf(geom, 'dgrad', 1)
                     ep = hl.epilogue(sums=hl.SUMS_STATS, groups=1, part=part, out_bf16=y16)
-                    if self._cdgrad(geom, a, 'dc%d/W' % (l + 1), w, b, y, ep=ep, ys=lambda: self._sp(saved['split'], l + 1, saved['a'][l + 1]),
-                                    force=l + 1 in saved['only']):
+                    if self._conv('dgrad', geom, a, 'dc%d/W' % (l + 1), w, b, y, ep=ep):
                         pending = (ep, part)
                 else:
-                    self._cdgrad(geom, a, 'dc%d/W' % (l + 1), w, b, y, ys=lambda: self._sp(saved['split'], l + 1, saved['a'][l + 1]),
-                                 force=l + 1 in saved['only'])
+                    self._conv('dgrad', geom, a, 'dc%d/W' % (l + 1), w, b, y)
         x = torch.empty((n, T, IMG, IMG, self.cp_out), device=dev)
         g5 = self._geom(5, frames, clip_order_n=n)
         if saved['a'][5].dtype == torch.bfloat16:
             g5 = hl.with_precision(g5, 'bf16y')
         if hl.dgrad_c4_mfma_covers(g5):
             # the last deconvolution (64 -> 3 channels) on the matrix pipe; bias + tanh (model/net.py:114) follow as an
-            # element-wise pass over the 4-channel clip (x = tanh(1 * x + b)), which the MFMA kernel cannot carry
-            if getattr(self, '_one_bias', None) is None or self._one_bias.device != dev:
-                self._one_bias = torch.ones(2 * self.cp_out, device=dev)
-            self._one_bias[self.cp_out:].copy_(fp.param('dc5/b'))
-            hl.conv_dgrad(g5, saved['a'][5], fp.param('dc5/W'), None, x)
-            hl.bn_act_fwd(x.numel() // self.cp_out, self.cp_out, x, self._one_bias, hl.ACT_TANH, x)
+            # element-wise pass over the 4-channel clip, which the MFMA kernel cannot carry
+            hl.conv_dgrad(g5, saved['a'][5].t, fp.param('dc5/W'), None, x)
+            self._bias_tanh(x)
         else:
-            hl.conv_dgrad(g5, saved['a'][5], fp.param('dc5/W'), fp.param('dc5/b'), x, act=hl.ACT_TANH)
+            hl.conv_dgrad(g5, saved['a'][5].t, fp.param('dc5/W'), fp.param('dc5/b'), x, act=hl.ACT_TANH)
         saved['x'] = x
         return x, saved
+
+    def _bias_tanh(self, x):
+        """x = tanh(1 * x + dc5/b) in place: bn_act_fwd with scale 1 and the bias as its shift"""
+        cp = self.cp_out
+        if self._one_bias is None:
+            self._one_bias = torch.ones(2 * cp, device=self.device)
+        self._one_bias[cp:].copy_(self.fp.param('dc5/b'))
+        hl.bn_act_fwd(x.numel() // cp, cp, x, self._one_bias, hl.ACT_TANH, x)
 
     # ---- sampling (test mode only) -------------------------------------------------------------
     # What a trained generator is for: chainer.config.train = False, forward only.  The fixed BatchNorm of the running averages is
@@ -1038,18 +1032,16 @@ class GenNet(_Net):
         updating the running averages without touching fp.version could leave stale)"""
         fp = self.fp
         lo, hi = fp.offsets['dc1/W'], fp.offsets['dc5/W']
-        f = self.__dict__.get('_fold')
-        if f is None:
-            f = self._fold = torch.empty(hi - lo, device=self.device)
-            self._fold16 = None
+        if self._fold is None:
+            self._fold = torch.empty(hi - lo, device=self.device)
         for l in (1, 2, 3, 4):
             bn = 'bn%d' % l
             hl.bn_fold_deconv(fp.param('dc%d/W' % l), fp.param('dc%d/b' % l), self.chans[l], fp.param(bn + '/gamma'), fp.param(bn + '/beta'),
                               self.running[bn + '/avg_mean'], self.running[bn + '/avg_var'], self._folded('dc%d/W' % l), self._folded('dc%d/b' % l))
         if self.precision == 'bf16':                                # the bf16 shadow of the folded filters (as FlatParams.refresh16)
             if self._fold16 is None:
-                self._fold16 = torch.empty_like(f, dtype=torch.bfloat16)
-            self._fold16.copy_(f)
+                self._fold16 = torch.empty_like(self._fold, dtype=torch.bfloat16)
+            self._fold16.copy_(self._fold)
 
     def _folded(self, name, stored16=False):
         o = self.fp.offsets[name] - self.fp.offsets['dc1/W']
@@ -1059,15 +1051,13 @@ class GenNet(_Net):
     def _folded_split(self, name):
         """'f32x3': the split form of a folded filter as the input-gradient GEMM reads it (planes of 16 filters)"""
         w = self._folded(name)
-        cache = self.__dict__.setdefault('_fold_splits', {})
-        out = cache.get(name)
-        cache[name] = out = hl.split_planes(w, run=16 * (w.numel() // w.shape[0]), out=out)
+        out = self._fold_splits[name] = hl.split_planes(w, run=16 * (w.numel() // w.shape[0]), out=self._fold_splits.get(name))
         return out
 
     def _sview(self, i, shape, dtype=torch.float32):
         """a tensor in ping-pong buffer i (0 / 1; 2: sample_many's byte output): held by the net, grown on demand, reused by every
         sample call"""
-        bufs = self.__dict__.setdefault('_sbuf', [None, None, None])
+        bufs = self._sbuf
         nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
         b = bufs[i]
         if b is None or b.numel() < nbytes:
@@ -1077,7 +1067,7 @@ class GenNet(_Net):
 
     def _unit_scale_shift(self, c):
         """[scale | shift] = (1, 0) for bn_act_fwd as a plain activation pass, built once by fills"""
-        u = self.__dict__.get('_unit_ss')
+        u = self._unit_ss
         if u is None or u.numel() != 2 * c:
             u = self._unit_ss = torch.empty(2 * c, device=self.device)
             u[:c].fill_(1.0)
@@ -1147,10 +1137,7 @@ class GenNet(_Net):
             if to_u8:
                 hl.clip_to_u8(lead[0], self.out_channels, self.cp_out, lead[1], hw, x, u8, bias=fp.param('dc5/b'), act=hl.ACT_TANH)
             else:
-                if getattr(self, '_one_bias', None) is None or self._one_bias.device != dev:
-                    self._one_bias = torch.ones(2 * self.cp_out, device=dev)
-                self._one_bias[self.cp_out:].copy_(fp.param('dc5/b'))
-                hl.bn_act_fwd(x.numel() // self.cp_out, self.cp_out, x, self._one_bias, hl.ACT_TANH, x)
+                self._bias_tanh(x)
         else:
             hl.conv_dgrad(g5, a, fp.param('dc5/W'), fp.param('dc5/b'), x, act=hl.ACT_TANH, tune=False)
             if to_u8:
@@ -1210,58 +1197,37 @@ class GenNet(_Net):
             ci = lay.pad4(self.chans[l])
             m = g.numel() // ci
             s16 = self._s16(l)
-            gy_split = None
             if l < 5:
-                name = 'bn%d' % l
                 gy = torch.empty_like(g, dtype=torch.bfloat16) if s16 else g      # bf16-stored operand of wgrad / fprop, else in place
-                if self._split_only(('wgrad', geom), ('fprop', geom)):            # 'f32x3': written in the split form only
-                    gy_split = torch.empty(g.shape[:-1] + (4 * ci,), device=g.device, dtype=torch.bfloat16)
-                go = gy_split if gy_split is not None else gy
-                if pending is not None:
-                    ep, part = pending
-                    hl.bn_act_bwd_from_partials(m, ci, g, saved['y'][l], saved['stats'][l], fp.param(name + '/gamma'), hl.ACT_RELU, part,
-                                                ep.n_slots, ep.slot_stride, go, fp.grad(name + '/gamma'), fp.grad(name + '/beta'), self.ws,
-                                                split_out=gy_split is not None)
-                else:
-                    hl.bn_act_bwd(m, ci, g, saved['y'][l], saved['stats'][l], fp.param(name + '/gamma'), hl.ACT_RELU, go,
-                                  fp.grad(name + '/gamma'), fp.grad(name + '/beta'), self.ws, sync=self.sync_bn, split_out=gy_split is not None)
-                g = gy
-            if l == 5:
+                # 'f32x3': written in the split form only when both GEMMs that read it take that form
+                go, out, split_out = self._operand(gy, ('wgrad', geom), ('fprop', geom))
+                self._bn_bwd('bn%d' % l, m, ci, g, saved['y'][l], saved['stats'][l], hl.ACT_RELU, pending, out, split_out=split_out)
+            else:
                 hl.colsum_acc(m, ci, g, fp.grad('dc5/b'), self.ws)         # dc1..dc4 feed BatchNorm: exact zero
-            gsp = {} if gy_split is None else {0: gy_split}      # 'f32x3': the split form of g, shared by the two GEMMs that read it
-
-            def gxs():
-                return self._sp(gsp, 0, g)
-            g_only = gy_split is not None                        # g exists in its split form only
+                go = Operand(g)
+            # go: the gradient w.r.t. dc<l>'s output as the two GEMMs that read it take it (they share its split form)
             a5_16 = l == 5 and saved['a'][5].dtype == torch.bfloat16      # (the 64-channel side of the last layer stored in bf16)
-            self._cwgrad(hl.with_precision(geom, 'bf16y') if a5_16 else geom, g, saved['a'][l], fp.grad('dc%d/W' % l), xs=gxs,
-                         ys=lambda: self._sp(saved.get('split'), l, saved['a'][l]), force=g_only or l in saved.get('only', ()))
+            self._cwgrad(hl.with_precision(geom, 'bf16y') if a5_16 else geom, go, saved['a'][l], fp.grad('dc%d/W' % l))
             if l == 2 and on_late_bucket is not None:
                 self._after_wgrads(on_late_bucket)
             wl = self._w('dc%d/W' % l, s16)
             g16 = (OUT16 and 2 < l < 5 and s16 and self.sync_bn is None                        # (layer 1's gradient feeds the fp32 fully-connected layer)
-                   and hl.fprop_tile(geom, g, wl, None) < 1000)                            # (as DisNet.backward)
+                   and hl.fprop_tile(geom, go.t, wl, None) < 1000)                         # (as DisNet.backward)
             g16 = g16 or (a5_16 and OUT16 and self.sync_bn is None)     # ... and its gradient likewise (BatchNorm's backward reads bf16)
-            ga = torch.empty_like(saved['a'][l], dtype=torch.bfloat16 if g16 else torch.float32)
+            ga = saved['a'][l].empty_like(torch.bfloat16 if g16 else torch.float32)
             pending = None
             if self._fuse_bwd_sums(s16, 'fprop', geom):     # ga is the gradient w.r.t. relu(bn_{l-1}(y_{l-1})): the sums of that BatchNorm's backward
                 part = self._part_buf(geom, 'fprop', 1)
                 ep = hl.epilogue(sums=hl.SUMS_BN_BWD, groups=1, part=part, bn_y=saved['y'][l - 1], bn_stats=[saved['stats'][l - 1]],
                                  bn_act=hl.ACT_RELU, out_bf16=g16)
-                if self._with_bwd_sums(lambda e: self._cfprop(geom, g, 'dc%d/W' % l, wl, None, ga, ep=e, xs=gxs, force=g_only), ep):
+                if self._with_bwd_sums(lambda e: self._conv('fprop', geom, go, 'dc%d/W' % l, wl, None, ga, ep=e), ep):
                     pending = (ep, part)
             else:
-                self._cfprop(geom, g, 'dc%d/W' % l, wl, None, ga, xs=gxs, force=g_only)
+                self._conv('fprop', geom, go, 'dc%d/W' % l, wl, None, ga)
             g = ga
         c1 = self.chans[1]
         k1 = 16 * c1
-        if pending is not None:
-            ep, part = pending
-            hl.bn_act_bwd_from_partials(frames * 16, c1, g, saved['y'][1], saved['stats'][1], fp.param('bn1/gamma'), hl.ACT_RELU, part,
-                                        ep.n_slots, ep.slot_stride, g, fp.grad('bn1/gamma'), fp.grad('bn1/beta'), self.ws)
-        else:
-            hl.bn_act_bwd(frames * 16, c1, g, saved['y'][1], saved['stats'][1], fp.param('bn1/gamma'), hl.ACT_RELU, g,
-                          fp.grad('bn1/gamma'), fp.grad('bn1/beta'), self.ws, sync=self.sync_bn)
+        self._bn_bwd('bn1', frames * 16, c1, g, saved['y'][1], saved['stats'][1], hl.ACT_RELU, pending, g)
         hl.fc_wgrad(frames, k1, self.n_hidden, g.view(frames, k1), saved['z'], fp.grad('dc1/W').view(self.n_hidden, k1))
         gz = torch.empty_like(saved['z'])
         hl.fc_fprop(frames, k1, self.n_hidden, g.view(frames, k1), fp.param('dc1/W').view(self.n_hidden, k1), None, gz)

@@ -10,15 +10,13 @@ The kernel schedule reproduces the reference's observable ordering:
 Gradients Chainer computes into the other networks and then discards (Q6) are not computed.
 """
 import math
+import os
 
 import torch
 
 from . import hiplib as hl
 from . import layout as lay
 from . import nets
-
-
-import os
 
 CHAINS = os.environ.get('MCG_CHAINS', '1') == '1'          # the VideoDiscriminator's real / fake calls as two chains on two streams (A/B switch)
 CHAINS_MIN_N = int(os.environ.get('MCG_CHAINS_MIN_N', '64'))  # ... from this many clips per call on (measured on one MI355X, clips/s with / without:
@@ -418,7 +416,7 @@ def pretune_and_share_tiles(exchange, model, precision, batch, rank, **model_kw)
     everyone's.  No reference counterpart (the reference is single-device, train.py:87-91)."""
     if exchange is None or not exchange.active:
         return
-    if hl._autotune:
+    if hl.autotune_on():
         model_kw.setdefault('num_labels', 6)
         gen, di, dv = make_models(model, seed=0, **model_kw)           # (same widths / channels as the run: same geometries)
         ts = TrainStep(model, gen, di, dv, seed=0, rank=rank, precision=precision)
@@ -429,6 +427,4 @@ def pretune_and_share_tiles(exchange, model, precision, batch, rank, **model_kw)
         del ts, gen, di, dv, x
     table = [[[list(k), v] for k, v in hl.tile_choices().items()]] if rank == 0 else [None]
     exchange.dist.broadcast_object_list(table, src=0, group=exchange.group)
-    hl._tile_cache.clear()
-    for k, v in table[0]:
-        hl._tile_cache[tuple(k)] = int(v)
+    hl.replace_tile_choices(table[0])

@@ -343,6 +343,29 @@ def test_split_form_predicates(monkeypatch):
     assert g3.precision == hl.PREC_SPLIT and g3.tile == 0 and wide.precision == hl.PREC_F32
 
 
+def test_operand_keeps_the_split_only_invariant():
+    """nets.Operand (host logic of the 'f32x3' networks, no launch): an operand written in the split form only never hands out its
+    unwritten plain tensor, and a row slice -- what DisNet.select_group does -- slices both forms and keeps the mark."""
+    import mocogan_chainer_amd.nets as nets
+    t = torch.arange(6 * 16, dtype=torch.float32).view(6, 16)
+    s = torch.arange(6 * 64, dtype=torch.float32).view(6, 64).to(torch.bfloat16)
+    only = nets.Operand(t, s, True)
+    with pytest.raises(AssertionError):
+        only.t
+    assert only.split() is s and only.dtype == torch.float32 and only.empty_like(torch.bfloat16).shape == t.shape
+    part = only[2:4]
+    assert part.split_only and torch.equal(part.split(), s[2:4]) and part.split().data_ptr() == s[2:4].data_ptr()
+    with pytest.raises(AssertionError):
+        part.t
+    assert part.empty_like(torch.float32).shape == (2, 16)
+    both = nets.Operand(t, s)[4:]                               # both forms written: both sliced, both readable
+    assert not both.split_only and torch.equal(both.t, t[4:]) and torch.equal(both.split(), s[4:])
+    plain = nets.Operand(t)[:3]                                 # no split form yet: none appears by slicing
+    assert plain._s is None and torch.equal(plain.t, t[:3])
+    with pytest.raises(AssertionError):
+        nets.Operand(t, None, True)                             # split-only needs the split form
+
+
 def test_prefetch_iterator_resumes_from_a_restored_position():
     """load_state must drop the look-ahead queued from the old position; a resumed PrefetchIterator has to
     show what a SerialIterator restored to the same state shows (reference: --resume, train.py:162-163)."""

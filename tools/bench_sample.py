@@ -135,7 +135,7 @@ def main():
                     'bytes_differing_share': float((d != 0).mean()), 'bytes_max_abs_diff': int(d.max())}
             print(json.dumps(line), flush=True)
             lines.append(line)
-            gen.impl.__dict__.pop('_sbuf', None)
+            gen.impl._sbuf = [None, None, None]
             torch.cuda.empty_cache()
     if args.out:
         with open(args.out, 'w') as f:
