@@ -66,7 +66,7 @@ enum { MCG_PREC_F32 = 0, MCG_PREC_BF16 = 1,
         * mcg_split_planes writes: along the channel dimension that the GEMM sums over (Ci of x and w for fprop, Co of y and
         * w for dgrad) groups of 16 channels x 4 planes (hi, mid, lo, padding) of bf16, i.e. 4 * C uint16_t per pixel / filter row
         * (for dgrad's w: 16 filters x 4 planes, see mcg_split_planes).
-        * Outputs stay fp32.  LDS-DMA kernels only (tile 0, 7 or 8); channel counts along the sum powers of two >= 16. */
+        * Outputs stay fp32.  LDS-DMA kernels only (tile 0, 7, 8 or 10, and 9 in dgrad); channel counts along the sum powers of two >= 16. */
        MCG_PREC_SPLIT = 3,
        /* as MCG_PREC_BF16, with the y-side tensor bf16 IN MEMORY while x and w stay fp32: the clip-side layers of bf16 networks
         * (Ci = 4: D's first layer, G's last), whose 64-channel neighbour tensor -- dc1's output gradient, G's last activation -- is

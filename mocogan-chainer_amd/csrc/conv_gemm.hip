@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 #include "mocogan_hip.h"
 #include "mcg_common.h"
@@ -2506,62 +2505,6 @@ __global__ __launch_bounds__(NTHREADS) void dgrad_c4_kernel(Geom g, const float*
     }
 }
 
-// the weight-stationary Ci = 4 forward kernel: geometry it covers (and the only epilogues it carries)
-bool c4_fprop_ok(const Geom& g, const Epi& e) {
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    return g.Ci == 4 && g.Co == 64 && (g.Wo == 32 || g.Wo == 16) && g.Ho % (256 / g.Wo) == 0 && !g.perm_n && g.xs0 == frame &&
-           g.prec != MCG_PREC_BF16_STORE && (e.mode == 0 || e.mode == EPI_ACT) &&        // (this layer's tensors are fp32 in memory)
-           (!e.out16 || e.mode == EPI_ACT || (e.mode == 0 && g.prec == MCG_PREC_BF16));      // (a plain bf16 output: G's dc5 read backwards)
-}
-
-template <int KT, int WO>
-int launch_fprop_c4(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, hipStream_t s) {
-    C4FpropP p;
-    p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
-    p.M = g.N * g.To * g.Ho * g.Wo;
-    constexpr int R = 256 / WO, K = KT * 64;
-    const size_t lds = (size_t)64 * (K + 4) * 4 + (size_t)KT * (2 * R + 2) * 2 * (WO + 2) * 16 + 4096;
-    static std::once_flag once[4];                        // > 64 KiB of dynamic LDS needs the opt-in once per kernel and process
-    hipError_t attr = hipSuccess;
-    const dim3 grid(g.N * (g.Ho / R));
-#define MCG_C4_LAUNCH(EPI_, CV_, SLOT_) do { \
-        std::call_once(once[SLOT_], [&] { attr = hipFuncSetAttribute((const void*)fprop_c4_kernel<KT, WO, EPI_, CV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
-        if (attr != hipSuccess) return MCG_ERR_LAUNCH; \
-        hipLaunchKernelGGL((fprop_c4_kernel<KT, WO, EPI_, CV_>), grid, dim3(512), lds, s, p); } while (0)
-    if (e.mode & EPI_ACT) { if (g.cv <= 3) MCG_C4_LAUNCH(3, 3, 0); else MCG_C4_LAUNCH(3, 4, 1); }
-    else { if (g.cv <= 3) MCG_C4_LAUNCH(1, 3, 2); else MCG_C4_LAUNCH(1, 4, 3); }
-#undef MCG_C4_LAUNCH
-    return MCG_OK;
-}
-
-// the MFMA col2im input-gradient kernel of the Ci = 4 layers: what it covers
-bool c4_dgrad_mfma_ok(const Geom& g, const Epi& e, const float* bias, int act, int accumulate) {
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    // x must be ONE dense buffer of N frames (it is cleared as a whole): plain batch order, or the generator's
-    // (T,N) -> (N,T) frame permutation, which maps the N frames one-to-one onto it
-    const bool whole = g.perm_n ? (g.xs1 == frame && g.xs0 == (long long)(g.N / g.perm_n) * frame) : g.xs0 == frame;
-    return g.Ci == 4 && g.cv <= 3 && g.Co == 64 && (g.Wo == 32 || g.Wo == 16) && g.Ho % (128 / g.Wo) == 0 && whole &&
-           !e.mode && !e.out16 && !bias && act == MCG_ACT_NONE && !accumulate;
-}
-
-constexpr int C4_DGRAD_MAX_BLOCKS = 1024;      // blocks of the persistent first-layer input-gradient kernel (4 per CU; each walks tiles)
-template <int KT, int WO, bool BF, bool Y16 = false>
-int launch_dgrad_c4_mfma(const Geom& g, const float* y, const float* w, float* x, hipStream_t s) {
-    C4DgradP p;
-    p.g = g; p.y = y; p.w = w; p.x = x;
-    constexpr int R = 128 / WO, NPX = (2 * R + 2) * 2 * WO, LD = BF ? 40 : 68;
-    const size_t lds = (size_t)(128 * LD + KT * 48 * LD + ((BF && KT > 1) ? 2 : 1) * 128 * 52) * 4 + (size_t)KT * NPX * 16;
-    static std::once_flag once;
-    hipError_t attr = hipSuccess;
-    std::call_once(once, [&] { attr = hipFuncSetAttribute((const void*)dgrad_c4_mfma_kernel<KT, WO, BF, Y16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-    // the rows two neighbouring blocks share are ADDED (two addends, order-independent): x starts from zero
-    if (hipMemsetAsync(x, 0, (size_t)g.N * g.Ti * g.Hi * g.Wi * 4 * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;
-    const int ntiles = g.N * (g.Ho / R);
-    hipLaunchKernelGGL((dgrad_c4_mfma_kernel<KT, WO, BF, Y16>), dim3(ntiles < C4_DGRAD_MAX_BLOCKS ? ntiles : C4_DGRAD_MAX_BLOCKS), dim3(512), lds, s, p);
-    return MCG_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // wgrad for Ci == 4 (<= 3 data channels), Co == 64: dw[co][a][kh][kw][ci] += sum_pix y[pix][co] * x[pix @ tap][ci].
 // In the generic kernel this layer is a 64 x 256 output with a K of millions of pixels whose B operand is a 16-byte
@@ -2927,87 +2870,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void wg
     }
 }
 
-bool c4_wgrad_bf16_ok(const Geom& g) {
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    return g.Ci == 4 && g.cv <= 3 && g.Co == 64 && (g.Wo == 32 || g.Wo == 16) && g.Ho % (256 / g.Wo) == 0 && !g.perm_n &&
-           g.xs0 == frame && g.prec == MCG_PREC_BF16 && g.y16;          // (Ho a multiple of the 256-pixel step's rows, hence of the 128-pixel step's)
-}
+// ==========================================================================================
+// Host layer: mcg_conv_geom -> kernel instantiation, grid, dynamic LDS size and K split.  Each decision is made once:
+// extents(), plan_ksplit() / plan_pixsplit(), dgrad_ksplit(), launch<>(), with_epi<>(), with_kt_wo(), and per pass one block
+// that picks the kernel family and tile shape (the table above conv_fprop_impl).
+// ==========================================================================================
 
-template <int KT, int WO>
-int launch_wgrad_c4_bf16(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
-    // 3-D layers with enough rows: 128-pixel steps, 256 threads, two blocks per CU; otherwise 256-pixel steps, one block per CU
-    constexpr bool SMALL = KT == 4;
-    constexpr int BM = SMALL ? 128 : 256, NT = SMALL ? 256 : 512;
-    C4WgradP p;
-    p.g = g; p.x = x; p.y = y; p.dw = dw;
-    constexpr int R = BM / WO;
-    const size_t lds = (size_t)(KT + 1) * (2 * R + 2) * (2 * WO + 4) * 8 + 2 * BM * WC4_YS;
-    static std::once_flag once;
-    hipError_t attr = hipSuccess;
-    std::call_once(once, [&] { attr = hipFuncSetAttribute((const void*)wgrad_c4_bf16_kernel<KT, WO, NT, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-    // (row block, batch item) pairs over ~2 rounds of blocks; with fewer the frames of an item are split (as launch_wgrad_c4)
-    // 512 blocks: ONE round of the 3-D form at two per CU (every block ends in 64 x kt * 48 float atomics onto the same dw: measured
-    // at 512 clips 0.458-0.472 ms with 1024 blocks, 0.397-0.406 with 512, 0.412-0.420 with 256)
-    constexpr int WC4_TARGET = 512;
-    const int hblocks = g.Ho / R, target = WC4_TARGET;
-    p.nsplit = g.N; p.tsplit = 1;
-    if (hblocks * p.nsplit > target) p.nsplit = target / hblocks > 0 ? target / hblocks : 1;
-    while (hblocks * p.nsplit * p.tsplit < target / 2 && 2 * p.tsplit * 2 <= g.To) p.tsplit *= 2;
-    hipLaunchKernelGGL((wgrad_c4_bf16_kernel<KT, WO, NT, BM>), dim3(hblocks * p.nsplit * p.tsplit), dim3(NT), lds, s, p);
-    return MCG_OK;
-}
-
-bool c4_wgrad_ok(const Geom& g) {
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    return g.Ci == 4 && g.cv <= 3 && g.Co == 64 && (g.Wo == 32 || g.Wo == 16) && g.Ho % (256 / g.Wo) == 0 && !g.perm_n &&
-           g.xs0 == frame && g.prec == MCG_PREC_F32;
-}
-
-template <int KT, int WO>
-int launch_wgrad_c4(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
-    C4WgradP p;
-    p.g = g; p.x = x; p.y = y; p.dw = dw;
-    constexpr int R = 256 / WO;
-    const size_t lds = (size_t)(KT + 1) * (2 * R + 2) * 2 * (WO + 2) * 16;
-    static std::once_flag once;
-    hipError_t attr = hipSuccess;
-    std::call_once(once, [&] { attr = hipFuncSetAttribute((const void*)wgrad_c4_kernel<KT, WO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-    // one block per CU: (row block, batch item) pairs; with fewer than 256 of them the frames of an item are split as well
-    // (each part re-reads kt - 1 frames), with more a block walks several items (every block ends in 64 x kt * 48 atomics)
-    const int hblocks = g.Ho / R;
-    p.nsplit = g.N; p.tsplit = 1;
-    if (hblocks * p.nsplit > 512) p.nsplit = 512 / hblocks > 0 ? 512 / hblocks : 1;
-    while (hblocks * p.nsplit * p.tsplit < 256 && 2 * p.tsplit * 2 <= g.To) p.tsplit *= 2;        // >= 2 steps per part
-    hipLaunchKernelGGL((wgrad_c4_kernel<KT, WO>), dim3(hblocks * p.nsplit * p.tsplit), dim3(512), lds, s, p);
-    return MCG_OK;
-}
-
-template <int KT, int WO>
-int launch_fprop_c4_bf16(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, hipStream_t s) {
-    C4FpropP p;
-    p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
-    p.M = g.N * g.To * g.Ho * g.Wo;
-    constexpr int R = 256 / WO, K = KT * 64;
-    const size_t lds = (size_t)64 * (K + 8) * 2 + (size_t)KT * (2 * R + 2) * (2 * WO + 4) * 8 + 4096;
-    static std::once_flag once[2];
-    hipError_t attr = hipSuccess;
-    const dim3 grid(g.N * (g.Ho / R));
-    if (e.mode & EPI_ACT) {
-        std::call_once(once[0], [&] { attr = hipFuncSetAttribute((const void*)fprop_c4_bf16_kernel<KT, WO, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-        if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-        hipLaunchKernelGGL((fprop_c4_bf16_kernel<KT, WO, 3>), grid, dim3(512), lds, s, p);
-    } else {
-        std::call_once(once[1], [&] { attr = hipFuncSetAttribute((const void*)fprop_c4_bf16_kernel<KT, WO, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-        if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-        hipLaunchKernelGGL((fprop_c4_bf16_kernel<KT, WO, 1>), grid, dim3(512), lds, s, p);
-    }
-    return MCG_OK;
-}
-
-// which fused-epilogue instantiation serves this combination of options (make_epi rejects the others)
-int epi_class(int mode) { return (mode & EPI_ACT) ? 3 : (mode & EPI_BNBWD) ? 2 : 1; }
+template <int V> using ic = std::integral_constant<int, V>;
 
 int ilog2_exact(int v) {
     if (v <= 0 || (v & (v - 1))) return -1;
@@ -3015,6 +2884,20 @@ int ilog2_exact(int v) {
     while ((1 << l) < v) ++l;
     return l;
 }
+
+long long frame_elems(const Geom& g) { return (long long)g.Ti * g.Hi * g.Wi * g.Ci; }
+// x is ONE buffer of N frames in batch order
+bool dense_x(const Geom& g) { return !g.perm_n && g.xs0 == frame_elems(g); }
+
+// Element counts of the three tensors (x: up to the end of its last batch item, whatever the strides).  Loader offsets are
+// 32-bit byte offsets checked by the buffer hardware against the tensor extent; 2 GiB and above is the "out of range" marker,
+// so each tensor must stay below 2 GiB at the element size of its operand form.
+struct Extents { long long x, y, w; };
+Extents extents(const Geom& g) {
+    const long long last = g.perm_n ? (long long)(g.perm_n - 1) * g.xs0 + (long long)(g.N / g.perm_n - 1) * g.xs1 : (long long)(g.N - 1) * g.xs0;
+    return {last + frame_elems(g), (long long)g.N * g.To * g.Ho * g.Wo * g.Co, (long long)g.Co * g.taps * g.Ci};
+}
+bool fits(long long elems, int esz) { return elems * esz < (1ll << 31); }
 
 int make_geom(const mcg_conv_geom* c, Geom& g) {
     if (!c) return MCG_ERR_BAD_ARG;
@@ -3039,289 +2922,325 @@ int make_geom(const mcg_conv_geom* c, Geom& g) {
     if (g.kt != 1 && g.kt != 4) return MCG_ERR_UNSUPPORTED;
     if (g.Hi != 2 * g.Ho || g.Wi != 2 * g.Wo || g.To != g.Ti - g.kt + 1 || g.To <= 0) return MCG_ERR_UNSUPPORTED;
     if (g.perm_n < 0 || (g.perm_n && g.N % g.perm_n) || g.xs0 < 0 || g.xs1 < 0) return MCG_ERR_BAD_ARG;
-    // Loader offsets are 32-bit byte offsets checked by the buffer hardware against the tensor extent;
-    // 2 GiB and above is the "out of range" marker, so each tensor must stay below 2 GiB.
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    const long long x_elems = (g.perm_n ? (long long)(g.perm_n - 1) * g.xs0 + (long long)(g.N / g.perm_n - 1) * g.xs1
-                                        : (long long)(g.N - 1) * g.xs0) + frame;
-    const long long y_elems = (long long)g.N * g.To * g.Ho * g.Wo * g.Co;
-    const long long w_elems = (long long)g.Co * g.taps * g.Ci;
-    if (x_elems * 4 >= (1ll << 31) || y_elems * 4 >= (1ll << 31) || w_elems * 4 >= (1ll << 31)) return MCG_ERR_UNSUPPORTED;
+    const Extents n = extents(g);
+    if (!fits(n.x, 4) || !fits(n.y, 4) || !fits(n.w, 4)) return MCG_ERR_UNSUPPORTED;
     // (buffer extents of the INPUT operands of a pass: 2-byte elements when they are bf16 in memory)
     const int esz = g.prec == MCG_PREC_BF16_STORE ? 2 : 4;
     if (esz == 2 && ((g.Ci & 7) || (g.Co & 7))) return MCG_ERR_UNSUPPORTED;       // a 16-byte slot = 8 channels
     if (g.y16 && (g.Co & 7)) return MCG_ERR_UNSUPPORTED;
-    g.x_bytes = (u32)(x_elems * esz); g.y_bytes = (u32)(y_elems * (g.y16 ? 2 : esz)); g.w_bytes = (u32)(w_elems * esz);
+    g.x_bytes = (u32)(n.x * esz); g.y_bytes = (u32)(n.y * (g.y16 ? 2 : esz)); g.w_bytes = (u32)(n.w * esz);
     g.magic_To = (u32)((1ull << 32) / (unsigned)g.To) + 1u;
     g.magic_N = (u32)((1ull << 32) / (unsigned)g.N) + 1u;
     return MCG_OK;
 }
 
-int launch_status() { return hipGetLastError() == hipSuccess ? MCG_OK : MCG_ERR_LAUNCH; }
+// MCG_PREC_SPLIT: the launch is that of a bf16-stored layer whose summed dimension holds 4 planes of bf16 (8 bytes) per fp32
+// value, and the kernel's SPLIT flag turns a K-step into the six products.  Along the channels (fprop: Ci, dgrad: Co) that is a
+// layer with FOUR TIMES the channels, 16 channels x 4 planes per group (mcg_split_planes); along the pixels (wgrad: 16 pixels x
+// 4 planes per K-step) the geometry keeps its shape and only the extents of x and y grow.
+enum SplitDim { SPLIT_CI, SPLIT_CO, SPLIT_PIX };
+bool split_ok(const Geom& g, SplitDim d) {
+    const Extents n = extents(g);
+    if (d == SPLIT_PIX) return fits(n.x, 8) && fits(n.y, 8) && (n.y / g.Co) % 16 == 0;
+    const int c = d == SPLIT_CI ? g.Ci : g.Co;
+    return c >= 16 && (c & (c - 1)) == 0 && fits(d == SPLIT_CI ? n.x : n.y, 8) && fits(n.w, 8);
+}
+Geom split_geom(const Geom& g, SplitDim d) {
+    const Extents n = extents(g);
+    Geom h = g;
+    h.prec = MCG_PREC_BF16_STORE;
+    if (d == SPLIT_PIX) { h.x_bytes = (u32)(n.x * 8); h.y_bytes = (u32)(n.y * 8); return h; }
+    h.split = 1;       // every fourth 16-channel plane of K is zero: its loader slots stay out of range
+    if (d == SPLIT_CI) { h.Ci = 4 * g.Ci; h.lgCi = g.lgCi + 2; h.cv = h.Ci; h.xs0 = 4 * g.xs0; h.xs1 = 4 * g.xs1; h.x_bytes = (u32)(n.x * 8); }
+    else { h.Co = 4 * g.Co; h.lgCo = g.lgCo + 2; h.y_bytes = (u32)(n.y * 8); }
+    h.w_bytes = (u32)(n.w * 8);
+    return h;
+}
 
+// ---- split plans (pure functions of integers) ----
+// K-split plan: a sum of `len` terms taken in steps of `step` over `want` blocks, each keeping >= min_steps steps.
+// n blocks take `chunk` terms each (a multiple of step; the last one what is left).
+struct Split { int n, chunk; };
+Split plan_ksplit(int len, int step, int want, int min_steps) {
+    const int steps = (len + step - 1) / step;
+    int n = want < steps / min_steps ? want : steps / min_steps;
+    if (n < 1) n = 1;
+    const int chunk = ((steps + n - 1) / n) * step;
+    return {(len + chunk - 1) / chunk, chunk};
+}
+// Pixel-split plan of a weight gradient: as many splits as bring its `tiles` output tiles to `target` blocks.
+Split plan_pixsplit(int pixels, int step, int target, int tiles, int min_steps) {
+    return plan_ksplit(pixels, step, (target + tiles - 1) / tiles, min_steps);
+}
+// mcg_conv_geom.tile + 1000 / + 2000 doubles / halves a weight gradient's block target
+int wgrad_target(const Geom& g, int base) { return g.ksplit == 2 ? 2 * base : (g.ksplit == 4 ? base / 2 : base); }
+
+// Split K of fprop / dgrad: partial tiles are ADDED onto the fp32 output with atomics, so a fused epilogue or a bf16 store
+// (which need whole output elements) take one block per tile ...
+int fprop_ksplit(const Geom& g, const Epi& e) { return (e.mode || e.out16) ? 1 : g.ksplit; }
+// ... and so does an input gradient with an activation behind the sum, or whose x is neither accumulated into nor one dense
+// buffer (which plan_dgrad() then zeroes as a whole); the rule for every input-gradient kernel that splits K
+int dgrad_ksplit(const Geom& g, int act, int acc, const Epi& e) {
+    return (act == MCG_ACT_NONE && (acc || dense_x(g)) && !e.mode && !e.out16) ? g.ksplit : 1;
+}
+int clear_output(float* out, long long elems, hipStream_t s) {
+    return hipMemsetAsync(out, 0, (size_t)elems * sizeof(float), s) == hipSuccess ? MCG_OK : MCG_ERR_LAUNCH;
+}
+
+// ---- the launch ----
+// Dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised once per kernel instantiation and process (above 64 KiB;
+// asked for whenever a kernel takes any).  The outcome is kept: after a failure every launch of that kernel reports it.
+template <auto KERNEL> int lds_opt_in(size_t lds) {
+    static const hipError_t st = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return st == hipSuccess ? MCG_OK : MCG_ERR_LAUNCH;
+}
+template <auto KERNEL, class... A> int launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    if (lds && lds_opt_in<KERNEL>(lds) != MCG_OK) return MCG_ERR_LAUNCH;
+    KERNEL<<<grid, block, lds, s>>>(args...);
+    return hipGetLastError() == hipSuccess ? MCG_OK : MCG_ERR_LAUNCH;
+}
+
+// Run-time epilogue class -> compile-time EPI of fused_epilogue: 0 plain store, 1 column sums (+ mask multiply), 2 BatchNorm's
+// backward sums, 3 activation + noise (make_epi admits one class per launch).  MAXC is the highest class the kernel family is
+// instantiated with; anything above is refused here, before the launcher clears an output or writes to mcg_conv_epilogue.
+template <int MAXC, class F> int with_epi(const Epi& e, F&& f) {
+    const int cls = !e.mode ? 0 : (e.mode & EPI_ACT) ? 3 : (e.mode & EPI_BNBWD) ? 2 : 1;
+    if (cls > MAXC) return MCG_ERR_UNSUPPORTED;
+    if constexpr (MAXC >= 3) if (cls == 3) return f(ic<3>{});
+    if constexpr (MAXC >= 2) if (cls == 2) return f(ic<2>{});
+    return cls == 1 ? f(ic<1>{}) : f(ic<0>{});
+}
+
+// The kernels written for the Ci = 4 layers are instantiated for kt in {1, 4} (make_geom) x Wo in {16, 32} (c4_layer)
+template <class F> int with_kt_wo(const Geom& g, F&& f) {
+    if (g.kt == 4) return g.Wo == 32 ? f(ic<4>{}, ic<32>{}) : f(ic<4>{}, ic<16>{});
+    return g.Wo == 32 ? f(ic<1>{}, ic<32>{}) : f(ic<1>{}, ic<16>{});
+}
+
+// ---- register-staged kernels (gemm_kernel / gemm_bf16_kernel; tile codes 1-5) ----
 // PM (precision mode of a launch): 0 = fp32 MFMA; 1 = bf16 MFMA, operands fp32 in memory (rounded in the kernel);
-// 2 = bf16 MFMA, operands bf16 in memory (MCG_PREC_BF16_STORE).  The fused-epilogue classes 2 / 3 exist for PM 0 / 1.
-template <int BM, int BN, int BK, int PM = 0>
-int launch_fprop(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
-    using Pol = FpropP<BM, BN, BK, PM == 2 ? 8 : 4, PM != 0>;
-    Pol p;
+// 2 = bf16 MFMA, operands bf16 in memory (MCG_PREC_BF16_STORE); 3 (wgrad) = 1 with y bf16 in memory.
+// LDS-DMA kernels (gemm_bf16_v2_kernel; tile codes 7, 8, 10): PM 0 or 2, and SPLIT for MCG_PREC_SPLIT operands.
+
+// Fills a forward policy of either family and plans its launch: grid = (row tiles, column tiles, K splits)
+template <int BM, int BN, class Pol>
+int plan_fprop(Pol& p, dim3& grid, const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, mcg_conv_epilogue* ep,
+               int step, int min_steps, hipStream_t s) {
     p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
     p.M = g.N * g.To * g.Ho * g.Wo; p.K = g.taps * g.Ci;
+    const Split k = plan_ksplit(p.K, step, fprop_ksplit(g, e), min_steps);
+    p.kchunk = k.chunk;
+    if (k.n > 1 && clear_output(y, (long long)p.M * g.Co, s) != MCG_OK) return MCG_ERR_LAUNCH;
     if (ep) { ep->n_slots = (p.M + BM - 1) / BM; ep->slot_stride = e.slot_stride; }
-    int splits = e.mode ? 1 : g.ksplit;                         // a fused epilogue needs whole output elements
-    const int ksteps = (p.K + BK - 1) / BK;
-    if (splits > ksteps / 8) splits = ksteps / 8;               // keep >= 8 K-steps per block
-    if (splits < 1) splits = 1;
-    p.kchunk = ((ksteps + splits - 1) / splits) * BK;
-    splits = (p.K + p.kchunk - 1) / p.kchunk;
-    if (splits == 1) p.kchunk = p.K > 0 ? ((p.K + BK - 1) / BK) * BK : BK;
-    else if (hipMemsetAsync(y, 0, (size_t)p.M * g.Co * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;   // the atomics need a cleared y
-    dim3 grid((p.M + BM - 1) / BM, (g.Co + BN - 1) / BN, splits);
-    const int cls = e.mode ? epi_class(e.mode) : 0;
-    if (PM == 2 && cls > 1) return MCG_ERR_UNSUPPORTED;
-    if (cls == 2 && (e.out16 || e.bn_y16)) return MCG_ERR_UNSUPPORTED;     // (bf16 tensors around BatchNorm's backward sums: the LDS-DMA kernels)
-    if constexpr (PM == 0) {
-        if (cls == 0) hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 0>), grid, dim3(NTHREADS), 0, s, p);
-        else if (cls == 1) hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 1>), grid, dim3(NTHREADS), 0, s, p);
-        else if (cls == 2) hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 2>), grid, dim3(NTHREADS), 0, s, p);
-        else hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 3>), grid, dim3(NTHREADS), 0, s, p);
-    } else {
-        if (cls == 0) hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 0>), grid, dim3(NTHREADS), 0, s, p);
-        else if (cls == 1) hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 1>), grid, dim3(NTHREADS), 0, s, p);
-        else if constexpr (PM == 1) {
-            if (cls == 2) hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 2>), grid, dim3(NTHREADS), 0, s, p);
-            else hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 3>), grid, dim3(NTHREADS), 0, s, p);
-        }
-    }
+    grid = dim3((p.M + BM - 1) / BM, (g.Co + BN - 1) / BN, k.n);
     return MCG_OK;
 }
-
-template <int BM, int BN, int BK, int PM = 0>
-int launch_dgrad(const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
-    using Pol = DgradP<BM, BN, BK, PM == 2 ? 8 : 4, PM != 0>;
-    Pol p;
+// ... an input-gradient policy: grid = 8-tile groups x 4 output-parity classes x K splits
+template <int BM, int BN, class Pol>
+int plan_dgrad(Pol& p, dim3& grid, const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e,
+               mcg_conv_epilogue* ep, int step, int min_steps, hipStream_t s) {
     p.g = g; p.e = e; p.y = y; p.w = w; p.bias = bias; p.x = x; p.act = act; p.accumulate = acc;
     p.M = g.N * g.Ti * g.Ho * g.Wo; p.K = g.kt * 4 * g.Co;
-    if (ep) { ep->n_slots = 4 * ((p.M + BM - 1) / BM); ep->slot_stride = e.slot_stride; }
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    const bool dense_x = !g.perm_n && g.xs0 == frame;
-    int splits = (act == MCG_ACT_NONE && (acc || dense_x) && !e.mode) ? g.ksplit : 1;
-    const int ksteps = (p.K + BK - 1) / BK;
-    if (splits > ksteps / 8) splits = ksteps / 8;
-    if (splits < 1) splits = 1;
-    p.kchunk = ((ksteps + splits - 1) / splits) * BK;
-    splits = (p.K + p.kchunk - 1) / p.kchunk;
-    if (splits > 1 && !acc && hipMemsetAsync(x, 0, (size_t)g.N * frame * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;
+    const Split k = plan_ksplit(p.K, step, dgrad_ksplit(g, act, acc, e), min_steps);
+    p.kchunk = k.chunk;
+    if (k.n > 1 && !acc && clear_output(x, g.N * frame_elems(g), s) != MCG_OK) return MCG_ERR_LAUNCH;
     p.gxm = (p.M + BM - 1) / BM; p.gyn = (g.Ci + BN - 1) / BN; p.tiles8 = (p.gxm * p.gyn + 7) / 8;
-    dim3 grid(8 * p.tiles8 * 4 * splits, 1, 1);
-    const int cls = e.mode ? epi_class(e.mode) : 0;                      // (class 3 is fprop only: make_epi)
-    if (PM == 2 && cls > 1) return MCG_ERR_UNSUPPORTED;
-    if (cls == 2 && (e.out16 || e.bn_y16)) return MCG_ERR_UNSUPPORTED;
-    if constexpr (PM == 0) {
-        if (cls == 0) hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 0>), grid, dim3(NTHREADS), 0, s, p);
-        else if (cls == 1) hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 1>), grid, dim3(NTHREADS), 0, s, p);
-        else hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 2>), grid, dim3(NTHREADS), 0, s, p);
-    } else {
-        if (cls == 0) hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 0>), grid, dim3(NTHREADS), 0, s, p);
-        else if (cls == 1) hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 1>), grid, dim3(NTHREADS), 0, s, p);
-        else if constexpr (PM == 1) hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 2>), grid, dim3(NTHREADS), 0, s, p);
-    }
+    if (ep) { ep->n_slots = 4 * p.gxm; ep->slot_stride = e.slot_stride; }
+    grid = dim3(8 * p.tiles8 * 4 * k.n, 1, 1);
     return MCG_OK;
 }
-
-template <int BM, int BN, int BK, int PM = 0>
-int launch_wgrad(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
-    using Pol = WgradP<BM, BN, BK, PM == 2 ? 8 : 4, NTHREADS, false, false, (PM == 2 || PM == 3) ? 8 : 4>;     // PM 3: y bf16 in memory, x fp32
-    Pol p;
+// ... a weight-gradient policy: grid = (filter tiles, tap-channel tiles, pixel splits), `step` pixels per K-step
+template <int BM, int BN, class Pol>
+void plan_wgrad(Pol& p, dim3& grid, const Geom& g, const float* x, const float* y, float* dw, int step, int target, int min_steps) {
     p.g = g; p.x = x; p.y = y; p.dw = dw;
     p.Mpix = g.N * g.To * g.Ho * g.Wo; p.Kf = g.taps * g.Ci;
-    int tiles = ((g.Co + BM - 1) / BM) * ((p.Kf + BN - 1) / BN);
-    int ksteps = (p.Mpix + BK - 1) / BK;
-    // aim at ~4 blocks per CU; mcg_conv_geom.tile + 1000 / + 2000 doubles / halves that target
-    const int target = g.ksplit == 2 ? 2048 : (g.ksplit == 4 ? 512 : 1024);
-    int splits = (target + tiles - 1) / tiles;
-    if (splits > ksteps / 4) splits = ksteps / 4;        // keep >= 4 K-steps per block
-    if (splits < 1) splits = 1;
-    int steps_per = (ksteps + splits - 1) / splits;
-    p.chunk = steps_per * BK;
-    splits = (p.Mpix + p.chunk - 1) / p.chunk;
-    dim3 grid((g.Co + BM - 1) / BM, (p.Kf + BN - 1) / BN, splits);
-    if constexpr (PM == 0) hipLaunchKernelGGL((gemm_kernel<Pol, BM, BN, BK, 0>), grid, dim3(NTHREADS), 0, s, p);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<Pol, BM, BN, BK, 0>), grid, dim3(NTHREADS), 0, s, p);
-    return MCG_OK;
+    const int gx = (g.Co + BM - 1) / BM, gy = (p.Kf + BN - 1) / BN;
+    const Split k = plan_pixsplit(p.Mpix, step, wgrad_target(g, target), gx * gy, min_steps);
+    p.chunk = k.chunk;
+    grid = dim3(gx, gy, k.n);
 }
 
-// ---- launches of gemm_bf16_v2_kernel (tile codes 7 = 256x128, three-buffer ring; 8 = 256x256, two buffers) ----
-// what the LDS-DMA kernels cover: bf16-stored operands, every K-step inside one filter tap
+
+// register-staged: K-steps of BK, >= 8 per block; the fused-epilogue classes 2 / 3 exist for PM 0 / 1 (class 3: fprop) and
+// class 2 reads and writes fp32 (bf16 tensors around BatchNorm's backward sums: the LDS-DMA kernels)
+template <int BM, int BN, int BK, int PM>
+int launch_fprop(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
+    using Pol = FpropP<BM, BN, BK, PM == 2 ? 8 : 4, PM != 0>;
+    if ((e.mode & EPI_BNBWD) && (e.out16 || e.bn_y16)) return MCG_ERR_UNSUPPORTED;
+    return with_epi<PM == 2 ? 1 : 3>(e, [&](auto epi) -> int {
+        Pol p; dim3 grid;
+        if (int st = plan_fprop<BM, BN>(p, grid, g, x, w, bias, y, e, ep, BK, 8, s)) return st;
+        if constexpr (PM == 0) return launch<gemm_kernel<Pol, BM, BN, BK, epi>>(grid, dim3(NTHREADS), 0, s, p);
+        else return launch<gemm_bf16_kernel<Pol, BM, BN, BK, epi>>(grid, dim3(NTHREADS), 0, s, p);
+    });
+}
+template <int BM, int BN, int BK, int PM>
+int launch_dgrad(const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
+    using Pol = DgradP<BM, BN, BK, PM == 2 ? 8 : 4, PM != 0>;
+    if ((e.mode & EPI_BNBWD) && (e.out16 || e.bn_y16)) return MCG_ERR_UNSUPPORTED;
+    return with_epi<PM == 2 ? 1 : 2>(e, [&](auto epi) -> int {
+        Pol p; dim3 grid;
+        if (int st = plan_dgrad<BM, BN>(p, grid, g, y, w, bias, x, act, acc, e, ep, BK, 8, s)) return st;
+        if constexpr (PM == 0) return launch<gemm_kernel<Pol, BM, BN, BK, epi>>(grid, dim3(NTHREADS), 0, s, p);
+        else return launch<gemm_bf16_kernel<Pol, BM, BN, BK, epi>>(grid, dim3(NTHREADS), 0, s, p);
+    });
+}
+// ~4 blocks per CU, >= 4 K-steps per block
+template <int BM, int BN, int BK, int PM>
+int launch_wgrad(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
+    using Pol = WgradP<BM, BN, BK, PM == 2 ? 8 : 4, NTHREADS, false, false, (PM == 2 || PM == 3) ? 8 : 4>;
+    Pol p; dim3 grid;
+    plan_wgrad<BM, BN>(p, grid, g, x, y, dw, BK, 1024, 4);
+    if constexpr (PM == 0) return launch<gemm_kernel<Pol, BM, BN, BK, 0>>(grid, dim3(NTHREADS), 0, s, p);
+    else return launch<gemm_bf16_kernel<Pol, BM, BN, BK, 0>>(grid, dim3(NTHREADS), 0, s, p);
+}
+
+// tile code (1-5; anything else 64x64) / K-depth / precision mode -> instantiation of a register-staged launcher
+#define MCG_TILES(fn, t, BK, PM, ...)                                                                                   \
+    ((t) == 1 ? fn<128, 128, BK, PM>(__VA_ARGS__) : (t) == 2 ? fn<128, 64, BK, PM>(__VA_ARGS__)                         \
+     : (t) == 4 ? fn<256, 64, (PM) ? BK : 32, PM>(__VA_ARGS__)      /* fp32: 64-deep K-steps of the long tiles */       \
+     : (t) == 5 ? fn<64, 256, (PM) ? BK : 32, PM>(__VA_ARGS__)      /* would not fit the 64 KiB of static LDS    */     \
+                : fn<64, 64, BK, PM>(__VA_ARGS__))
+#define MCG_DEPTHS(fn, t, bk64, PM, ...) ((bk64) ? MCG_TILES(fn, t, 64, PM, __VA_ARGS__) : MCG_TILES(fn, t, 32, PM, __VA_ARGS__))
+#define MCG_DISPATCH(fn, t, bk64, pm, ...)                                                                              \
+    ((pm) == 2 ? MCG_DEPTHS(fn, t, bk64, 2, __VA_ARGS__) : (pm) == 1 ? MCG_DEPTHS(fn, t, bk64, 1, __VA_ARGS__) : MCG_DEPTHS(fn, t, bk64, 0, __VA_ARGS__))
+
+// LDS-DMA: what the kernels cover -- fp32 or bf16-stored operands, every K-step inside one filter tap, no K split by request
 bool v2_ok(const Geom& g, int kdim /* channel count along K: Ci (fprop), Co (dgrad) */) {
     return (g.prec == MCG_PREC_BF16_STORE || g.prec == MCG_PREC_F32) && kdim >= 64 && (kdim & (kdim - 1)) == 0 && g.ksplit == 1;
 }
+constexpr size_t v2_lds(int BM, int BN, int STAGES) { return (size_t)STAGES * (BM + BN) * 128; }
 
-// MCG_PREC_SPLIT: the launch is that of a bf16-stored layer with FOUR TIMES the channels along the summed dimension (16 channels x
-// 4 planes per group, mcg_split_planes); the kernel's SPLIT flag turns a group's K-step into the six products.
-Geom split_geom(const Geom& g, bool on_ci) {
-    Geom h = g;
-    h.prec = MCG_PREC_BF16_STORE;
-    h.split = 1;
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    const long long x_elems = (g.perm_n ? (long long)(g.perm_n - 1) * g.xs0 + (long long)(g.N / g.perm_n - 1) * g.xs1
-                                        : (long long)(g.N - 1) * g.xs0) + frame;
-    const long long y_elems = (long long)g.N * g.To * g.Ho * g.Wo * g.Co;
-    const long long w_elems = (long long)g.Co * g.taps * g.Ci;
-    if (on_ci) { h.Ci = 4 * g.Ci; h.lgCi = g.lgCi + 2; h.cv = h.Ci; h.xs0 = 4 * g.xs0; h.xs1 = 4 * g.xs1; h.x_bytes = (u32)(x_elems * 8); }
-    else { h.Co = 4 * g.Co; h.lgCo = g.lgCo + 2; h.y_bytes = (u32)(y_elems * 8); }
-    h.w_bytes = (u32)(w_elems * 8);
-    return h;
-}
-bool split_ok(const Geom& g, bool on_ci) {
-    const int c = on_ci ? g.Ci : g.Co;
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    const long long x_elems = (g.perm_n ? (long long)(g.perm_n - 1) * g.xs0 + (long long)(g.N / g.perm_n - 1) * g.xs1
-                                        : (long long)(g.N - 1) * g.xs0) + frame;
-    const long long y_elems = (long long)g.N * g.To * g.Ho * g.Wo * g.Co;
-    const long long w_elems = (long long)g.Co * g.taps * g.Ci;
-    return c >= 16 && (c & (c - 1)) == 0 && (on_ci ? x_elems : y_elems) * 8 < (1ll << 31) && w_elems * 8 < (1ll << 31);
-}
-
-template <class K> int v2_set_lds(K kernel, size_t lds, std::once_flag& once) {
-    hipError_t attr = hipSuccess;
-    std::call_once(once, [&] { attr = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    return attr == hipSuccess ? MCG_OK : MCG_ERR_LAUNCH;
-}
-#define MCG_V2_LAUNCH(KERNEL, GRID, LDS, P)                                                     \
-    do {                                                                                        \
-        static std::once_flag once_;                                                            \
-        if (v2_set_lds(KERNEL, LDS, once_) != MCG_OK) return MCG_ERR_LAUNCH;                    \
-        hipLaunchKernelGGL(KERNEL, GRID, dim3(NT2), LDS, s, P);                                 \
-    } while (0)
-
-// PM as in launch_fprop: 0 = fp32 operands (fp32 MFMA), 2 = bf16-stored operands
+// K-steps of 64, >= 16 per block (split-K, tile codes + 1000 / + 2000: the few tiles of a late layer on more CUs); class 2
+// (BatchNorm's backward sums) with bf16-stored / split operands only
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_fprop_v2(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
     using Pol = FpropP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true>;
-    Pol p;
-    p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
-    p.M = g.N * g.To * g.Ho * g.Wo; p.K = g.taps * g.Ci;
-    // split-K (tile codes + 1000 / + 2000, plain launches only): the few tiles of a late layer on more CUs; partial tiles are added
-    // onto a cleared y
-    int splits = (e.mode || e.out16) ? 1 : g.ksplit;
-    const int ksteps = p.K / 64;
-    if (splits > ksteps / 16) splits = ksteps / 16;
-    if (splits < 1) splits = 1;
-    p.kchunk = ((ksteps + splits - 1) / splits) * 64;
-    splits = (p.K + p.kchunk - 1) / p.kchunk;
-    if (splits == 1) p.kchunk = p.K;
-    else if (hipMemsetAsync(y, 0, (size_t)p.M * g.Co * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;
-    if (ep) { ep->n_slots = (p.M + BM - 1) / BM; ep->slot_stride = e.slot_stride; }
-    const int cls = e.mode ? epi_class(e.mode) : 0;
-    if (cls > 2 || (cls == 2 && PM != 2)) return MCG_ERR_UNSUPPORTED;       // (class 2, BatchNorm's backward sums: bf16-stored / split operands)
-    const dim3 grid((p.M + BM - 1) / BM, (g.Co + BN - 1) / BN, splits);
-    constexpr size_t lds = (size_t)STAGES * (BM + BN) * 128;
-    if (cls == 0) MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>), grid, lds, p);
-    else if (cls == 1) MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 1, SPLIT>), grid, lds, p);
-    else if constexpr (PM == 2) MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 2, SPLIT>), grid, lds, p);
-    return MCG_OK;
+    return with_epi<PM == 2 ? 2 : 1>(e, [&](auto epi) -> int {
+        Pol p; dim3 grid;
+        if (int st = plan_fprop<BM, BN>(p, grid, g, x, w, bias, y, e, ep, 64, 16, s)) return st;
+        return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, epi, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
+    });
 }
-
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_dgrad_v2(const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
-    using Pol = DgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true>;
-    Pol p;
-    p.g = g; p.e = e; p.y = y; p.w = w; p.bias = bias; p.x = x; p.act = act; p.accumulate = acc;
-    p.M = g.N * g.Ti * g.Ho * g.Wo; p.K = g.kt * 4 * g.Co;
-    const long long frame = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-    const bool dense_x = !g.perm_n && g.xs0 == frame;
-    int splits = (act == MCG_ACT_NONE && (acc || dense_x) && !e.mode && !e.out16) ? g.ksplit : 1;       // (as launch_dgrad)
-    const int ksteps = p.K / 64;
-    if (splits > ksteps / 16) splits = ksteps / 16;
-    if (splits < 1) splits = 1;
-    p.kchunk = ((ksteps + splits - 1) / splits) * 64;
-    splits = (p.K + p.kchunk - 1) / p.kchunk;
-    if (splits == 1) p.kchunk = p.K;
-    else if (!acc && hipMemsetAsync(x, 0, (size_t)g.N * frame * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;
-    if (ep) { ep->n_slots = 4 * ((p.M + BM - 1) / BM); ep->slot_stride = e.slot_stride; }
-    p.gxm = (p.M + BM - 1) / BM; p.gyn = (g.Ci + BN - 1) / BN; p.tiles8 = (p.gxm * p.gyn + 7) / 8;
-    const dim3 grid(8 * p.tiles8 * 4 * splits, 1, 1);
-    const int cls = e.mode ? epi_class(e.mode) : 0;
-    if (cls > 2 || (cls == 2 && PM != 2)) return MCG_ERR_UNSUPPORTED;
-    constexpr size_t lds = (size_t)STAGES * (BM + BN) * 128;
-    if (cls == 0) MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>), grid, lds, p);
-    else if (cls == 1) MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 1, SPLIT>), grid, lds, p);
-    else if constexpr (PM == 2) MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 2, SPLIT>), grid, lds, p);
-    return MCG_OK;
+    // not instantiated: 256x256 on split operands (three planes of fragments spill); 256x64 with two buffers on fp32 ones
+    if constexpr ((SPLIT && BM == 256 && BN == 256) || (PM == 0 && BN == 64 && STAGES == 2)) return MCG_ERR_UNSUPPORTED;
+    else {
+        using Pol = DgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true>;
+        return with_epi<PM == 2 ? 2 : 1>(e, [&](auto epi) -> int {
+            Pol p; dim3 grid;
+            if (int st = plan_dgrad<BM, BN>(p, grid, g, y, w, bias, x, act, acc, e, ep, 64, 16, s)) return st;
+            return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, epi, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
+        });
+    }
 }
-
+// One block per CU at a time (LDS): 2 rounds of blocks, >= 8 K-steps (split: 32, i.e. 512 pixels) per block; every block ends in BM x BN float atomics, so
+// fewer, longer blocks than the register-staged kernel's (a 2-D layer with few taps has few tiles -- G's dc3: 4 -- and 128 pixel
+// splits would each add 128 x 256 atomics onto the SAME 0.5 MB of dw)
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_wgrad_v2(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
     constexpr int BK = PM ? (SPLIT ? 16 : 64) : 32;              // PIXELS per K-step (split: 16 pixels x 4 planes = 64 k rows)
     using Pol = WgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, NT2, true, SPLIT != 0>;
-    Pol p;
-    p.g = g; p.x = x; p.y = y; p.dw = dw;
-    p.Mpix = g.N * g.To * g.Ho * g.Wo; p.Kf = g.taps * g.Ci;
-    const int tiles = ((g.Co + BM - 1) / BM) * ((p.Kf + BN - 1) / BN);
-    const int ksteps = (p.Mpix + BK - 1) / BK;
-    // one block per CU at a time (LDS): aim at 2 rounds of blocks; every block ends in BM x BN float atomics, so fewer, longer
-    // blocks than the register-staged kernel's.  Tile codes + 1000 / + 2000 (round 6) double / halve the target: a 2-D layer with
-    // few taps has few tiles (G's dc3: 4), so 128 pixel splits each add 128 x 256 atomics onto the SAME 0.5 MB of dw
-    const int target = g.ksplit == 2 ? 1024 : (g.ksplit == 4 ? 256 : 512);
-    int splits = (target + tiles - 1) / tiles;
-    constexpr int MINSTEPS = SPLIT ? 32 : 8;             // keep >= 512 pixels per block
-    if (splits > ksteps / MINSTEPS) splits = ksteps / MINSTEPS;
-    if (splits < 1) splits = 1;
-    p.chunk = ((ksteps + splits - 1) / splits) * BK;
-    splits = (p.Mpix + p.chunk - 1) / p.chunk;
-    const dim3 grid((g.Co + BM - 1) / BM, (p.Kf + BN - 1) / BN, splits);
-    constexpr size_t lds = (size_t)STAGES * (BM + BN) * 128;
-    MCG_V2_LAUNCH((gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>), grid, lds, p);
-    return MCG_OK;
+    Pol p; dim3 grid;
+    plan_wgrad<BM, BN>(p, grid, g, x, y, dw, BK, 512, SPLIT ? 32 : 8);
+    return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
 }
 
+// operand form of an LDS-DMA launch -> (PM, SPLIT) of the launcher `fn`
+enum { FORM_F32, FORM_BF16S, FORM_SPLIT };
+int v2_form(const Geom& g) { return g.prec == MCG_PREC_SPLIT ? FORM_SPLIT : g.prec == MCG_PREC_F32 ? FORM_F32 : FORM_BF16S; }
+#define MCG_V2_FORMS(fn, BM, BN, STAGES, form, ...)                                                                     \
+    ((form) == FORM_SPLIT ? fn<BM, BN, STAGES, 2, 1>(__VA_ARGS__) : (form) == FORM_F32 ? fn<BM, BN, STAGES, 0>(__VA_ARGS__) : fn<BM, BN, STAGES, 2>(__VA_ARGS__))
+
+// patch-stationary input gradient (tile code 9): one block per frame, all four output-parity classes
 bool dgrad_patch_ok(const Geom& g) {
     return g.prec == MCG_PREC_BF16_STORE && g.Ci == 64 && g.Ho == 16 && g.Wo == 16 && g.Co >= 64 && (g.Co & 63) == 0 && g.ksplit == 1 &&
            (long long)g.N * g.Ti < (1ll << 24);
 }
-
-template <int SPLIT = 0>
+template <int SPLIT>
 int launch_dgrad_patch(const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
-    DgPatchPol p;
-    p.g = g; p.e = e; p.y = y; p.w = w; p.bias = bias; p.x = x; p.act = act; p.accumulate = acc;
-    p.M = g.N * g.Ti * g.Ho * g.Wo; p.K = g.kt * 4 * g.Co;
-    p.gxm = p.M / 256; p.gyn = 1; p.tiles8 = (p.gxm + 7) / 8;
-    if (ep) { ep->n_slots = 4 * p.gxm; ep->slot_stride = e.slot_stride; }
-    const int cls = e.mode ? epi_class(e.mode) : 0;
-    if (cls > 1) return MCG_ERR_UNSUPPORTED;
-    const dim3 grid(g.N * g.Ti);
-    constexpr size_t lds = 2 * 48 * 1024 + 4 * 2 * 8192;
-    if (cls == 0) MCG_V2_LAUNCH((dgrad_patch_kernel<0, SPLIT>), grid, lds, p);
-    else MCG_V2_LAUNCH((dgrad_patch_kernel<1, SPLIT>), grid, lds, p);
-    return MCG_OK;
+    return with_epi<1>(e, [&](auto epi) -> int {
+        DgPatchPol p;
+        p.g = g; p.e = e; p.y = y; p.w = w; p.bias = bias; p.x = x; p.act = act; p.accumulate = acc;
+        p.M = g.N * g.Ti * g.Ho * g.Wo; p.K = g.kt * 4 * g.Co;
+        p.gxm = p.M / 256; p.gyn = 1; p.tiles8 = (p.gxm + 7) / 8;
+        if (ep) { ep->n_slots = 4 * p.gxm; ep->slot_stride = e.slot_stride; }
+        return launch<dgrad_patch_kernel<epi, SPLIT>>(dim3(g.N * g.Ti), dim3(NT2), 2 * 48 * 1024 + 4 * 2 * 8192, s, p);
+    });
 }
 
-// tile / K-depth / MFMA-type dispatch of the launch_* templates
-#define MCG_TILES(fn, t, BK, BF, ...)                                   \
-    do {                                                                \
-        if ((t) == 1) st = fn<128, 128, BK, BF>(__VA_ARGS__);           \
-        else if ((t) == 2) st = fn<128, 64, BK, BF>(__VA_ARGS__);       \
-        else if ((t) == 4) st = fn<256, 64, (BF) ? BK : 32, BF>(__VA_ARGS__);   /* fp32: 64-deep K-steps of the long tiles */ \
-        else if ((t) == 5) st = fn<64, 256, (BF) ? BK : 32, BF>(__VA_ARGS__);   /* would not fit the 64 KiB of static LDS     */ \
-        else st = fn<64, 64, BK, BF>(__VA_ARGS__);                      \
-    } while (0)
-#define MCG_DISPATCH(fn, t, bk64, pm, ...)                              \
-    do {                                                                \
-        if ((pm) == 2)      { if (bk64) MCG_TILES(fn, t, 64, 2, __VA_ARGS__); else MCG_TILES(fn, t, 32, 2, __VA_ARGS__); }      \
-        else if ((pm) == 1) { if (bk64) MCG_TILES(fn, t, 64, 1, __VA_ARGS__); else MCG_TILES(fn, t, 32, 1, __VA_ARGS__); }      \
-        else                { if (bk64) MCG_TILES(fn, t, 64, 0, __VA_ARGS__); else MCG_TILES(fn, t, 32, 0, __VA_ARGS__); }      \
-    } while (0)
+// ---- the kernels written for the Ci = 4 layers (the 3-channel clip padded to 4; tile code 6) ----
+// what they share: Co = 64, rows of 16 or 32 output pixels, a whole number of `pixels`-pixel block steps per frame
+bool c4_layer(const Geom& g, int pixels) { return g.Ci == 4 && g.Co == 64 && (g.Wo == 32 || g.Wo == 16) && g.Ho % (pixels / g.Wo) == 0; }
 
-// a launch status that also reports a failed clear of a split-K output (st) -- the atomics would otherwise add onto stale data
-int finish(int st) { return st != MCG_OK ? st : launch_status(); }
+// weight-stationary forward kernel; the only epilogue it carries is the activation (this layer's tensors are fp32 in memory;
+// a plain bf16 output: G's dc5 read backwards)
+bool c4_fprop_ok(const Geom& g, const Epi& e) {
+    return c4_layer(g, 256) && dense_x(g) && g.prec != MCG_PREC_BF16_STORE && (e.mode == 0 || e.mode == EPI_ACT) &&
+           (!e.out16 || e.mode == EPI_ACT || (e.mode == 0 && g.prec == MCG_PREC_BF16));
+}
+template <int KT, int WO, bool BF>
+int launch_fprop_c4(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, hipStream_t s) {
+    C4FpropP p;
+    p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
+    p.M = g.N * g.To * g.Ho * g.Wo;
+    constexpr int R = 256 / WO, K = KT * 64;
+    constexpr size_t lds = BF ? (size_t)64 * (K + 8) * 2 + (size_t)KT * (2 * R + 2) * (2 * WO + 4) * 8 + 4096
+                              : (size_t)64 * (K + 4) * 4 + (size_t)KT * (2 * R + 2) * 2 * (WO + 2) * 16 + 4096;
+    const dim3 grid(g.N * (g.Ho / R)), block(512);
+    const bool act = e.mode & EPI_ACT, cv3 = g.cv <= 3;
+    if constexpr (BF) return act ? launch<fprop_c4_bf16_kernel<KT, WO, 3>>(grid, block, lds, s, p) : launch<fprop_c4_bf16_kernel<KT, WO, 1>>(grid, block, lds, s, p);
+    else if (act) return cv3 ? launch<fprop_c4_kernel<KT, WO, 3, 3>>(grid, block, lds, s, p) : launch<fprop_c4_kernel<KT, WO, 3, 4>>(grid, block, lds, s, p);
+    else return cv3 ? launch<fprop_c4_kernel<KT, WO, 1, 3>>(grid, block, lds, s, p) : launch<fprop_c4_kernel<KT, WO, 1, 4>>(grid, block, lds, s, p);
+}
 
-std::once_flag g_c4_lds_once;      // dgrad_c4_kernel<4> needs the 64 KiB dynamic-LDS opt-in once per process (one process per GPU)
+// MFMA col2im input gradient.  x must be ONE dense buffer of N frames (it is cleared as a whole): plain batch order, or the
+// generator's (T,N) -> (N,T) frame permutation, which maps the N frames one-to-one onto it
+bool c4_dgrad_mfma_ok(const Geom& g, const Epi& e, const float* bias, int act, int accumulate) {
+    const long long frame = frame_elems(g);
+    const bool whole = g.perm_n ? (g.xs1 == frame && g.xs0 == (long long)(g.N / g.perm_n) * frame) : g.xs0 == frame;
+    return c4_layer(g, 128) && g.cv <= 3 && whole && !e.mode && !e.out16 && !bias && act == MCG_ACT_NONE && !accumulate;
+}
+constexpr int C4_DGRAD_MAX_BLOCKS = 1024;      // blocks of the persistent first-layer input-gradient kernel (4 per CU; each walks tiles)
+template <int KT, int WO, bool BF, bool Y16>
+int launch_dgrad_c4_mfma(const Geom& g, const float* y, const float* w, float* x, hipStream_t s) {
+    C4DgradP p;
+    p.g = g; p.y = y; p.w = w; p.x = x;
+    constexpr int R = 128 / WO, NPX = (2 * R + 2) * 2 * WO, LD = BF ? 40 : 68;
+    constexpr size_t lds = (size_t)(128 * LD + KT * 48 * LD + ((BF && KT > 1) ? 2 : 1) * 128 * 52) * 4 + (size_t)KT * NPX * 16;
+    constexpr auto kernel = dgrad_c4_mfma_kernel<KT, WO, BF, Y16>;
+    if (lds_opt_in<kernel>(lds) != MCG_OK) return MCG_ERR_LAUNCH;          // (before x is touched)
+    // the rows two neighbouring blocks share are ADDED (two addends, order-independent): x starts from zero
+    if (clear_output(x, g.N * frame_elems(g), s) != MCG_OK) return MCG_ERR_LAUNCH;
+    const int ntiles = g.N * (g.Ho / R);
+    return launch<kernel>(dim3(ntiles < C4_DGRAD_MAX_BLOCKS ? ntiles : C4_DGRAD_MAX_BLOCKS), dim3(512), lds, s, p);
+}
 
-}  // namespace
-
-
-namespace {
+// patch-in-LDS weight gradient (<= 3 data channels), fp32 or -- bf16 networks, y bf16 beside the fp32 clip -- on the bf16 MFMA
+// with the y tile in LDS too.  (Ho a multiple of the 256-pixel step's rows, hence of the 128-pixel step's.)
+bool c4_wgrad_ok(const Geom& g) {
+    return c4_layer(g, 256) && g.cv <= 3 && dense_x(g) && (g.prec == MCG_PREC_F32 || (g.prec == MCG_PREC_BF16 && g.y16));
+}
+template <int KT, int WO, bool BF>
+int launch_wgrad_c4(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
+    // bf16, 3-D layers (enough rows): 128-pixel steps, 256 threads, two blocks per CU; otherwise 256-pixel steps, one block per CU
+    constexpr int BM = (BF && KT == 4) ? 128 : 256, NT = 2 * BM, R = BM / WO;
+    constexpr size_t lds = BF ? (size_t)(KT + 1) * (2 * R + 2) * (2 * WO + 4) * 8 + 2 * BM * WC4_YS : (size_t)(KT + 1) * (2 * R + 2) * 2 * (WO + 2) * 16;
+    C4WgradP p;
+    p.g = g; p.x = x; p.y = y; p.dw = dw;
+    // (row block, batch item) pairs, at most 512 blocks: with more pairs a block walks several items (every block ends in
+    // 64 x kt * 48 float atomics onto the same dw: measured at 512 clips 0.458-0.472 ms with 1024 blocks, 0.397-0.406 with 512,
+    // 0.412-0.420 with 256); with fewer than 256 the frames of an item are split as well (each part re-reads kt - 1 frames;
+    // >= 2 steps per part)
+    const int hblocks = g.Ho / R;
+    p.nsplit = g.N; p.tsplit = 1;
+    if (hblocks * p.nsplit > 512) p.nsplit = 512 / hblocks > 0 ? 512 / hblocks : 1;
+    while (hblocks * p.nsplit * p.tsplit < 256 && 2 * p.tsplit * 2 <= g.To) p.tsplit *= 2;
+    const dim3 grid(hblocks * p.nsplit * p.tsplit);
+    if constexpr (BF) return launch<wgrad_c4_bf16_kernel<KT, WO, NT, BM>>(grid, dim3(NT), lds, s, p);
+    else return launch<wgrad_c4_kernel<KT, WO>>(grid, dim3(NT), lds, s, p);
+}
 
 // mcg_conv_epilogue -> Epi (validated on the host); pass 0 = fprop (C = Co), 1 = dgrad (C = Ci)
 int make_epi(const mcg_conv_epilogue* ep, const Geom& g, int pass, Epi& e) {
@@ -3372,9 +3291,25 @@ int make_epi(const mcg_conv_epilogue* ep, const Geom& g, int pass, Epi& e) {
     return MCG_OK;
 }
 
+}  // namespace
+
+// Tile code x pass -> kernel (t = mcg_conv_geom.tile % 100; "LDS-DMA BMxBN/S": gemm_bf16_v2_kernel with S tile buffers):
+//   t      fprop                          dgrad                                      wgrad
+//   0      Ci = 4 layers: as 6; else heuristic over 1-3 (split operands: as 7)       heuristic over 1, 3 (split: as 7)
+//   1-5    register-staged 128x128, 128x64, 64x64, 256x64, 64x256 (gemm_kernel fp32 / gemm_bf16_kernel), all passes
+//   6      fprop_c4[_bf16]_kernel         dgrad_c4_mfma_kernel, else as 0            wgrad_c4[_bf16]_kernel
+//   7      LDS-DMA 256x128/3              256x128/3 (Ci = 64: 256x64/3)              128x256/3
+//   8      LDS-DMA 256x256/2              256x256/2 (Ci = 64, 128 and split: as 7)   256x256/2 (Co = 128: as 7)
+//          (split, Co < 256: as 7)
+//   9      -                              dgrad_patch_kernel                         -
+//   10     LDS-DMA 128x128/2              128x128/2 (Ci = 64: 256x64/2, not fp32)    128x128/2
+// dgrad, t = 0, Ci = 4 outside dgrad_c4_mfma_kernel's reach: dgrad_c4_kernel (VALU).  The LDS-DMA kernels take fp32,
+// bf16-stored or split operands (one dispatch on the form, MCG_V2_FORMS), tile 9 bf16-stored or split ones.
+
 // The three passes can be compiled as separate translation units (-DMCG_TU=1 fprop, 2 dgrad, 3 wgrad + the
 // fully-connected GEMMs) so that the build runs in parallel; without MCG_TU this file is the whole library part.
 #if !defined(MCG_TU) || MCG_TU == 1
+namespace {
 int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, const float* bias, float* y,
                     mcg_conv_epilogue* ep, void* stream) {
     Geom g;
@@ -3385,59 +3320,37 @@ int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, cons
     if ((st = make_epi(ep, g, 0, e)) != MCG_OK) return st;
     if (!e.mode) ep = nullptr;
     hipStream_t s = (hipStream_t)stream;
-    long long M = (long long)g.N * g.To * g.Ho * g.Wo;
-    // Tile choice (measured on MI355X, tools/bench_layers.py): 128x128 only when there are enough tiles
-    // that the last partial round of blocks does not matter, else 128x64, else 64x64 to fill 256 CUs.
+    const bool split = g.prec == MCG_PREC_SPLIT;                   // fp32 values as three bf16 terms: the LDS-DMA kernels only
     int t = g.tile;
-    const int bk = g.bk;
-    if (g.prec == MCG_PREC_SPLIT) {                                // fp32 values as three bf16 terms: the LDS-DMA kernels only
-        if ((t != 0 && t != 7 && t != 8 && t != 10) || !split_ok(g, true) || (e.mode & ~(EPI_STATS | EPI_COL | EPI_MASKMUL | EPI_BNBWD)) || e.out16) return MCG_ERR_UNSUPPORTED;
-        const Geom h = split_geom(g, true);
-        if (t == 10) st = launch_fprop_v2<128, 128, 2, 2, 1>(h, x, w, bias, y, e, ep, s);        // two blocks per CU
-        else st = (t == 8 && g.Co >= 256) ? launch_fprop_v2<256, 256, 2, 2, 1>(h, x, w, bias, y, e, ep, s) : launch_fprop_v2<256, 128, 3, 2, 1>(h, x, w, bias, y, e, ep, s);
-        return finish(st);
-    }
-    if ((t == 0 || t == 6) && c4_fprop_ok(g, e)) {                 // the 3-channel clip padded to 4: weight-stationary kernel
+    if (split) {
+        if ((t != 0 && t != 7 && t != 8 && t != 10) || !split_ok(g, SPLIT_CI) || e.out16) return MCG_ERR_UNSUPPORTED;
+        if (!t) t = 7;
+    } else if ((t == 0 || t == 6) && c4_fprop_ok(g, e)) {          // the 3-channel clip padded to 4: weight-stationary kernel
         if (ep) { ep->n_slots = 0; ep->slot_stride = e.slot_stride; }
-        if (g.prec == MCG_PREC_BF16) {
-            if (g.kt == 4) st = g.Wo == 32 ? launch_fprop_c4_bf16<4, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4_bf16<4, 16>(g, x, w, bias, y, e, s);
-            else st = g.Wo == 32 ? launch_fprop_c4_bf16<1, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4_bf16<1, 16>(g, x, w, bias, y, e, s);
-        } else {
-            if (g.kt == 4) st = g.Wo == 32 ? launch_fprop_c4<4, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4<4, 16>(g, x, w, bias, y, e, s);
-            else st = g.Wo == 32 ? launch_fprop_c4<1, 32>(g, x, w, bias, y, e, s) : launch_fprop_c4<1, 16>(g, x, w, bias, y, e, s);
-        }
-        return finish(st);
+        if (g.prec == MCG_PREC_BF16) return with_kt_wo(g, [&](auto kt, auto wo) { return launch_fprop_c4<kt, wo, true>(g, x, w, bias, y, e, s); });
+        return with_kt_wo(g, [&](auto kt, auto wo) { return launch_fprop_c4<kt, wo, false>(g, x, w, bias, y, e, s); });
     }
     if (t == 6 || t == 9) return MCG_ERR_UNSUPPORTED;
-    if (t == 7 || t == 8 || t == 10) {                             // the LDS-DMA kernels (bf16-stored operands, wide layers)
-        if (!v2_ok(g, g.Ci) || e.mode & ~(EPI_STATS | EPI_COL | EPI_MASKMUL | EPI_BNBWD)) return MCG_ERR_UNSUPPORTED;
-        if (t == 10) {                                             // 128x128, two buffers: TWO blocks per CU
-            if (g.prec == MCG_PREC_F32) return finish(launch_fprop_v2<128, 128, 2, 0>(g, x, w, bias, y, e, ep, s));
-            return finish(launch_fprop_v2<128, 128, 2, 2>(g, x, w, bias, y, e, ep, s));
-        }
-        if (g.prec == MCG_PREC_F32)
-            st = t == 7 ? launch_fprop_v2<256, 128, 3, 0>(g, x, w, bias, y, e, ep, s) : launch_fprop_v2<256, 256, 2, 0>(g, x, w, bias, y, e, ep, s);
-        else
-            st = t == 7 ? launch_fprop_v2<256, 128, 3, 2>(g, x, w, bias, y, e, ep, s) : launch_fprop_v2<256, 256, 2, 2>(g, x, w, bias, y, e, ep, s);
-        return finish(st);
+    if (t == 7 || t == 8 || t == 10) {                             // the LDS-DMA kernels (wide layers)
+        if (!split && !v2_ok(g, g.Ci)) return MCG_ERR_UNSUPPORTED;
+        const Geom h = split ? split_geom(g, SPLIT_CI) : g;
+        const int form = v2_form(g);
+        if (t == 10) return MCG_V2_FORMS(launch_fprop_v2, 128, 128, 2, form, h, x, w, bias, y, e, ep, s);     // two blocks per CU
+        if (t == 8 && (!split || g.Co >= 256)) return MCG_V2_FORMS(launch_fprop_v2, 256, 256, 2, form, h, x, w, bias, y, e, ep, s);
+        return MCG_V2_FORMS(launch_fprop_v2, 256, 128, 3, form, h, x, w, bias, y, e, ep, s);
     }
-    const long long mt = (M + 127) / 128;
+    // Tile choice (measured on MI355X, tools/bench_layers.py): 128x128 only when there are enough tiles
+    // that the last partial round of blocks does not matter, else 128x64, else 64x64 to fill 256 CUs.
+    const long long M = (long long)g.N * g.To * g.Ho * g.Wo, mt = (M + 127) / 128;
     if (!t) t = g.Co <= 64 ? 2 : (mt * ((g.Co + 127) / 128) >= 1024 ? 1 : (mt * ((g.Co + 63) / 64) >= 512 ? 2 : 3));
     // 64-deep K-steps halve the per-step overhead (barriers, LDS refill, address math) and pay off when the
     // grid is small (few resident waves to hide it: measured on dc4); big grids prefer the higher occupancy of 32.
     const long long nblk = ((M + (t == 3 ? 63 : 127)) / (t == 3 ? 64 : 128)) * ((g.Co + (t == 1 ? 127 : 63)) / (t == 1 ? 128 : 64));
-    const bool bk64 = (g.taps * g.Ci) % 64 == 0 && (bk ? bk == 64 : (nblk < 1024 || g.prec != MCG_PREC_F32));
-    MCG_DISPATCH(launch_fprop, t, bk64, g.prec, g, x, w, bias, y, e, ep, s);
-    return finish(st);
+    const bool bk64 = (g.taps * g.Ci) % 64 == 0 && (g.bk ? g.bk == 64 : (nblk < 1024 || g.prec != MCG_PREC_F32));
+    return MCG_DISPATCH(launch_fprop, t, bk64, g.prec, g, x, w, bias, y, e, ep, s);
 }
-#endif
-
-int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x, int act, int accumulate,
-                    mcg_conv_epilogue* ep, void* stream);
-
 }  // namespace
 
-#if !defined(MCG_TU) || MCG_TU == 1
 extern "C" int mcg_conv_fprop(const mcg_conv_geom* c, const float* x, const float* w, const float* bias, float* y, void* stream) {
     return conv_fprop_impl(c, x, w, bias, y, nullptr, stream);
 }
@@ -3455,21 +3368,9 @@ extern "C" int64_t mcg_conv_epilogue_part_bytes(const mcg_conv_geom* c, int pass
 #endif
 
 #if !defined(MCG_TU) || MCG_TU == 2
-extern "C" int mcg_conv_dgrad(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x, int act,
-                              int accumulate, void* stream) {
-    return conv_dgrad_impl(c, y, w, bias, x, act, accumulate, nullptr, stream);
-}
-extern "C" int mcg_conv_dgrad_ex(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x,
-                                 mcg_conv_epilogue* ep, void* stream) {
-    if (ep) { ep->n_slots = 0; ep->slot_stride = 0; }
-    return conv_dgrad_impl(c, y, w, bias, x, ep ? ep->act : MCG_ACT_NONE, 0, ep, stream);      // (ep->act: MCG_ACT_NONE or MCG_ACT_RELU, make_epi)
-}
-
 namespace {
-
 int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x, int act, int accumulate,
                     mcg_conv_epilogue* ep, void* stream) {
-
     Geom g;
     int st = make_geom(c, g);
     if (st) return st;
@@ -3481,84 +3382,47 @@ int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, cons
     // ReLU (test-mode BatchNorm folded into w and bias: x = max(conv_transpose(y, w') + b', 0)) lives in the store of whole output
     // elements of the wide layers: never on partial tiles, an accumulating call, next to a sums / mask epilogue, or on the clip side
     if (act == MCG_ACT_RELU && (g.ksplit > 1 || accumulate || e.mode || g.Ci == 4)) return MCG_ERR_UNSUPPORTED;
-    if (e.mode) {                                                // the epilogue addresses x as a dense [pixels][Ci] tensor
-        const long long frame_ = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-        if (g.perm_n || g.xs0 != frame_ || act != MCG_ACT_NONE || accumulate) return MCG_ERR_UNSUPPORTED;
-    }
+    // the epilogue addresses x as a dense [pixels][Ci] tensor
+    if (e.mode && (!dense_x(g) || act != MCG_ACT_NONE || accumulate)) return MCG_ERR_UNSUPPORTED;
     if (e.out16 && (accumulate || g.Ci == 4)) return MCG_ERR_UNSUPPORTED;   // (the clip-side kernels and accumulating calls write fp32)
     hipStream_t s = (hipStream_t)stream;
-    long long M = (long long)g.N * g.Ti * g.Ho * g.Wo;
+    const bool split = g.prec == MCG_PREC_SPLIT;                 // fp32 values as three bf16 terms: the LDS-DMA kernels only
     int t = g.tile;
-    const int bk = g.bk;
-    if (g.prec == MCG_PREC_SPLIT) {                              // fp32 values as three bf16 terms: the LDS-DMA kernels only
-        if ((t != 0 && t != 7 && t != 8 && t != 9 && t != 10) || !split_ok(g, false) || g.Ci < 64 || (g.Ci & (g.Ci - 1)) || (e.mode & ~(EPI_STATS | EPI_COL | EPI_MASKMUL | EPI_BNBWD)) || e.out16)
-            return MCG_ERR_UNSUPPORTED;
-        const Geom h = split_geom(g, false);
-        if (t == 9) {                                            // patch-stationary, four parity classes per block
-            if (!dgrad_patch_ok(h)) return MCG_ERR_UNSUPPORTED;
-            return finish(launch_dgrad_patch<1>(h, y, w, bias, x, act, accumulate, e, ep, s));
+    if (split) {
+        if ((t != 0 && t != 7 && t != 8 && t != 9 && t != 10) || !split_ok(g, SPLIT_CO) || e.out16) return MCG_ERR_UNSUPPORTED;
+        if (!t) t = 7;
+    } else {
+        if ((t == 0 || t == 6) && g.prec != MCG_PREC_BF16_STORE && c4_dgrad_mfma_ok(g, e, bias, act, accumulate)) {
+            // computes in fp32; bf16 networks: the same kernel on the bf16 MFMA, with MCG_PREC_BF16_Y16 reading a y that is bf16 in memory
+            if (g.y16) return with_kt_wo(g, [&](auto kt, auto wo) { return launch_dgrad_c4_mfma<kt, wo, true, true>(g, y, w, x, s); });
+            if (g.prec == MCG_PREC_BF16) return with_kt_wo(g, [&](auto kt, auto wo) { return launch_dgrad_c4_mfma<kt, wo, true, false>(g, y, w, x, s); });
+            return with_kt_wo(g, [&](auto kt, auto wo) { return launch_dgrad_c4_mfma<kt, wo, false, false>(g, y, w, x, s); });
         }
-        if (t == 10) {                                           // two blocks per CU: 128x128, or 256x64 with two buffers (2 x 80 KB of LDS)
-            if (g.Ci == 64) return finish(launch_dgrad_v2<256, 64, 2, 2, 1>(h, y, w, bias, x, act, accumulate, e, ep, s));
-            return finish(launch_dgrad_v2<128, 128, 2, 2, 1>(h, y, w, bias, x, act, accumulate, e, ep, s));
-        }
-        if (g.Ci == 64) st = launch_dgrad_v2<256, 64, 3, 2, 1>(h, y, w, bias, x, act, accumulate, e, ep, s);
-        else st = launch_dgrad_v2<256, 128, 3, 2, 1>(h, y, w, bias, x, act, accumulate, e, ep, s);     // (256x256 with three planes of fragments spills)
-        return finish(st);
+        if (g.y16) return MCG_ERR_UNSUPPORTED;                   // (a bf16 y beside fp32 w: the first-layer kernel above only)
+        if (t == 6) t = 0;                                       // elsewhere the first-layer code means "the kernel written for it"
     }
-    if ((t == 0 || t == 6) && g.prec != MCG_PREC_BF16_STORE && c4_dgrad_mfma_ok(g, e, bias, act, accumulate)) {      // (computes in fp32)
-        if (g.prec == MCG_PREC_BF16 && g.y16) {                  // ... reading a y tensor that is bf16 in memory (MCG_PREC_BF16_Y16)
-            if (g.kt == 4) st = g.Wo == 32 ? launch_dgrad_c4_mfma<4, 32, true, true>(g, y, w, x, s) : launch_dgrad_c4_mfma<4, 16, true, true>(g, y, w, x, s);
-            else st = g.Wo == 32 ? launch_dgrad_c4_mfma<1, 32, true, true>(g, y, w, x, s) : launch_dgrad_c4_mfma<1, 16, true, true>(g, y, w, x, s);
-        } else if (g.prec == MCG_PREC_BF16) {                    // bf16 networks: the same kernel on the bf16 MFMA
-            if (g.kt == 4) st = g.Wo == 32 ? launch_dgrad_c4_mfma<4, 32, true>(g, y, w, x, s) : launch_dgrad_c4_mfma<4, 16, true>(g, y, w, x, s);
-            else st = g.Wo == 32 ? launch_dgrad_c4_mfma<1, 32, true>(g, y, w, x, s) : launch_dgrad_c4_mfma<1, 16, true>(g, y, w, x, s);
-        } else {
-            if (g.kt == 4) st = g.Wo == 32 ? launch_dgrad_c4_mfma<4, 32, false>(g, y, w, x, s) : launch_dgrad_c4_mfma<4, 16, false>(g, y, w, x, s);
-            else st = g.Wo == 32 ? launch_dgrad_c4_mfma<1, 32, false>(g, y, w, x, s) : launch_dgrad_c4_mfma<1, 16, false>(g, y, w, x, s);
-        }
-        return finish(st);
+    const Geom h = split ? split_geom(g, SPLIT_CO) : g;
+    if (t == 9) {                                                // patch-stationary (Ci = 64, 16 x 16)
+        if (!dgrad_patch_ok(h)) return MCG_ERR_UNSUPPORTED;
+        return split ? launch_dgrad_patch<1>(h, y, w, bias, x, act, accumulate, e, ep, s) : launch_dgrad_patch<0>(h, y, w, bias, x, act, accumulate, e, ep, s);
     }
-    if (g.y16) return MCG_ERR_UNSUPPORTED;                       // (a bf16 y beside fp32 w: the first-layer kernel above only)
-    if (t == 6) t = 0;                                           // elsewhere the first-layer code means "the kernel written for it"
-    if (t == 9) {                                                // patch-stationary, four parity classes per block (Ci = 64, 16 x 16)
-        if (!dgrad_patch_ok(g) || (e.mode & ~(EPI_STATS | EPI_COL | EPI_MASKMUL))) return MCG_ERR_UNSUPPORTED;
-        return finish(launch_dgrad_patch(g, y, w, bias, x, act, accumulate, e, ep, s));
+    if (t == 7 || t == 8 || t == 10) {                           // the LDS-DMA kernels (wide layers)
+        if ((!split && !v2_ok(g, g.Co)) || g.Ci < 64 || (g.Ci & (g.Ci - 1))) return MCG_ERR_UNSUPPORTED;
+        const int form = v2_form(g);
+        if (g.Ci == 64 && t == 10) return MCG_V2_FORMS(launch_dgrad_v2, 256, 64, 2, form, h, y, w, bias, x, act, accumulate, e, ep, s);      // (2 x 80 KB of LDS: two blocks per CU)
+        if (g.Ci == 64) return MCG_V2_FORMS(launch_dgrad_v2, 256, 64, 3, form, h, y, w, bias, x, act, accumulate, e, ep, s);
+        if (t == 10) return MCG_V2_FORMS(launch_dgrad_v2, 128, 128, 2, form, h, y, w, bias, x, act, accumulate, e, ep, s);                   // two blocks per CU
+        if (g.Ci == 128 || t == 7 || split) return MCG_V2_FORMS(launch_dgrad_v2, 256, 128, 3, form, h, y, w, bias, x, act, accumulate, e, ep, s);
+        return MCG_V2_FORMS(launch_dgrad_v2, 256, 256, 2, form, h, y, w, bias, x, act, accumulate, e, ep, s);
     }
-    if (t == 7 || t == 8 || t == 10) {                           // the LDS-DMA kernels (bf16-stored operands, wide layers)
-        const long long frame_ = (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-        if (!v2_ok(g, g.Co) || g.Ci < 64 || (g.Ci & (g.Ci - 1)) || (e.mode & ~(EPI_STATS | EPI_COL | EPI_MASKMUL | EPI_BNBWD))) return MCG_ERR_UNSUPPORTED;
-        if (t == 10) {                                           // two blocks per CU: 128x128, or (Ci = 64, bf16-stored) 256x64 with two buffers
-            if (g.Ci == 64) {
-                if (g.prec != MCG_PREC_BF16_STORE) return MCG_ERR_UNSUPPORTED;
-                return finish(launch_dgrad_v2<256, 64, 2, 2>(g, y, w, bias, x, act, accumulate, e, ep, s));
-            }
-            if (g.prec == MCG_PREC_F32) return finish(launch_dgrad_v2<128, 128, 2, 0>(g, y, w, bias, x, act, accumulate, e, ep, s));
-            return finish(launch_dgrad_v2<128, 128, 2, 2>(g, y, w, bias, x, act, accumulate, e, ep, s));
-        }
-        (void)frame_;
-#define MCG_DG2(PM_) do {                                                                                              \
-            if (g.Ci == 64) st = launch_dgrad_v2<256, 64, 3, PM_>(g, y, w, bias, x, act, accumulate, e, ep, s);                 \
-            else if (g.Ci == 128 || t == 7) st = launch_dgrad_v2<256, 128, 3, PM_>(g, y, w, bias, x, act, accumulate, e, ep, s); \
-            else st = launch_dgrad_v2<256, 256, 2, PM_>(g, y, w, bias, x, act, accumulate, e, ep, s); } while (0)
-        if (g.prec == MCG_PREC_F32) MCG_DG2(0); else MCG_DG2(2);
-#undef MCG_DG2
-        return finish(st);
-    }
+    const long long M = (long long)g.N * g.Ti * g.Ho * g.Wo;     // half-resolution positions
     if (!t && !e.mode && g.Ci == 4 && g.Co == 64 && (g.Wo & 15) == 0) {      // VALU kernel for the padded 3-channel clip
-        const int runs = (int)(M / 16);                          // M = N*Ti*Ho*Wo half-resolution positions
+        const int runs = (int)(M / 16);
         const int per_block = (NTHREADS / 64) * C4_RUNS_PER_WAVE;
-        dim3 grid((runs + per_block - 1) / per_block, 1, 1);
+        const dim3 grid((runs + per_block - 1) / per_block, 1, 1);
         const size_t lds = (size_t)g.kt * 16 * 64 * sizeof(f32x4);
-        if (g.kt == 4) {
-            hipError_t attr = hipSuccess;
-            std::call_once(g_c4_lds_once, [&] { attr = hipFuncSetAttribute((const void*)dgrad_c4_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-            if (attr != hipSuccess) return MCG_ERR_LAUNCH;
-            hipLaunchKernelGGL(dgrad_c4_kernel<4>, grid, dim3(NTHREADS), lds, s, g, y, w, bias, x, act, accumulate, runs);
-        } else {
-            hipLaunchKernelGGL(dgrad_c4_kernel<1>, grid, dim3(NTHREADS), lds, s, g, y, w, bias, x, act, accumulate, runs);
-        }
-        return launch_status();
+        if (g.kt == 4) return launch<dgrad_c4_kernel<4>>(grid, dim3(NTHREADS), lds, s, g, y, w, bias, x, act, accumulate, runs);
+        return launch<dgrad_c4_kernel<1>>(grid, dim3(NTHREADS), lds, s, g, y, w, bias, x, act, accumulate, runs);
     }
     if (!t) {
         const long long mt = (M + 127) / 128;
@@ -3566,12 +3430,20 @@ int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, cons
         else t = g.Ci <= 64 ? 2 : (4 * mt * ((g.Ci + 127) / 128) >= 1024 ? 1 : 2);
     }
     const long long nblk = 4 * ((M + (t == 3 ? 63 : 127)) / (t == 3 ? 64 : 128)) * ((g.Ci + (t == 1 ? 127 : 63)) / (t == 1 ? 128 : 64));
-    const bool bk64 = (g.kt * 4 * g.Co) % 64 == 0 && (bk ? bk == 64 : (nblk < 1024 || g.prec != MCG_PREC_F32));
-    MCG_DISPATCH(launch_dgrad, t, bk64, g.prec, g, y, w, bias, x, act, accumulate, e, ep, s);
-    return finish(st);
+    const bool bk64 = (g.kt * 4 * g.Co) % 64 == 0 && (g.bk ? g.bk == 64 : (nblk < 1024 || g.prec != MCG_PREC_F32));
+    return MCG_DISPATCH(launch_dgrad, t, bk64, g.prec, g, y, w, bias, x, act, accumulate, e, ep, s);
 }
-
 }  // namespace
+
+extern "C" int mcg_conv_dgrad(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x, int act,
+                              int accumulate, void* stream) {
+    return conv_dgrad_impl(c, y, w, bias, x, act, accumulate, nullptr, stream);
+}
+extern "C" int mcg_conv_dgrad_ex(const mcg_conv_geom* c, const float* y, const float* w, const float* bias, float* x,
+                                 mcg_conv_epilogue* ep, void* stream) {
+    if (ep) { ep->n_slots = 0; ep->slot_stride = 0; }
+    return conv_dgrad_impl(c, y, w, bias, x, ep ? ep->act : MCG_ACT_NONE, 0, ep, stream);      // (ep->act: MCG_ACT_NONE or MCG_ACT_RELU, make_epi)
+}
 #endif
 
 #if !defined(MCG_TU) || MCG_TU == 3
@@ -3580,99 +3452,63 @@ extern "C" int mcg_conv_wgrad(const mcg_conv_geom* c, const float* x, const floa
     int st = make_geom(c, g);
     if (st) return st;
     if (!x || !dw || !y) return MCG_ERR_BAD_ARG;
-    if (g.prec == MCG_PREC_SPLIT) {                              // x and y in the split layout: 16 pixels x 4 planes per K-step
-        const long long x_el = (g.perm_n ? (long long)(g.perm_n - 1) * g.xs0 + (long long)(g.N / g.perm_n - 1) * g.xs1 : (long long)(g.N - 1) * g.xs0) +
-                               (long long)g.Ti * g.Hi * g.Wi * g.Ci;
-        const long long y_el = (long long)g.N * g.To * g.Ho * g.Wo * g.Co;
-        if ((g.tile != 0 && g.tile != 7 && g.tile != 8 && g.tile != 10) || g.Co < 128 || (g.Co & 63) || g.Ci < 64 || (g.Ci & (g.Ci - 1)) ||
-            x_el * 8 >= (1ll << 31) || y_el * 8 >= (1ll << 31) || (y_el / g.Co) % 16) return MCG_ERR_UNSUPPORTED;
-        Geom h = g;
-        h.prec = MCG_PREC_BF16_STORE; h.x_bytes = (u32)(x_el * 8); h.y_bytes = (u32)(y_el * 8);
-        if (g.tile == 10) return finish(launch_wgrad_v2<128, 128, 2, 2, 1>(h, x, y, dw, (hipStream_t)stream));      // two blocks per CU
-        st = (g.Co == 128 || g.tile != 8) ? launch_wgrad_v2<128, 256, 3, 2, 1>(h, x, y, dw, (hipStream_t)stream)
-                                          : launch_wgrad_v2<256, 256, 2, 2, 1>(h, x, y, dw, (hipStream_t)stream);
-        return finish(st);
-    }
     hipStream_t s = (hipStream_t)stream;
-    int Kf = g.taps * g.Ci;
+    const bool split = g.prec == MCG_PREC_SPLIT;                 // x and y in the split layout: 16 pixels x 4 planes per K-step
     int t = g.tile;
-    const int bk = g.bk;
-    // the 3-channel clip padded to 4: patch-in-LDS kernel.  Only on request (tile code 6): measured on the MI355X it equals the
-    // generic kernel on D_V's first layer at 64 clips (0.250 ms) and loses below that -- its steps run at the MFMA rate, but all
-    // blocks finish together and their 64 x kt * 48 device-scope atomics each (~80 us) are not hidden behind other blocks' work
-    if (t == 6 && c4_wgrad_bf16_ok(g)) {                         // bf16 networks (y bf16 beside the fp32 clip): patch + y tile in LDS, bf16 MFMA
-        if (g.kt == 4) st = g.Wo == 32 ? launch_wgrad_c4_bf16<4, 32>(g, x, y, dw, s) : launch_wgrad_c4_bf16<4, 16>(g, x, y, dw, s);
-        else st = g.Wo == 32 ? launch_wgrad_c4_bf16<1, 32>(g, x, y, dw, s) : launch_wgrad_c4_bf16<1, 16>(g, x, y, dw, s);
-        return finish(st);
-    }
-    if (g.y16 && (t == 6 || t == 7 || t == 8 || t == 9 || t == 10)) return MCG_ERR_UNSUPPORTED;      // (the register-staged tiles only)
-    if (t == 6 && c4_wgrad_ok(g)) {
-        if (g.kt == 4) st = g.Wo == 32 ? launch_wgrad_c4<4, 32>(g, x, y, dw, s) : launch_wgrad_c4<4, 16>(g, x, y, dw, s);
-        else st = g.Wo == 32 ? launch_wgrad_c4<1, 32>(g, x, y, dw, s) : launch_wgrad_c4<1, 16>(g, x, y, dw, s);
-        return finish(st);
+    if (split) {
+        if ((t != 0 && t != 7 && t != 8 && t != 10) || !split_ok(g, SPLIT_PIX)) return MCG_ERR_UNSUPPORTED;
+        if (!t) t = 7;
+    } else {
+        // the 3-channel clip padded to 4: patch-in-LDS kernel.  Only on request (tile code 6): measured on the MI355X it equals the
+        // generic kernel on D_V's first layer at 64 clips (0.250 ms) and loses below that -- its steps run at the MFMA rate, but all
+        // blocks finish together and their 64 x kt * 48 device-scope atomics each (~80 us) are not hidden behind other blocks' work
+        if (t == 6 && c4_wgrad_ok(g)) {
+            if (g.y16) return with_kt_wo(g, [&](auto kt, auto wo) { return launch_wgrad_c4<kt, wo, true>(g, x, y, dw, s); });
+            return with_kt_wo(g, [&](auto kt, auto wo) { return launch_wgrad_c4<kt, wo, false>(g, x, y, dw, s); });
+        }
+        if (g.y16 && t >= 6) return MCG_ERR_UNSUPPORTED;         // (a bf16 y beside an fp32 x: the register-staged tiles only)
     }
     if (t == 6 || t == 9) return MCG_ERR_UNSUPPORTED;
-    if (t == 7 || t == 8 || t == 10) {                           // the LDS-DMA kernels: 128x256 (Co = 128) or 256x256; 10: 128x128, two blocks per CU
-        if ((g.prec != MCG_PREC_BF16_STORE && g.prec != MCG_PREC_F32) || g.Co < 128 || (g.Co & 63) || g.Ci < 64 || (g.Ci & (g.Ci - 1))) return MCG_ERR_UNSUPPORTED;
-        if (t == 10) {
-            if (g.prec == MCG_PREC_F32) return finish(launch_wgrad_v2<128, 128, 2, 0>(g, x, y, dw, s));
-            return finish(launch_wgrad_v2<128, 128, 2, 2>(g, x, y, dw, s));
-        }
-        if (g.prec == MCG_PREC_F32) {
-            if (g.Co == 128 || t == 7) st = launch_wgrad_v2<128, 256, 3, 0>(g, x, y, dw, s);
-            else st = launch_wgrad_v2<256, 256, 2, 0>(g, x, y, dw, s);
-        } else {
-            if (g.Co == 128 || t == 7) st = launch_wgrad_v2<128, 256, 3, 2>(g, x, y, dw, s);
-            else st = launch_wgrad_v2<256, 256, 2, 2>(g, x, y, dw, s);
-        }
-        return finish(st);
+    if (t == 7 || t == 8 || t == 10) {                           // the LDS-DMA kernels (wide layers)
+        if ((!split && g.prec != MCG_PREC_BF16_STORE && g.prec != MCG_PREC_F32) || g.Co < 128 || (g.Co & 63) || g.Ci < 64 || (g.Ci & (g.Ci - 1))) return MCG_ERR_UNSUPPORTED;
+        const Geom h = split ? split_geom(g, SPLIT_PIX) : g;
+        const int form = v2_form(g);
+        if (t == 10) return MCG_V2_FORMS(launch_wgrad_v2, 128, 128, 2, form, h, x, y, dw, s);                   // two blocks per CU
+        if (g.Co == 128 || t == 7) return MCG_V2_FORMS(launch_wgrad_v2, 128, 256, 3, form, h, x, y, dw, s);
+        return MCG_V2_FORMS(launch_wgrad_v2, 256, 256, 2, form, h, x, y, dw, s);
     }
-    if (!t) t = (g.Co <= 64 || Kf <= 64) ? 3 : 1;
-    const bool bk64 = bk ? bk == 64 : g.prec != MCG_PREC_F32;
-    if (g.y16) {                                                 // y bf16 in memory beside an fp32 x (the clip-side layers of bf16 networks)
-        if (bk64) MCG_TILES(launch_wgrad, t, 64, 3, g, x, y, dw, s); else MCG_TILES(launch_wgrad, t, 32, 3, g, x, y, dw, s);
-        return finish(st);
-    }
-    MCG_DISPATCH(launch_wgrad, t, bk64, g.prec, g, x, y, dw, s);
-    return finish(st);
+    if (!t) t = (g.Co <= 64 || g.taps * g.Ci <= 64) ? 3 : 1;
+    const bool bk64 = g.bk ? g.bk == 64 : g.prec != MCG_PREC_F32;
+    if (g.y16) return MCG_DEPTHS(launch_wgrad, t, bk64, 3, g, x, y, dw, s);      // y bf16 in memory beside an fp32 x (the clip-side layers of bf16 networks)
+    return MCG_DISPATCH(launch_wgrad, t, bk64, g.prec, g, x, y, dw, s);
 }
 
 // ---- fully-connected layers on the GEMM core (called by mcg_fc_fprop / mcg_fc_wgrad in small_ops.hip when the
 // output width is large enough to fill MFMA tiles; not part of the public header: hidden visibility, the shared library does
 // not export them) ----
 extern "C" __attribute__((visibility("hidden"))) int mcg_detail_fc_fprop_gemm(int M, int K, int N, const float* x, const float* w, const float* bias, float* y, void* stream) {
-    if ((K & 63) || (long long)M * K * 4 >= (1ll << 31) || (long long)N * K * 4 >= (1ll << 31)) return MCG_ERR_UNSUPPORTED;
+    if ((K & 63) || !fits((long long)M * K, 4) || !fits((long long)N * K, 4)) return MCG_ERR_UNSUPPORTED;
     constexpr int BM = 64, BN = 64, BK = 64;
     FcFpropP<BM, BN, BK> p;
     p.x = x; p.w = w; p.bias = bias; p.y = y; p.M = M; p.N = N; p.K = K;
     p.x_bytes = (u32)((long long)M * K * 4); p.w_bytes = (u32)((long long)N * K * 4);
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), ksteps = K / BK;
-    int splits = (512 + tiles - 1) / tiles;
-    if (splits > ksteps / 4) splits = ksteps / 4;
-    if (splits < 1) splits = 1;
-    p.kchunk = ((ksteps + splits - 1) / splits) * BK;
-    splits = (K + p.kchunk - 1) / p.kchunk;
+    const int gx = (M + BM - 1) / BM, gy = (N + BN - 1) / BN;
+    const Split k = plan_ksplit(K, BK, (512 + gx * gy - 1) / (gx * gy), 4);      // ~2 blocks per CU, >= 4 K-steps per block
+    p.kchunk = k.chunk;
     hipStream_t s = (hipStream_t)stream;
-    if (splits > 1 && hipMemsetAsync(y, 0, (size_t)M * N * sizeof(float), s) != hipSuccess) return MCG_ERR_LAUNCH;
-    dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, splits);
-    hipLaunchKernelGGL((gemm_kernel<FcFpropP<BM, BN, BK>, BM, BN, BK>), grid, dim3(NTHREADS), 0, s, p);
-    return launch_status();
+    if (k.n > 1 && clear_output(y, (long long)M * N, s) != MCG_OK) return MCG_ERR_LAUNCH;
+    return launch<gemm_kernel<FcFpropP<BM, BN, BK>, BM, BN, BK>>(dim3(gx, gy, k.n), dim3(NTHREADS), 0, s, p);
 }
 
 extern "C" __attribute__((visibility("hidden"))) int mcg_detail_fc_wgrad_gemm(int M, int K, int N, const float* x, const float* y, float* dw, void* stream) {
-    if ((K & 3) || (N & 3) || (long long)M * K * 4 >= (1ll << 31) || (long long)M * N * 4 >= (1ll << 31)) return MCG_ERR_UNSUPPORTED;
+    if ((K & 3) || (N & 3) || !fits((long long)M * K, 4) || !fits((long long)M * N, 4)) return MCG_ERR_UNSUPPORTED;
     constexpr int BM = 64, BN = 64, BK = 32;
     FcWgradP<BM, BN, BK> p;
     p.x = x; p.y = y; p.dw = dw; p.M = M; p.N = N; p.K = K;
     p.x_bytes = (u32)((long long)M * K * 4); p.y_bytes = (u32)((long long)M * N * 4);
-    const int tiles = ((N + BM - 1) / BM) * ((K + BN - 1) / BN), ksteps = (M + BK - 1) / BK;
-    int splits = (1024 + tiles - 1) / tiles;
-    if (splits > ksteps / 4) splits = ksteps / 4;
-    if (splits < 1) splits = 1;
-    p.chunk = ((ksteps + splits - 1) / splits) * BK;
-    splits = (M + p.chunk - 1) / p.chunk;
-    dim3 grid((N + BM - 1) / BM, (K + BN - 1) / BN, splits);
-    hipLaunchKernelGGL((gemm_kernel<FcWgradP<BM, BN, BK>, BM, BN, BK>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, p);
-    return launch_status();
+    const int gx = (N + BM - 1) / BM, gy = (K + BN - 1) / BN;
+    const Split k = plan_pixsplit(M, BK, 1024, gx * gy, 4);
+    p.chunk = k.chunk;
+    return launch<gemm_kernel<FcWgradP<BM, BN, BK>, BM, BN, BK>>(dim3(gx, gy, k.n), dim3(NTHREADS), 0, (hipStream_t)stream, p);
 }
 #endif
