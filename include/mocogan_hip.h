@@ -121,7 +121,8 @@ typedef struct mcg_conv_geom {
 /* ABI revision of this header: a host built against another revision must not call in (argument lists differ).
  * 3 = round 3 (mcg_randint, bf16 tensors in the synchronised-BatchNorm backward; round 2 changed mcg_bn_act_fwd / mcg_bn_act_bwd / mcg_adam_wd / mcg_conv_geom);
  * 6 = round 5 (mcg_split_planes_multi); 7 = round 6 (mcg_pack_clip_u8; nothing else changed);
- * 8 = the sampling path (mcg_bn_fold_deconv, mcg_clip_to_u8, MCG_ACT_RELU in mcg_conv_dgrad / mcg_conv_dgrad_ex; no argument list changed). */
+ * 8 = the sampling path (mcg_bn_fold_deconv, mcg_clip_to_u8, MCG_ACT_RELU in mcg_conv_dgrad / mcg_conv_dgrad_ex; no argument list changed);
+ *     still 8 with the averaged generator (mcg_adam_wd_ema, mcg_ema_multi added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -375,6 +376,23 @@ int mcg_loss_gen(int N, int C, const float* y_fake_i, const float* y_fake_v, con
 int mcg_adam_wd(int64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta1,
                 double beta2, double eps, double wd, double grad_scale, uint16_t* p_bf16, void* stream);
 /* (p_bf16, may be NULL: a bf16 copy of the updated parameters, the weight operand of MCG_PREC_BF16_STORE launches) */
+
+/* mcg_adam_wd plus an exponential moving average of the parameters in the same pass (no reference counterpart: the reference
+ * samples the last iterate of train.py:93-101's optimizers): after the update above, ema <- ema + ema_rate * (p - ema) with the
+ * parameter just written, as one subtraction and one fma; ema_rate == 1 stores p itself, bit for bit.  p, m, v and p_bf16 come
+ * out bit for bit as mcg_adam_wd writes them.  ema_rate = 1 - decay in (0, 1], formed by the caller in double (a warm-up
+ * schedule lives there, like lr_t).  ema [n] must not overlap p, g, m or v.  Pointers need 4-byte alignment only (p_bf16: 2);
+ * when all are 16-byte aligned (p_bf16: 8) the pass uses 16-byte accesses.  MCG_ERR_BAD_ARG: a null pointer (p_bf16 may be
+ * NULL), n <= 0, ema_rate outside (0, 1], ema overlapping p / g / m / v. */
+int mcg_adam_wd_ema(int64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta1,
+                    double beta2, double eps, double wd, double grad_scale, uint16_t* p_bf16, float* ema,
+                    float ema_rate, void* stream);
+/* The same average for tensors no optimizer writes -- the generator's BatchNorm running statistics (model/net.py:50-53), so
+ * that the averaged generator is a complete test-mode network: dst <- dst + ema_rate * (src - dst) (ema_rate == 1: dst = src)
+ * over nseg <= 32 segments of any n >= 1 in ONE launch.  `segs` is a HOST array; 4-byte alignment suffices.
+ * MCG_ERR_BAD_ARG: a null pointer, nseg <= 0 or > 32, an n <= 0, ema_rate outside (0, 1]. */
+typedef struct mcg_ema_seg { const float* src; float* dst; int64_t n; } mcg_ema_seg;
+int mcg_ema_multi(int nseg, const mcg_ema_seg* segs, float ema_rate, void* stream);
 
 /* out[i] = sigma * N(0,1), the same Philox stream mcg_bn_act_fwd / mcg_pack_clip draw from. */
 int mcg_randn(int64_t n, float sigma, uint64_t seed, uint64_t stream_id, float* out, void* stream);

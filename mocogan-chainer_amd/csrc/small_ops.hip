@@ -1228,20 +1228,80 @@ __global__ __launch_bounds__(NT) void loss_gen_kernel(int N, int C, const float*
 // ------------------------------------------------------------------------------------------
 // Adam + weight decay, randn
 // ------------------------------------------------------------------------------------------
+struct AdamK { float lr, b1c, b2c, eps, wd, gscale; };
+
+// One parameter's update: the ONE statement of the arithmetic, with every fused multiply-add written out.  Left to the compiler's
+// contraction, g * gscale + wd * p became fma(wd, p, g * gscale) in the scalar form of the kernel below and fma(gscale, g, wd * p)
+// in its 16-byte form: one element in some ten thousand then differs in the last bit.  What is spelled here is what the scalar
+// kernel has always computed, so the forms (scalar / 16-byte accesses, with / without the average) agree bit for bit.
+__device__ __forceinline__ float adam_wd_elem(float pv, float g, float& mv, float& vv, const AdamK& k) {
+    const float gg = fmaf(k.wd, pv, g * k.gscale);   // gscale = 1 / world: the all-reduced SUM becomes the mean here (x 1.0f is exact)
+    mv = fmaf(k.b1c, gg - mv, mv);
+    vv = fmaf(k.b2c, fmaf(gg, gg, -vv), vv);
+    return pv - k.lr * mv / (sqrtf(vv) + k.eps);
+}
+
+// e <- e + r (x - e): one subtraction, one fma (the form of m and v above: x == e is a fixed point).  r == 1 takes x itself --
+// e + (x - e) is not x in floating point -- so a decay of 0 tracks the parameters exactly.
+__device__ __forceinline__ float ema_elem(float e, float x, float r, bool take_x) { return take_x ? x : fmaf(r, x - e, e); }
+
+// EMA: the exponential moving average `ema` of the parameters follows in the same pass (the fresh parameter is in a register).
+// V = 4: 16-byte accesses, for pointers that are all 16-byte aligned (p16: 8-byte); the n % 4 last elements are done one by one
+// by the first threads of block 0.  V = 1: any 4-byte aligned pointers.
+template <bool EMA, int V>
 __global__ __launch_bounds__(NT) void adam_wd_kernel(long long n, float* __restrict__ p, const float* __restrict__ g,
-                                                     float* __restrict__ m, float* __restrict__ v, float lr, float b1c,
-                                                     float b2c, float eps, float wd, float gscale, __bf16* __restrict__ p16) {
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
-        float pv = p[i];
-        float gg = g[i] * gscale + wd * pv;      // gscale = 1 / world: the all-reduced SUM becomes the mean here (x 1.0f is exact)
+                                                     float* __restrict__ m, float* __restrict__ v, AdamK k, __bf16* __restrict__ p16,
+                                                     float* __restrict__ ema, float r) {
+    const bool take_x = r == 1.0f;
+    const long long stride = (long long)gridDim.x * NT, first = (long long)blockIdx.x * NT + threadIdx.x;
+    auto one = [&](long long i) {
         float mv = m[i], vv = v[i];
-        mv += b1c * (gg - mv);
-        vv += b2c * (gg * gg - vv);
+        const float pv = adam_wd_elem(p[i], g[i], mv, vv, k);
         m[i] = mv; v[i] = vv;
-        pv -= lr * mv / (sqrtf(vv) + eps);
         p[i] = pv;
         if (p16) p16[i] = (__bf16)pv;             // the GEMMs' bf16 copy of the master weights (MCG_PREC_BF16_STORE)
+        if (EMA) ema[i] = ema_elem(ema[i], pv, r, take_x);
+    };
+    if constexpr (V == 1) {
+        for (long long i = first; i < n; i += stride) one(i);
+        return;
     }
+    const long long n4 = n >> 2;
+    for (long long i = first; i < n4; i += stride) {
+        f32x4 pv = reinterpret_cast<const f32x4*>(p)[i], mv = reinterpret_cast<const f32x4*>(m)[i], vv = reinterpret_cast<const f32x4*>(v)[i];
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 ev;
+        if (EMA) ev = reinterpret_cast<const f32x4*>(ema)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float mj = mv[j], vj = vv[j];
+            pv[j] = adam_wd_elem(pv[j], gv[j], mj, vj, k);
+            mv[j] = mj; vv[j] = vj;
+            if (EMA) ev[j] = ema_elem(ev[j], pv[j], r, take_x);
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mv; reinterpret_cast<f32x4*>(v)[i] = vv;
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        if (p16) reinterpret_cast<bf16x4_t*>(p16)[i] = __builtin_convertvector(pv, bf16x4_t);
+        if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
+    }
+    const long long tail = (n4 << 2) + first;      // (first < 3 in block 0 only)
+    if (tail < n) one(tail);
+}
+
+// mcg_ema_multi: dst <- dst + r (src - dst) over up to 32 segments of any length in one launch (the generator's eight running
+// statistics).  A block belongs to one segment, found as split_planes_multi_kernel below finds it; 4-byte accesses.
+constexpr int MAX_EMA_SEGS = 32, EMA_SEG_BLOCKS = 64;
+struct EmaSegs { const float* src[MAX_EMA_SEGS]; float* dst[MAX_EMA_SEGS]; long long n[MAX_EMA_SEGS]; int blk_end[MAX_EMA_SEGS]; int nseg; };
+__global__ __launch_bounds__(NT) void ema_multi_kernel(EmaSegs sg, float r) {
+    int s = 0;
+    while (s + 1 < sg.nseg && (int)blockIdx.x >= sg.blk_end[s]) ++s;                    // (block-uniform)
+    const int b0 = s ? sg.blk_end[s - 1] : 0, nb = sg.blk_end[s] - b0;
+    const float* src = sg.src[s];
+    float* dst = sg.dst[s];
+    const long long n = sg.n[s];
+    const bool take_x = r == 1.0f;
+    for (long long i = (long long)((int)blockIdx.x - b0) * NT + threadIdx.x; i < n; i += (long long)nb * NT)
+        dst[i] = ema_elem(dst[i], src[i], r, take_x);
 }
 
 __global__ __launch_bounds__(NT) void randn_kernel(long long n, float sigma, uint64_t seed, uint64_t stream_id, float* __restrict__ out) {
@@ -1684,12 +1744,56 @@ extern "C" int mcg_loss_gen(int N, int C, const float* y_fake_i, const float* y_
     return launch_status();
 }
 
+namespace {
+AdamK adam_consts(double lr_t, double beta1, double beta2, double eps, double wd, double grad_scale) {
+    // hyper-parameters arrive as doubles so that (1 - beta) is rounded to fp32 once, like Chainer's python-float arithmetic
+    return {(float)lr_t, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)wd, (float)grad_scale};
+}
+bool ema_rate_ok(float r) { return r > 0.0f && r <= 1.0f; }                              // (false for a NaN)
+bool overlaps(const float* a, const float* b, int64_t n) {                               // [a, a + n) and [b, b + n)
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+    return x < y + len && y < x + len;
+}
+}  // namespace
+
 extern "C" int mcg_adam_wd(int64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta1, double beta2, double eps,
                            double wd, double grad_scale, uint16_t* p_bf16, void* stream) {
     if (!p || !g || !m || !v || n <= 0) return MCG_ERR_BAD_ARG;
-    // hyper-parameters arrive as doubles so that (1 - beta) is rounded to fp32 once, like Chainer's python-float arithmetic
-    hipLaunchKernelGGL(adam_wd_kernel, dim3(ew_grid(n)), dim3(NT), 0, (hipStream_t)stream, (long long)n, p, g, m, v, (float)lr_t,
-                       (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)wd, (float)grad_scale, (__bf16*)p_bf16);
+    hipLaunchKernelGGL((adam_wd_kernel<false, 1>), dim3(ew_grid(n)), dim3(NT), 0, (hipStream_t)stream, (long long)n, p, g, m, v,
+                       adam_consts(lr_t, beta1, beta2, eps, wd, grad_scale), (__bf16*)p_bf16, (float*)nullptr, 0.0f);
+    return launch_status();
+}
+
+extern "C" int mcg_adam_wd_ema(int64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta1, double beta2, double eps,
+                               double wd, double grad_scale, uint16_t* p_bf16, float* ema, float ema_rate, void* stream) {
+    if (!p || !g || !m || !v || !ema || n <= 0 || !ema_rate_ok(ema_rate)) return MCG_ERR_BAD_ARG;
+    if (overlaps(ema, p, n) || overlaps(ema, g, n) || overlaps(ema, m, n) || overlaps(ema, v, n)) return MCG_ERR_BAD_ARG;
+    const AdamK k = adam_consts(lr_t, beta1, beta2, eps, wd, grad_scale);
+    // the ABI promises 4-byte alignment only: the 16-byte form needs every pointer on a 16-byte boundary (the bf16 copy: 8)
+    const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | ((uintptr_t)p_bf16 << 1);
+    if ((bits & 15) == 0 && n >= 4)
+        hipLaunchKernelGGL((adam_wd_kernel<true, 4>), dim3(ew_grid(n / 4)), dim3(NT), 0, (hipStream_t)stream, (long long)n, p, g, m, v, k,
+                           (__bf16*)p_bf16, ema, ema_rate);
+    else
+        hipLaunchKernelGGL((adam_wd_kernel<true, 1>), dim3(ew_grid(n)), dim3(NT), 0, (hipStream_t)stream, (long long)n, p, g, m, v, k,
+                           (__bf16*)p_bf16, ema, ema_rate);
+    return launch_status();
+}
+
+extern "C" int mcg_ema_multi(int nseg, const mcg_ema_seg* segs, float ema_rate, void* stream) {
+    if (!segs || nseg <= 0 || nseg > MAX_EMA_SEGS || !ema_rate_ok(ema_rate)) return MCG_ERR_BAD_ARG;
+    EmaSegs sg;
+    int blocks = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const mcg_ema_seg& q = segs[s];
+        if (!q.src || !q.dst || q.n <= 0) return MCG_ERR_BAD_ARG;
+        long long nb = (q.n + NT - 1) / NT;
+        if (nb > EMA_SEG_BLOCKS) nb = EMA_SEG_BLOCKS;                 // (the rest of a long segment is grid-strided)
+        blocks += (int)nb;
+        sg.src[s] = q.src; sg.dst[s] = q.dst; sg.n[s] = q.n; sg.blk_end[s] = blocks;
+    }
+    sg.nseg = nseg;
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, sg, ema_rate);
     return launch_status();
 }
 

@@ -86,6 +86,8 @@ SIGNATURES = {
     "mcg_loss_dis": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mcg_loss_gen": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mcg_adam_wd": (_I, [_I64, _P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _P, _P]),
+    "mcg_adam_wd_ema": (_I, [_I64, _P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _P, _P, _F, _P]),
+    "mcg_ema_multi": (_I, [_I, _P, _F, _P]),
     "mcg_randn": (_I, [_I64, _F, _U64, _U64, _P, _P]),
     "mcg_randint": (_I, [_I64, _I, _U64, _U64, _P, _P]),
     "mcg_split_planes": (_I, [_I64, _I64, _P, _P, _P]),
@@ -887,6 +889,31 @@ def adam_wd(p, g, m, v, lr_t, beta1, beta2, eps, wd, grad_scale=1.0, p16=None):
     """p16: optional bf16 buffer of p's size that receives a copy of the updated parameters"""
     _check(load().mcg_adam_wd(p.numel(), _p(_dense(p)), _p(_dense(g)), _p(_dense(m)), _p(_dense(v)), lr_t, beta1, beta2, eps, wd,
                               grad_scale, _p(_dense(p16), torch.bfloat16), _stream()), "mcg_adam_wd")
+
+
+def adam_wd_ema(p, g, m, v, lr_t, beta1, beta2, eps, wd, ema, ema_rate, grad_scale=1.0, p16=None):
+    """adam_wd, and in the same launch ema <- ema + ema_rate * (p - ema) with the parameter just written (ema_rate == 1: ema = p)"""
+    for name, t in (('g', g), ('m', m), ('v', v), ('ema', ema), ('p16', p16)):
+        if t is not None and t.numel() != p.numel():
+            raise McgError("%s has %d elements, p has %d" % (name, t.numel(), p.numel()))
+    _check(load().mcg_adam_wd_ema(p.numel(), _p(_dense(p)), _p(_dense(g)), _p(_dense(m)), _p(_dense(v)), lr_t, beta1, beta2, eps, wd,
+                                  grad_scale, _p(_dense(p16), torch.bfloat16), _p(_dense(ema)), ema_rate, _stream()), "mcg_adam_wd_ema")
+
+
+class EmaSeg(C.Structure):                                         # mcg_ema_seg
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n", C.c_int64)]
+
+
+def ema_multi(pairs, rate):
+    """pairs: [(fp32 source tensor, fp32 average of the same size), ...], at most 32 -- dst <- dst + rate * (src - dst) for every
+    pair in ONE launch (the generator's running statistics right after its Adam update)"""
+    segs = (EmaSeg * len(pairs))()
+    for q, (src, dst) in zip(segs, pairs):
+        if src.numel() != dst.numel():
+            raise McgError("an average and its source differ in size")
+        _p(_dense(src)), _p(_dense(dst))                           # (device, dtype and density are checked here)
+        q.src, q.dst, q.n = src.data_ptr(), dst.data_ptr(), src.numel()
+    _check(load().mcg_ema_multi(len(pairs), C.cast(segs, C.c_void_p), rate, _stream()), "mcg_ema_multi")
 
 
 def randint(out, modulus, seed, stream_id):

@@ -66,6 +66,7 @@ class FlatParams:
         self.v = torch.zeros_like(self.p)
         self.p16 = None                 # bf16 copy of p (same offsets): the weight operand of the bf16-storage GEMMs
         self.version = 0                # bumped by whatever writes p (touch): derived copies (the split filters of 'f32x3') follow it
+        self.e = None                   # exponential moving average of p (GenNet.enable_ema): written by the Adam launch, read through EmaParams
 
     def touch(self):
         self.version += 1
@@ -92,6 +93,28 @@ class FlatParams:
     def view(self, buf, name):
         """buf in 'p' (parameters), 'g' (gradients), 'm' / 'v' (Adam moments)."""
         return self._view(getattr(self, buf), name)
+
+
+class EmaParams(FlatParams):
+    """The averaged parameters as a network reads them: the live FlatParams' layout over its `e` buffer -- the very tensor the
+    Adam launch writes, no copy that could go stale -- and nothing an optimizer needs (no gradient, no moments)."""
+
+    def __init__(self, live):
+        self.names, self.offsets, self.shapes, self.size = live.names, live.offsets, live.shapes, live.size
+        self.p = live.e
+        self.g = self.m = self.v = self.e = None
+        self.p16 = None                 # bf16 copy of the average: nothing keeps it current, so it follows `version` on demand
+        self._v16 = -1
+        self.version = 0                # bumped by whatever writes the average (step.adam_update, a load, a move)
+
+    def refresh16(self):
+        super().refresh16()
+        self._v16 = self.version
+
+    def param16(self, name):
+        if self._v16 != self.version:
+            self.refresh16()
+        return super().param16(name)
 
 
 def _np_to(t, device):
@@ -159,6 +182,8 @@ class _Net:
         self.precision = precision
         if precision == 'bf16':
             self.fp.refresh16()
+        if self.ema is not None:
+            self.ema.set_precision(precision)
 
     @property
     def gemm_precision(self):
@@ -289,6 +314,7 @@ class _Net:
     # both only read the layer's output gradient, so they may run side by side: the blocks of one fill the
     # CUs the other leaves idle in its last, partial round of tiles.  None = everything on the caller's stream.
     wgrad_stream = None
+    ema = None                     # GenNet.enable_ema: the averaged network (EmaGenNet)
     sync_bn = None                 # step.GradExchange when BatchNorm is synchronised over the data-parallel ranks
 
     # (round 4: queueing a layer's weight gradient behind its input-gradient GEMM was measured slower, profiles/NOTES.md)
@@ -492,6 +518,9 @@ class _Net:
         self.ws = self.ws.to(device)
         self.device = device
         self._reset_derived()
+        if self.ema is not None:
+            self.fp.e = self.fp.e.to(device)
+            self.ema._moved(self)
         return self
 
     def _bn_keys(self, name, c):
@@ -830,6 +859,19 @@ class GenNet(_Net):
 
     def __init__(self, dim_zc=50, dim_zm=10, dim_zl=0, out_channels=3, n_filters=64, video_len=16,
                  device='cuda', seed=None):
+        self._alloc(self._shape(dim_zc, dim_zm, dim_zl, out_channels, n_filters, video_len), device)
+        self.running, self.bn_count = {}, {}
+        for l in (1, 2, 3, 4):
+            c = self.chans[l]
+            self.running['bn%d/avg_mean' % l] = torch.zeros(c, device=self.device)
+            self.running['bn%d/avg_var' % l] = torch.ones(c, device=self.device)
+            self.bn_count['bn%d' % l] = 0
+            self._init_bn('bn%d' % l)
+        if seed is not None:
+            self.init_weights(np.random.RandomState(seed))
+
+    def _shape(self, dim_zc, dim_zm, dim_zl, out_channels, n_filters, video_len):
+        """everything that follows from the constructor's sizes (attributes, Chainer keys and shapes) -> the flat buffer's specs"""
         self.dim_zc, self.dim_zm, self.dim_zl = dim_zc, dim_zm, dim_zl
         self.out_channels, self.n_filters, self.video_len = out_channels, n_filters, video_len
         self.n_hidden = dim_zc + dim_zm
@@ -855,16 +897,7 @@ class GenNet(_Net):
             self.ref_shapes.update(self._bn_keys('bn%d' % l, self.chans[l]))
             specs.append(('bn%d/gamma' % l, (self.chans[l],)))
             specs.append(('bn%d/beta' % l, (self.chans[l],)))
-        self._alloc(specs, device)
-        self.running, self.bn_count = {}, {}
-        for l in (1, 2, 3, 4):
-            c = self.chans[l]
-            self.running['bn%d/avg_mean' % l] = torch.zeros(c, device=self.device)
-            self.running['bn%d/avg_var' % l] = torch.ones(c, device=self.device)
-            self.bn_count['bn%d' % l] = 0
-            self._init_bn('bn%d' % l)
-        if seed is not None:
-            self.init_weights(np.random.RandomState(seed))
+        return specs
 
     def init_weights(self, rng):
         """GlorotNormal deconv weights (model/net.py:35), LeCunNormal GRU Linear weights (Chainer
@@ -1174,6 +1207,22 @@ class GenNet(_Net):
         u8 = self._sview(2, ((m, T) if order == 'NT' else (T, m)) + (IMG, IMG, self.out_channels), torch.uint8)
         return self.sample(m, d, video_len=video_len, out='uint8', order=order, u8_out=u8)
 
+    # ---- averaged generator -----------------------------------------------------------------
+    def enable_ema(self, decay):
+        """Keep an exponential moving average of this generator's parameters and running statistics (step.adam_update advances
+        it; decay in [0, 1), step.ema_rate is the schedule).  The average starts from the live values, with no update counted.
+        Returns the averaged network: GenNet's inference surface over the averaged buffers.  Calling it again keeps the
+        average and sets the decay."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError('the decay of the averaged generator must lie in [0, 1), got %r' % decay)
+        if self.ema is None:
+            self.fp.e = torch.empty_like(self.fp.p)
+            self.ema = EmaGenNet(self)
+            self.ema.reset_from(self)
+        self.ema.decay = decay
+        return self.ema
+
     # ---- backward --------------------------------------------------------------------------
     def grad_bucket_late(self):
         """(start, end) of the flat-gradient range dc2/W .. dc5/b: 85 % of the bytes, final once layer 2's weight
@@ -1234,3 +1283,75 @@ class GenNet(_Net):
         d = saved['draw']
         hl.gru_seq_bwd(n, T, dz, dl, dc, fp.param('g0'), d['e'], d['labels'], saved['gru'], gz, fp.grad('g0'))
         self._wgrad_join()
+
+
+class EmaGenNet(GenNet):
+    """The averaged generator: GenNet's test-mode surface (sample, sample_many, forward without statistics, reference-layout
+    export / import) over the exponential moving average of a live GenNet's parameters (fp.p IS the live net's fp.e, which the
+    Adam launch writes) and of its BatchNorm running statistics.  It holds no gradient or moment buffers and cannot train.
+    `decay` and `k` (updates done so far) are the state of step.ema_rate's schedule."""
+
+    def __init__(self, live):
+        self._shape(live.dim_zc, live.dim_zm, live.dim_zl, live.out_channels, live.n_filters, live.video_len)
+        self.device = live.device
+        self.live = live
+        self.fp = EmaParams(live.fp)
+        self.running = {k: torch.empty_like(v) for k, v in live.running.items()}
+        self.bn_count = dict(live.bn_count)
+        self.decay, self.k = 0.0, 0
+        self.t = 0
+        self.ws = None                                         # (BatchNorm workspace: train mode only)
+        self._reset_derived()
+        self.set_precision(live.precision)
+
+    def reset_from(self, live):
+        """the average := the live values, no update counted (enabling; resuming a snapshot that holds no average)"""
+        self.fp.p.copy_(live.fp.p)
+        for k, v in live.running.items():
+            self.running[k].copy_(v)
+        self.written(live)
+        self.k = 0
+
+    def written(self, live):
+        """the buffers have been written (an update, a reset, a broadcast): what is derived from them follows"""
+        self.bn_count = dict(live.bn_count)                     # ('/N' of the exported BatchNorm links: the live net's)
+        self.fp.touch()
+
+    def _moved(self, live):
+        """the live net has moved its buffers (fp.e among them) to another device"""
+        self.device = live.device
+        self.fp.p = live.fp.e
+        self.fp.p16 = None
+        self.fp.touch()
+        self.running = {k: v.to(self.device) for k, v in self.running.items()}
+        self._reset_derived()
+
+    def to(self, device):
+        self.live.to(device)                                   # (the average lives beside the parameters it follows)
+        return self
+
+    def enable_ema(self, decay):
+        raise hl.McgError("the averaged generator has no average of its own")
+
+    def forward(self, n, draw, update_stats=False):
+        if config.train or update_stats:
+            raise hl.McgError("the averaged generator is a test-mode network (config.train = False): it has no batch statistics to update")
+        return super().forward(n, draw, False)
+
+    def _cannot_train(self):
+        raise hl.McgError("the averaged generator cannot train: it holds no gradients and no optimizer state")
+
+    def backward(self, saved, gx_clip, on_late_bucket=None):
+        self._cannot_train()
+
+    def zero_grad(self):
+        self._cannot_train()
+
+    def export_reference_grads(self):
+        self._cannot_train()
+
+    def export_adam_state(self):
+        self._cannot_train()
+
+    def load_adam_state(self, state):
+        self._cannot_train()

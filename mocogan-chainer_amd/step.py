@@ -49,13 +49,33 @@ class AdamHyper:
         return self.alpha * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
 
 
+def ema_rate(decay, k):
+    """r_k = 1 - d_k of the averaged generator's k-th update (k = 0, 1, ...: updates already done): d_k = min(decay, (1 + k) / (10 + k)),
+    a warm-up that lets the average forget its starting point (rates 0.9, 0.82, 0.75, ... until the decay takes over).  In double,
+    like AdamHyper.lr; the kernels take it as a float.  No reference counterpart: the reference samples the last iterate."""
+    if not 0.0 <= decay < 1.0:
+        raise ValueError('the decay of the averaged generator must lie in [0, 1), got %r' % (decay,))
+    return 1.0 - min(float(decay), (1.0 + k) / (10.0 + k))
+
+
 def adam_update(net, hyper, grad_scale=1.0):
     """optimizer.update() tail: hooks, t += 1, per-parameter Adam -- one launch over the flat buffers.
-    grad_scale: 1 / world under data parallelism (the flat gradient then holds the SUM over the ranks)."""
+    grad_scale: 1 / world under data parallelism (the flat gradient then holds the SUM over the ranks).
+    A net with an averaged twin (nets.GenNet.enable_ema): the same launch advances the average of the parameters (fp.e), one more
+    launch behind it on the same stream the average of the running statistics."""
     net.t += 1
     fp = net.fp
-    hl.adam_wd(fp.p, fp.g, fp.m, fp.v, hyper.lr(net.t), hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay, grad_scale,
-               p16=fp.p16 if net.precision == 'bf16' else None)
+    ema = net.ema
+    if ema is None:
+        hl.adam_wd(fp.p, fp.g, fp.m, fp.v, hyper.lr(net.t), hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay, grad_scale,
+                   p16=fp.p16 if net.precision == 'bf16' else None)
+    else:
+        r = ema_rate(ema.decay, ema.k)
+        hl.adam_wd_ema(fp.p, fp.g, fp.m, fp.v, hyper.lr(net.t), hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay, fp.e, r, grad_scale,
+                       p16=fp.p16 if net.precision == 'bf16' else None)
+        hl.ema_multi([(net.running[key], ema.running[key]) for key in sorted(net.running)], r)
+        ema.k += 1
+        ema.written(net)
     fp.touch()
     net.refresh_wsplits()                                         # ('f32x3': the split forms of the filters follow in one launch)
 
@@ -102,18 +122,59 @@ class GradExchange:
         for t in tensors:
             self.dist.broadcast(t, src=src, group=self.group)
 
+    def broadcast_replica(self, net, src=0):
+        """rank src's copy of everything a replica of `net` holds (replica_tensors, replica_counters) replaces everyone's"""
+        if not self.active:
+            return
+        self.broadcast_params(replica_tensors(net), src)
+        cnt = torch.tensor(replica_counters(net), dtype=torch.int64, device=net.fp.p.device)
+        self.broadcast_params([cnt], src)
+        set_replica_counters(net, cnt.tolist())
+
+
+def replica_tensors(net):
+    """What makes two replicas of a network equal, as the tensors a data-parallel run broadcasts after construction / resume:
+    parameters, Adam moments, running statistics -- and, with an averaged twin, its parameters and running statistics."""
+    tensors = [net.fp.p, net.fp.m, net.fp.v] + list(net.running.values())
+    if net.ema is not None:
+        tensors += [net.fp.e] + list(net.ema.running.values())
+    return tensors
+
+
+def replica_counters(net):
+    """... and as integers: the Adam step counter (it sets lr_t), the BatchNorm call counts, the averaged twin's update count"""
+    return [net.t] + [net.bn_count[k] for k in sorted(net.bn_count)] + ([net.ema.k] if net.ema is not None else [])
+
+
+def set_replica_counters(net, values):
+    """replica_counters' list back into the net; what is derived from the tensors that arrived with it is rebuilt"""
+    names = sorted(net.bn_count)
+    net.t = int(values[0])
+    for k, v in zip(names, values[1:]):
+        net.bn_count[k] = int(v)
+    net.fp.touch()
+    if net.precision == 'bf16':
+        net.fp.refresh16()
+    if net.ema is not None:
+        net.ema.written(net)
+        net.ema.k = int(values[1 + len(names)])
+
 
 class TrainStep:
     """Holds the three networks, their Adam hyper-parameters and runs update_core on device data."""
 
     def __init__(self, model, gen, dis_i, dis_v, hyper=None, exchange=None, seed=0, rank=0, precision=None, overlap=False, sync_bn=False,
-                 input_ready_early=False):
+                 input_ready_early=False, ema_decay=None):
         assert model in ('normal', 'cgan', 'infogan')
         self.model, self.gen, self.dis_i, self.dis_v = model, gen, dis_i, dis_v
         if precision is not None:                                 # 'f32' | 'bf16': MFMA operand type of every conv GEMM
             assert precision in ('f32', 'bf16', 'f32x3')
             for net in (gen, dis_i, dis_v):
                 net.set_precision(precision)
+        # ema_decay: None = off (nothing allocated, the launches of before); D in [0, 1): the generator keeps an exponential moving
+        # average of its parameters and running statistics (gen.ema; ema_rate is the schedule), advanced by its Adam launch
+        if ema_decay is not None:
+            gen.enable_ema(ema_decay)
         self.hyper = hyper or {'image_gen': AdamHyper(), 'image_dis': AdamHyper(), 'video_dis': AdamHyper()}
         self.exchange = exchange
         # sync_bn (opt-in, SURVEY 8e): BatchNorm statistics and their backward sums are all-reduced over the ranks, i.e.

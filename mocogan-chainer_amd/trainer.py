@@ -573,6 +573,11 @@ class Trainer:
             for k in st['m']:
                 d['updater/optimizer:%s/%s/m' % (name, k)] = st['m'][k]
                 d['updater/optimizer:%s/%s/v' % (name, k)] = st['v'][k]
+            ema = getattr(link.impl, 'ema', None)                   # the averaged generator (no Chainer counterpart): its own key family
+            if ema is not None:
+                for k, v in ema.export_reference_params().items():
+                    d['updater/ema:%s/%s' % (name, k)] = v
+                d['updater/ema:%s/k' % name] = np.asarray(ema.k)
         return d
 
     def load_state(self, d):
@@ -605,6 +610,14 @@ class Trainer:
             keys = link.impl.trainable_keys()
             link.impl.load_adam_state({'t': int(d[opre + 't']), 'm': {k: d[opre + k + '/m'] for k in keys},
                                        'v': {k: d[opre + k + '/v'] for k in keys}})
+            ema = getattr(link.impl, 'ema', None)
+            if ema is not None:
+                epre = 'updater/ema:%s/' % name
+                if epre + 'k' in d:
+                    ema.load_reference_params({k[len(epre):]: v for k, v in d.items() if k.startswith(epre) and k != epre + 'k'})
+                    ema.k = int(d[epre + 'k'])
+                else:                                               # a snapshot of a run without averaging: start from what it holds
+                    ema.reset_from(link.impl)
 
 
 class extensions:

@@ -54,14 +54,32 @@ class _Link:
 
 class ImageGenerator(_Link):
     def __init__(self, dim_zc=50, dim_zm=10, dim_zl=0, out_channels=3, n_filters=64, video_len=16, device=None):
+        self._describe(dim_zc, dim_zm, dim_zl, out_channels, n_filters, video_len)
+        self.impl = _nets.GenNet(dim_zc, dim_zm, dim_zl, out_channels, n_filters, video_len,
+                                 device=device or _default_device())
+        self.impl.init_weights(np.random)          # Chainer initialises at construction from np.random
+
+    def _describe(self, dim_zc, dim_zm, dim_zl, out_channels, n_filters, video_len):
+        """the reference's attributes (model/net.py:20-30), shared with the averaged generator's link"""
         self.dim_zc, self.dim_zm, self.dim_zl = dim_zc, dim_zm, dim_zl
         self.out_channels, self.n_filters, self.video_len = out_channels, n_filters, video_len
         self.n_hidden = dim_zc + dim_zm
         self.use_label = dim_zl != 0
-        self.name = self.__class__.__name__
-        self.impl = _nets.GenNet(dim_zc, dim_zm, dim_zl, out_channels, n_filters, video_len,
-                                 device=device or _default_device())
-        self.impl.init_weights(np.random)          # Chainer initialises at construction from np.random
+        self.name = ImageGenerator.__name__
+
+    @property
+    def ema(self):
+        """The averaged generator (an extension: train.py --ema_decay, Updater(ema_decay=...)): None when averaging is off, else a
+        link over the exponential moving average of this generator's parameters and running statistics -- sample, sample_many,
+        test-mode __call__, serialize_dict / namedparams under this generator's keys.  It reads the buffers the training step
+        writes, so it is current after every iteration."""
+        impl = self.impl.ema
+        if impl is None:
+            return None
+        link = getattr(self, '_ema_link', None)
+        if link is None or link.impl is not impl:
+            link = self._ema_link = _AveragedGenerator(self, impl)
+        return link
 
     def make_hidden(self, batchsize, size):
         return np.random.normal(0, 0.33, size=[batchsize, size]).astype(np.float32)
@@ -162,6 +180,15 @@ class ImageGenerator(_Link):
         dev = self.impl.device
         return {'labels': None if labels is None else torch.as_tensor(labels, dtype=torch.int32, device=dev),
                 'h0': torch.as_tensor(h0, device=dev), 'e': torch.as_tensor(e, device=dev), 'zc': torch.as_tensor(zc, device=dev)}
+
+
+class _AveragedGenerator(ImageGenerator):
+    """ImageGenerator's surface over the averaged network of a live generator (ImageGenerator.ema).  Test mode only: __call__ under
+    config.train = True is refused, it has no batch statistics of its own to update."""
+
+    def __init__(self, live, impl):
+        self._describe(live.dim_zc, live.dim_zm, live.dim_zl, live.out_channels, live.n_filters, live.video_len)
+        self.impl = impl
 
 
 class _Discriminator(_Link):

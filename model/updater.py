@@ -33,6 +33,8 @@ class Updater:
         overlap = kwargs.pop('overlap', False)
         precision = kwargs.pop('precision', None)
         sync_bn = kwargs.pop('sync_bn', False)
+        # None: off; D in [0, 1): image_gen.ema is the exponential moving average of the generator (step.ema_rate)
+        ema_decay = kwargs.pop('ema_decay', None)
         if kwargs:
             raise TypeError('unexpected arguments: %s' % sorted(kwargs))
         self.iteration = 0
@@ -40,7 +42,7 @@ class Updater:
         hyper = {k: self._optimizers[k].hyper() for k in ('image_gen', 'image_dis', 'video_dis')}
         self._step = _step.TrainStep(self.model, self.image_gen.impl, self.image_dis.impl, self.video_dis.impl,
                                      hyper=hyper, exchange=exchange, seed=seed, rank=rank, overlap=overlap,
-                                     precision=precision, sync_bn=sync_bn)
+                                     precision=precision, sync_bn=sync_bn, ema_decay=ema_decay)
 
     # ---- StandardUpdater surface -------------------------------------------------------------------
     def get_optimizer(self, name):

@@ -71,7 +71,14 @@ def parse_args(argv=None):
     p.add_argument('--loader_workers', type=int, default=0,
                    help="0: the reference's serial in-process loading (SerialIterator); N > 0: N worker processes decode the "
                         "next batches while the GPU trains (PrefetchIterator)")
-    return p.parse_args(argv)
+    p.add_argument('--ema_decay', type=float, default=0.0,
+                   help="0 (default): off.  D in (0, 1): keep an exponential moving average of the generator's weights and running "
+                        "statistics (decay min(D, (1 + k) / (10 + k)) at its k-th update), advanced inside the generator's Adam launch, "
+                        "and write it as image_gen_ema_epoch_*.npz beside image_gen_epoch_*.npz (generate_samples.py reads either)")
+    args = p.parse_args(argv)
+    if not 0.0 <= args.ema_decay < 1.0:
+        p.error('--ema_decay must lie in [0, 1)')
+    return args
 
 
 def main(argv=None):
@@ -154,7 +161,8 @@ def main(argv=None):
     updater = Updater(model=args.model, models=(image_gen, image_dis, video_dis), video_length=video_length,
                       img_size=size, channel=channel, dim_zl=num_labels, iterator=train_iter,
                       tensorboard_writer=writer, optimizer=opts, device=args.gpu, seed=args.seed, exchange=exchange, rank=rank,
-                      overlap=bool(args.overlap), precision=args.mfma, sync_bn=bool(args.sync_bn))
+                      overlap=bool(args.overlap), precision=args.mfma, sync_bn=bool(args.sync_bn),
+                      ema_decay=args.ema_decay if args.ema_decay > 0 else None)
 
     save_path = Path('result') / args.save_name
     trainer = T.Trainer(updater, (args.max_epoch, 'epoch'), out=save_path)
@@ -162,6 +170,8 @@ def main(argv=None):
         snap = (args.snapshot_interval, 'epoch')
         trainer.extend(T.extensions.snapshot(filename='snapshot_epoch_{.updater.epoch}.npz'), trigger=snap)
         trainer.extend(T.extensions.snapshot_object(image_gen, 'image_gen_epoch_{.updater.epoch}.npz'), trigger=snap)
+        if image_gen.ema is not None:
+            trainer.extend(T.extensions.snapshot_object(image_gen.ema, 'image_gen_ema_epoch_{.updater.epoch}.npz'), trigger=snap)
         trainer.extend(T.extensions.snapshot_object(image_dis, 'image_dis_epoch_{.updater.epoch}.npz'), trigger=snap)
         trainer.extend(T.extensions.snapshot_object(video_dis, 'video_dis_epoch_{.updater.epoch}.npz'), trigger=snap)
         disp = (args.display_interval, 'epoch')
@@ -181,22 +191,11 @@ def main(argv=None):
         # Epoch semantics: with --dp_shard 1 (default) rank r walks items r, r + world, ... in its own order, so one epoch of all
         # ranks is ONE pass over the data; with --dp_shard 0 every rank walks the WHOLE dataset (an "epoch" is world-size passes).
         # BatchNorm running statistics are per rank and rank 0's are the ones saved.
-        import torch
+        # The Adam step counter (it sets lr_t) and the BatchNorm call counts travel too, and with --ema_decay the averaged
+        # generator and its update count (step.replica_tensors / replica_counters name all of it); the bf16 copy of the weights
+        # is rebuilt from what arrived.
         for link in (image_gen, image_dis, video_dis):
-            net = link.impl
-            exchange.broadcast_params([net.fp.p, net.fp.m, net.fp.v] + list(net.running.values()))
-            # the Adam step counter (it sets lr_t) and the BatchNorm call counts travel too; the bf16 copy of the
-            # weights is rebuilt from what arrived
-            names = sorted(net.bn_count)
-            cnt = torch.tensor([net.t] + [net.bn_count[k] for k in names], dtype=torch.int64, device=net.fp.p.device)
-            exchange.broadcast_params([cnt])
-            cnt = cnt.tolist()
-            net.t = int(cnt[0])
-            for k, v in zip(names, cnt[1:]):
-                net.bn_count[k] = int(v)
-            net.fp.touch()
-            if net.precision == 'bf16':
-                net.fp.refresh16()
+            exchange.broadcast_replica(link.impl)
 
     if rank == 0:
         # the reference's start-up banner (train.py:165-187), same lines and order
@@ -211,6 +210,8 @@ def main(argv=None):
     trainer.run()
     if rank == 0:
         T.save_npz(save_path / 'image_gen_epoch_fianl.npz', image_gen)     # (sic) train.py:190-192
+        if image_gen.ema is not None:
+            T.save_npz(save_path / 'image_gen_ema_epoch_fianl.npz', image_gen.ema)
         T.save_npz(save_path / 'image_dis_epoch_fianl.npz', image_dis)
         T.save_npz(save_path / 'video_dis_epoch_fianl.npz', video_dis)
     return trainer
