@@ -1,10 +1,12 @@
 // HBM-bound and tiny kernels of the MoCoGAN step for gfx950: BatchNorm statistics / apply /
 // backward fused with the activations and add_noise, Philox noise, layout packing, the
 // full-window (1x1-output) layers, the fused GRU recurrence, the GAN losses and Chainer-Adam.
-// All tensors are channels-last fp32 with C % 4 == 0, so every kernel moves 16 bytes per lane.
+// Tensors are channels-last with C % 4 == 0, fp32 or (MCG_IO_* flags, bf16 networks) bf16 in memory.  The element-wise passes
+// give a thread 4 channels, or 8 where a tensor of the call is bf16 and C % 8 == 0, so a lane's access is 16 bytes (8 for four bf16).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
+#include <type_traits>
 #include "mocogan_hip.h"
 #include "mcg_common.h"
 
@@ -19,29 +21,30 @@ int launch_status() { return hipGetLastError() == hipSuccess ? MCG_OK : MCG_ERR_
 
 using mcg::randn4;
 
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-// element i4 (a group of 4) of a tensor that is fp32 or (out16) bf16 in memory: MCG_PREC_BF16_STORE networks keep the
-// GEMM operands -- activations and output gradients -- in bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32)
-__device__ __forceinline__ void store4(float* out, long long i4, f32x4 v, int out16) {
-    if (out16) reinterpret_cast<bf16x4_t*>(out)[i4] = __builtin_convertvector(v, bf16x4_t);
-    else reinterpret_cast<f32x4*>(out)[i4] = v;
-}
-// the four elements starting at ELEMENT offset e (a multiple of 4) of a tensor that is fp32 or (in16) bf16 in memory: bf16
-// networks also keep the GEMM OUTPUTS the element-wise passes read -- pre-BatchNorm activations, input gradients -- in bf16
-__device__ __forceinline__ f32x4 load4(const float* in, long long e, int in16) {
-    if (in16) return __builtin_convertvector(*reinterpret_cast<const bf16x4_t*>(reinterpret_cast<const __bf16*>(in) + e), f32x4);
-    return *reinterpret_cast<const f32x4*>(in + e);
-}
+// W = 4 or 8 consecutive channels of a thread, as fp32 values (vecf) and as they lie in a bf16 tensor (vecb)
+template <int W> using vecf = float __attribute__((ext_vector_type(W)));
+template <int W> using vecb = __bf16 __attribute__((ext_vector_type(W)));
+template <int W> constexpr int LOG2 = W == 8 ? 3 : 2;
+typedef vecf<8> f32x8;
+typedef vecb<4> bf16x4_t;
+typedef vecb<8> bf16x8_t;
 
-// eight consecutive elements (element offset e, a multiple of 8): bf16 tensors then move 16 bytes per lane and access -- with
-// groups of four a bf16 load is 8 bytes per lane and the bf16 networks' element-wise passes ran at half the bytes in flight
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x8 load8(const float* in, long long e, int in16) {
-    if (in16) return __builtin_convertvector(*reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const __bf16*>(in) + e), f32x8);
-    const f32x4 a = *reinterpret_cast<const f32x4*>(in + e), b = *reinterpret_cast<const f32x4*>(in + e + 4);
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+// the W elements starting at ELEMENT offset e (a multiple of W) of a tensor that is fp32 or (in16) bf16 in memory: bf16 networks
+// keep the GEMM operands -- activations, output gradients -- and the GEMM outputs the element-wise passes read -- pre-BatchNorm
+// activations, input gradients -- in bf16.  W = 8 makes a bf16 access 16 bytes per lane (with groups of four it is 8, and the bf16
+// networks' passes ran at half the bytes in flight); fp32 accesses are 16 bytes at either width.
+template <int W>
+__device__ __forceinline__ vecf<W> loadv(const float* in, long long e, int in16) {
+    if (in16) return __builtin_convertvector(*reinterpret_cast<const vecb<W>*>(reinterpret_cast<const __bf16*>(in) + e), vecf<W>);
+    if constexpr (W == 4) return *reinterpret_cast<const f32x4*>(in + e);
+    else {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(in + e), b = *reinterpret_cast<const f32x4*>(in + e + 4);
+        return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
 }
+template <int W>
+__device__ __forceinline__ vecf<W> cvec(const float* p, int group) { return loadv<W>(p, group * W, 0); }    // per-channel constants of a channel group
+
 // fp32 -> the three bf16 terms of MCG_PREC_SPLIT (include/mocogan_hip.h): hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi - mid);
 // the differences are exact in fp32 and v == hi + mid + lo.  One thread: 8 consecutive values of a run -> one 16-byte piece of each
 // of the run's three planes (the fourth, padding, is not written).
@@ -61,15 +64,18 @@ __device__ __forceinline__ void store_split8(__bf16* dst, long long e, long long
     *reinterpret_cast<bf16x8_t*>(d + run) = mid;
     *reinterpret_cast<bf16x8_t*>(d + 2 * run) = lo;        // (the fourth plane only pads a group to 128 bytes: no kernel fetches it)
 }
-__device__ __forceinline__ void store8(float* out, long long e, f32x8 v, int out16) {       // out16: MCG_IO_OUT_BF16 / MCG_IO_OUT_SPLIT / 0
-    if (out16 & MCG_IO_OUT_SPLIT) { store_split8(reinterpret_cast<__bf16*>(out), e, 16, v); return; }     // (out16: MCG_IO_OUT_BF16 / _SPLIT / 0)
-    if (out16) { *reinterpret_cast<bf16x8_t*>(reinterpret_cast<__bf16*>(out) + e) = __builtin_convertvector(v, bf16x8_t); return; }
-    *reinterpret_cast<f32x4*>(out + e) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
-    *reinterpret_cast<f32x4*>(out + e + 4) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
-}
-__device__ __forceinline__ f32x8 cvec8(const float* p, int c8) {          // per-channel constants of channel group c8
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p + c8 * 8), b = *reinterpret_cast<const f32x4*>(p + c8 * 8 + 4);
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+// the store to match loadv; oflags: 0 (fp32), MCG_IO_OUT_BF16 (round-to-nearest-even, v_cvt_pk_bf16_f32) or, W = 8 only, MCG_IO_OUT_SPLIT
+template <int W>
+__device__ __forceinline__ void storev(float* out, long long e, vecf<W> v, int oflags) {
+    if constexpr (W == 8) {
+        if (oflags & MCG_IO_OUT_SPLIT) { store_split8(reinterpret_cast<__bf16*>(out), e, 16, v); return; }
+    }
+    if (oflags) { *reinterpret_cast<vecb<W>*>(reinterpret_cast<__bf16*>(out) + e) = __builtin_convertvector(v, vecb<W>); return; }
+    if constexpr (W == 4) *reinterpret_cast<f32x4*>(out + e) = v;
+    else {
+        *reinterpret_cast<f32x4*>(out + e) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
+        *reinterpret_cast<f32x4*>(out + e + 4) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
+    }
 }
 
 __device__ __forceinline__ float act_fwd(float v, int act) {
@@ -91,109 +97,62 @@ __device__ __forceinline__ float act_mask(float v, int act) {
 // MODE 0: (sum y, sum y^2)           -> BN statistics
 // MODE 1: (sum g_bn, sum g_bn*x_hat) -> BN backward
 // MODE 2: (sum g, unused)            -> bias gradient
-// Thread layout: C4 = C/4 float4 columns, NT/C4 row lanes per pass; the block's row lanes are
-// combined through LDS; part[block][2][C].
+// Thread layout: CW = C/W columns of W channels, RL = NT/CW row lanes per pass (CW divides NT: unsupported_c, wide_c); the
+// block's row lanes are combined through LDS; part[block][2][C].  W = 8 (MODE 1 of bf16 networks) has half the columns and
+// twice the row lanes of W = 4, so the two widths add the same addends in different trees.
 // ------------------------------------------------------------------------------------------
-template <int MODE, int IO = 0>                      // IO: MCG_IO_* flags of a (G) and y (Y), compile-time (see bn_act_fwd_kernel)
+template <int MODE, int W = 4, int IO = 0>           // IO: MCG_IO_* flags of a (G) and y (Y), compile-time (see bn_act_fwd_kernel)
 __global__ __launch_bounds__(NT) void col_partial_kernel(long long M, int C, long long rows_per_block,
                                                          const float* __restrict__ a, const float* __restrict__ y,
                                                          const float* __restrict__ stats, int act,
                                                          float* __restrict__ part) {
-    constexpr int io = IO;
-    __shared__ f32x4 red[2][NT];
-    const int C4 = C >> 2;
-    const int c4 = threadIdx.x % C4, rl = threadIdx.x / C4, RL = NT / C4;
+    using V = vecf<W>;
+    __shared__ V red[2][NT];
+    const int CW = C >> LOG2<W>;
+    const int c = threadIdx.x % CW, rl = threadIdx.x / CW, RL = NT / CW;
     const long long r0 = (long long)blockIdx.x * rows_per_block;
     long long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
-    f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
-    f32x4 mean = {0, 0, 0, 0}, istd = {1, 1, 1, 1}, sc = {1, 1, 1, 1}, sh = {0, 0, 0, 0};
-    if (MODE == 1 && stats && rl < RL) {
-        mean = *reinterpret_cast<const f32x4*>(stats + c4 * 4);
-        istd = *reinterpret_cast<const f32x4*>(stats + C + c4 * 4);
-        sc = *reinterpret_cast<const f32x4*>(stats + 2 * C + c4 * 4);
-        sh = *reinterpret_cast<const f32x4*>(stats + 3 * C + c4 * 4);
-    }
-    if (rl < RL) {
-        // four rows in flight per thread: with at most MAX_PART blocks on the chip a single dependent load per iteration
-        // leaves the pass latency-bound (measured 3.3 TB/s); the sums of a row quad are added in a fixed order
-        auto row = [&](long long r, f32x4& t0, f32x4& t1) {
-            f32x4 v = load4(a, r * C + c4 * 4, io & MCG_IO_G_BF16);
-            if (MODE == 0) { t0 = v; t1 = v * v; }
-            else if (MODE == 2) { t0 = v; }
-            else {
-                f32x4 yy = load4(y, r * C + c4 * 4, io & MCG_IO_Y_BF16);
+    V s0 = {}, s1 = {}, mean = {}, istd = {}, sc = {}, sh = {};
+    // (every launch of MODE 1 has stats; the four-wide kernel keeps its test of the pointer because without it the register
+    //  allocation comes out three VGPRs larger, 98, and costs the kernel a wave of occupancy)
+    if (MODE == 1 && (W == 8 || stats)) { mean = cvec<W>(stats, c); istd = cvec<W>(stats + C, c); sc = cvec<W>(stats + 2 * C, c); sh = cvec<W>(stats + 3 * C, c); }
+    auto row = [&](long long r, V& t0, V& t1) {
+        const V v = loadv<W>(a, r * C + c * W, IO & MCG_IO_G_BF16);
+        if constexpr (MODE == 0) { t0 = v; t1 = v * v; }
+        else if constexpr (MODE == 2) { t0 = v; }
+        else {
+            const V yy = loadv<W>(y, r * C + c * W, IO & MCG_IO_Y_BF16);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float gb = v[i] * act_mask(fmaf(yy[i], sc[i], sh[i]), act);
-                    t0[i] = gb; t1[i] = gb * (yy[i] - mean[i]) * istd[i];
-                }
+            for (int i = 0; i < W; ++i) {
+                const float gb = v[i] * act_mask(fmaf(yy[i], sc[i], sh[i]), act);
+                t0[i] = gb; t1[i] = gb * (yy[i] - mean[i]) * istd[i];
             }
-        };
-        long long r = r0 + rl;
-        for (; r + 3LL * RL < r1; r += 4LL * RL) {
-            f32x4 a0 = {0, 0, 0, 0}, a1 = a0, b0 = a0, b1 = a0, c0 = a0, c1 = a0, d0 = a0, d1 = a0;
-            row(r, a0, a1); row(r + RL, b0, b1); row(r + 2LL * RL, c0, c1); row(r + 3LL * RL, d0, d1);
-            s0 += (a0 + b0) + (c0 + d0); s1 += (a1 + b1) + (c1 + d1);
-        }
-        for (; r < r1; r += RL) {
-            f32x4 a0 = {0, 0, 0, 0}, a1 = a0;
-            row(r, a0, a1);
-            s0 += a0; s1 += a1;
-        }
-    }
-    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
-    __syncthreads();
-    if (threadIdx.x < C4) {
-        for (int k = 1; k < RL; ++k) { s0 += red[0][k * C4 + c4]; s1 += red[1][k * C4 + c4]; }
-        float* p = part + (long long)blockIdx.x * 2 * C;
-        *reinterpret_cast<f32x4*>(p + c4 * 4) = s0;
-        *reinterpret_cast<f32x4*>(p + C + c4 * 4) = s1;
-    }
-}
-
-// The BatchNorm-backward sums (MODE 1 above) with eight channels per thread, for bf16 networks (C % 8 == 0): part[block][2][C].
-template <int IO>
-__global__ __launch_bounds__(NT) void col_partial8_kernel(long long M, int C, long long rows_per_block, const float* __restrict__ a,
-                                                          const float* __restrict__ y, const float* __restrict__ stats, int act,
-                                                          float* __restrict__ part) {
-    constexpr int io = IO;
-    __shared__ f32x8 red[2][NT];
-    const int C8 = C >> 3;
-    const int c8 = threadIdx.x % C8, rl = threadIdx.x / C8, RL = NT / C8;
-    const long long r0 = (long long)blockIdx.x * rows_per_block;
-    long long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
-    f32x8 s0 = {0, 0, 0, 0, 0, 0, 0, 0}, s1 = s0;
-    const f32x8 mean = cvec8(stats, c8), istd = cvec8(stats + C, c8), sc = cvec8(stats + 2 * C, c8), sh = cvec8(stats + 3 * C, c8);
-    auto row = [&](long long r, f32x8& t0, f32x8& t1) {
-        const f32x8 v = load8(a, r * C + c8 * 8, io & MCG_IO_G_BF16), yy = load8(y, r * C + c8 * 8, io & MCG_IO_Y_BF16);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float gb = v[i] * act_mask(fmaf(yy[i], sc[i], sh[i]), act);
-            t0[i] = gb; t1[i] = gb * (yy[i] - mean[i]) * istd[i];
         }
     };
+    // four rows in flight per thread: with at most MAX_PART blocks on the chip a single dependent load per iteration
+    // leaves the pass latency-bound (measured 3.3 TB/s); the sums of a row quad are added in a fixed order
     long long r = r0 + rl;
-    for (; r + 3LL * RL < r1; r += 4LL * RL) {               // four rows in flight per thread, summed in a fixed order
-        f32x8 a0, a1, b0, b1, c0, c1, d0, d1;
+    for (; r + 3LL * RL < r1; r += 4LL * RL) {
+        V a0 = {}, a1 = {}, b0 = {}, b1 = {}, c0 = {}, c1 = {}, d0 = {}, d1 = {};
         row(r, a0, a1); row(r + RL, b0, b1); row(r + 2LL * RL, c0, c1); row(r + 3LL * RL, d0, d1);
         s0 += (a0 + b0) + (c0 + d0); s1 += (a1 + b1) + (c1 + d1);
     }
     for (; r < r1; r += RL) {
-        f32x8 a0, a1;
+        V a0 = {}, a1 = {};
         row(r, a0, a1);
         s0 += a0; s1 += a1;
     }
     red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
     __syncthreads();
-    if (threadIdx.x < C8) {
-        for (int k = 1; k < RL; ++k) { s0 += red[0][k * C8 + c8]; s1 += red[1][k * C8 + c8]; }
+    if (threadIdx.x < CW) {
+        for (int k = 1; k < RL; ++k) { s0 += red[0][k * CW + c]; s1 += red[1][k * CW + c]; }
         float* p = part + (long long)blockIdx.x * 2 * C;
-        store8(p, c8 * 8, s0, 0);
-        store8(p + C, c8 * 8, s1, 0);
+        storev<W>(p, c * W, s0, 0);
+        storev<W>(p + C, c * W, s1, 0);
     }
 }
 
-// C may exceed NT*4/…: handled by requiring C4 <= NT (C <= 1024)
+// blocks of col_partial_kernel and the rows each takes: at least 8 rows per thread of the four-wide layout, at most MAX_PART blocks
 struct PartPlan { int blocks; long long rows_per_block; };
 PartPlan plan_partial(long long M, int C) {
     int RL = NT / (C >> 2);
@@ -272,11 +231,11 @@ __device__ __forceinline__ bool reduce_partials(int nblocks, int C, const float*
     return true;
 }
 
-__global__ __launch_bounds__(FIN_CH * FIN_SL) void bn_stats_finalize_kernel(int nblocks, int C, double inv_m, double adjust, const float* __restrict__ part,
-                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                         float* __restrict__ stats, float* avg_mean, float* avg_var, float eps, float decay, long long stride) {
-    int c; double s, ss;
-    if (!reduce_partials(nblocks, C, part, c, s, ss, stride)) return;
+// Channel c's BatchNorm statistics from its sums over M = 1 / inv_m rows: stats[0..4C) = mean, inv_std, scale = gamma * inv_std,
+// shift = beta - mean * scale, and the running averages (adjust: bessel_adjust(M)).  The ONE statement of the Chainer-3.1 variance rule.
+__device__ __forceinline__ void bn_stats_write(int c, int C, double s, double ss, double inv_m, double adjust, const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, float* __restrict__ stats, float* avg_mean, float* avg_var,
+                                               float eps, float decay) {
     double mean = s * inv_m;
     double var = ss * inv_m - mean * mean;
     if (var < 0) var = 0;
@@ -293,17 +252,30 @@ __global__ __launch_bounds__(FIN_CH * FIN_SL) void bn_stats_finalize_kernel(int 
     }
 }
 
-// coef[0..C) = gamma*inv_std, [C..2C) = ggamma/M, [2C..3C) = gbeta/M ; dgamma/dbeta accumulated
+// Channel c of the backward pass: coef[0..C) = gamma*inv_std, [C..2C) = ggamma/M, [2C..3C) = gbeta/M from the sums (gb, gg) of the
+// batch the statistics were taken over; dgamma / dbeta accumulate this rank's own sums (the same numbers unless BatchNorm is synchronised)
+__device__ __forceinline__ void bn_bwd_write(int c, int C, double gb, double gg, double inv_m, double gb_local, double gg_local,
+                                             const float* __restrict__ stats, const float* __restrict__ gamma, float* __restrict__ coef,
+                                             float* dgamma, float* dbeta) {
+    coef[c] = gamma[c] * stats[C + c];
+    coef[C + c] = (float)(gg * inv_m);
+    coef[2 * C + c] = (float)(gb * inv_m);
+    if (dgamma) dgamma[c] += (float)gg_local;
+    if (dbeta) dbeta[c] += (float)gb_local;
+}
+
+__global__ __launch_bounds__(FIN_CH * FIN_SL) void bn_stats_finalize_kernel(int nblocks, int C, double inv_m, double adjust, const float* __restrict__ part,
+                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                         float* __restrict__ stats, float* avg_mean, float* avg_var, float eps, float decay, long long stride) {
+    int c; double s, ss;
+    if (reduce_partials(nblocks, C, part, c, s, ss, stride)) bn_stats_write(c, C, s, ss, inv_m, adjust, gamma, beta, stats, avg_mean, avg_var, eps, decay);
+}
+
 __global__ __launch_bounds__(FIN_CH * FIN_SL) void bn_bwd_finalize_kernel(int nblocks, int C, double inv_m, const float* __restrict__ part,
                                        const float* __restrict__ stats, const float* __restrict__ gamma,
                                        float* __restrict__ coef, float* dgamma, float* dbeta, long long stride) {
     int c; double gb, gg;
-    if (!reduce_partials(nblocks, C, part, c, gb, gg, stride)) return;
-    coef[c] = gamma[c] * stats[C + c];
-    coef[C + c] = (float)(gg * inv_m);
-    coef[2 * C + c] = (float)(gb * inv_m);
-    if (dgamma) dgamma[c] += (float)gg;
-    if (dbeta) dbeta[c] += (float)gb;
+    if (reduce_partials(nblocks, C, part, c, gb, gg, stride)) bn_bwd_write(c, C, gb, gg, inv_m, gb, gg, stats, gamma, coef, dgamma, dbeta);
 }
 
 // ---- synchronised BatchNorm (opt-in, data parallel): the per-channel sums leave the library as doubles, the caller
@@ -318,35 +290,15 @@ __global__ void bn_stats_from_sums_kernel(int C, double inv_m, double adjust, co
                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                           float* __restrict__ stats, float* avg_mean, float* avg_var, float eps, float decay) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double mean = sums[c] * inv_m;
-    double var = sums[C + c] * inv_m - mean * mean;
-    if (var < 0) var = 0;
-    var += eps;
-    float istd = (float)(1.0 / sqrt(var));
-    float scale = gamma[c] * istd;
-    stats[c] = (float)mean;
-    stats[C + c] = istd;
-    stats[2 * C + c] = scale;
-    stats[3 * C + c] = fmaf(-(float)mean, scale, beta[c]);
-    if (avg_mean) {
-        avg_mean[c] = avg_mean[c] * decay + (1.f - decay) * (float)mean;
-        avg_var[c] = avg_var[c] * decay + (1.f - decay) * (float)(adjust * var);
-    }
+    if (c < C) bn_stats_write(c, C, sums[c], sums[C + c], inv_m, adjust, gamma, beta, stats, avg_mean, avg_var, eps, decay);
 }
 
-// coef as in bn_bwd_finalize_kernel from the GLOBAL sums; dgamma / dbeta take the LOCAL sums (the gradient
-// exchange averages them over the ranks afterwards)
+// coef from the GLOBAL sums; dgamma / dbeta take the LOCAL sums (the gradient exchange averages them over the ranks afterwards)
 __global__ void bn_bwd_from_sums_kernel(int C, double inv_m_total, const double* __restrict__ local_sums, const double* __restrict__ global_sums,
                                         const float* __restrict__ stats, const float* __restrict__ gamma, float* __restrict__ coef,
                                         float* dgamma, float* dbeta) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    coef[c] = gamma[c] * stats[C + c];
-    coef[C + c] = (float)(global_sums[C + c] * inv_m_total);
-    coef[2 * C + c] = (float)(global_sums[c] * inv_m_total);
-    if (dgamma) dgamma[c] += (float)local_sums[C + c];
-    if (dbeta) dbeta[c] += (float)local_sums[c];
+    if (c < C) bn_bwd_write(c, C, global_sums[c], global_sums[C + c], inv_m_total, local_sums[c], local_sums[C + c], stats, gamma, coef, dgamma, dbeta);
 }
 
 __global__ __launch_bounds__(FIN_CH * FIN_SL) void colsum_finalize_kernel(int nblocks, int C, const float* __restrict__ part, float* db, long long stride) {
@@ -355,169 +307,98 @@ __global__ __launch_bounds__(FIN_CH * FIN_SL) void colsum_finalize_kernel(int nb
     db[c] += (float)s;
 }
 
-// out = act(y*scale+shift) + noise
-template <int IO>        // MCG_IO_* flags as a compile-time constant: a run-time element type puts a branch (and a wait) around every load
-__global__ __launch_bounds__(NT) void bn_act_fwd_kernel(long long n4, int C, int c_valid, const float* __restrict__ y,
-                                                        long long item4, long long item_stride,
-                                                        const float* __restrict__ ss, int act,
-                                                        const float* __restrict__ addend, float sigma,
-                                                        uint64_t seed, uint64_t stream_id, float* __restrict__ out) {
-    constexpr int io = IO;
-    const int C4 = C >> 2;
-    constexpr int out16 = io & MCG_IO_OUT_BF16;
+// The element-wise passes' grid-stride loop over n groups of W channels: two groups per trip, both loaded before either is used
+// -- with bf16 tensors a four-wide group is an 8-byte access, and one per thread in flight leaves the pass latency-bound.
+template <class Load, class Finish>
+__device__ __forceinline__ void for_each_pair(long long n, Load load, Finish finish) {
     const long long stride = (long long)gridDim.x * NT;
-    // source may be a batch-strided view (frame t of a clip tensor): item = i / item4
-    auto src_of = [&](long long i) { return item4 ? (i / item4) * item_stride + (i % item4) * 4 : i * 4; };
-    // a thread's channel group is the same on every trip when the grid stride is a multiple of C / 4 (every power-of-two
-    // channel count): the per-channel vectors are then loaded once, not once per group
-    const bool fixed_c = stride % C4 == 0;
-    f32x4 sc = {1, 1, 1, 1}, sh = {0, 0, 0, 0};
-    auto consts = [&](int c4) {
-        if (ss) { sc = *reinterpret_cast<const f32x4*>(ss + c4 * 4); sh = *reinterpret_cast<const f32x4*>(ss + C + c4 * 4); }
-    };
-    consts((int)(((long long)blockIdx.x * NT + threadIdx.x) % C4));
-    auto finish = [&](long long i, f32x4 v) {
-        const int c4 = (int)(i % C4);
-        if (!fixed_c) consts(c4);
-        if (ss) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = fmaf(v[k], sc[k], sh[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = act_fwd(v[k], act);
-        if (addend) {
-            v += *reinterpret_cast<const f32x4*>(addend + i * 4);
-        } else if (sigma > 0.f) {
-            f32x4 z = randn4((uint64_t)i, seed, stream_id);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (c4 * 4 + k < c_valid) v[k] = fmaf(sigma, z[k], v[k]);
-        }
-        store4(out, i, v, out16);
-    };
-    // two groups of four per trip, both loads issued before either is used: with bf16 tensors a group is an 8-byte access,
-    // and one per thread in flight leaves the pass latency-bound
-    for (long long i0 = (long long)blockIdx.x * NT + threadIdx.x; i0 < n4; i0 += 2 * stride) {
-        const long long i1 = i0 + stride < n4 ? i0 + stride : i0;          // (the tail repeats group 0's load, its result is dropped)
-        const f32x4 v0 = load4(y, src_of(i0), io & MCG_IO_Y_BF16);
-        const f32x4 v1 = load4(y, src_of(i1), io & MCG_IO_Y_BF16);
+    for (long long i0 = (long long)blockIdx.x * NT + threadIdx.x; i0 < n; i0 += 2 * stride) {
+        const long long i1 = i0 + stride < n ? i0 + stride : i0;          // (the tail repeats group 0's load, its result is dropped)
+        const auto v0 = load(i0);
+        const auto v1 = load(i1);
         finish(i0, v0);
         if (i1 != i0) finish(i1, v1);
     }
 }
+// A thread's channel group is the same on every trip when the grid stride is a multiple of C / W (every power-of-two channel
+// count): the per-channel vectors are then loaded once (first_group), not once per group.
+__device__ __forceinline__ bool fixed_group(int CW) { return ((long long)gridDim.x * NT) % CW == 0; }
+__device__ __forceinline__ int first_group(int CW) { return (int)(((long long)blockIdx.x * NT + threadIdx.x) % CW); }
 
-// gx = coef0 * (g*mask - x_hat*coef1 - coef2)    (BN)   or   gx = g*mask(y) / g*(1-y^2)  (no BN)
-template <int IO>
-__global__ __launch_bounds__(NT) void bn_act_bwd_apply_kernel(long long n4, int C, const float* __restrict__ g,
+// out = act(y*scale+shift) + noise over n groups of W channels.  Noise keeps its element order at either width: group i takes the
+// Philox counters i * W/4 + q, q < W/4.  W = 4 only: y may be a batch-strided view (frame t of a clip tensor: item = i / item_groups)
+// and channels >= c_valid (the clip's pad channel) take no noise; the eight-wide launches have dense y and every channel valid.
+template <int W, int IO>   // MCG_IO_* flags as a compile-time constant: a run-time element type puts a branch (and a wait) around every load
+__global__ __launch_bounds__(NT) void bn_act_fwd_kernel(long long n, int C, int c_valid, const float* __restrict__ y,
+                                                        long long item_groups, long long item_stride,
+                                                        const float* __restrict__ ss, int act,
+                                                        const float* __restrict__ addend, float sigma,
+                                                        uint64_t seed, uint64_t stream_id, float* __restrict__ out) {
+    using V = vecf<W>;
+    const int CW = C >> LOG2<W>;
+    const bool fixed_c = fixed_group(CW);
+    V sc = V{} + 1.f, sh = {};
+    auto consts = [&](int c) { if (ss) { sc = cvec<W>(ss, c); sh = cvec<W>(ss + C, c); } };
+    consts(first_group(CW));
+    auto load = [&](long long i) {
+        long long e = i * W;
+        if constexpr (W == 4) { if (item_groups) e = (i / item_groups) * item_stride + (i % item_groups) * 4; }
+        return loadv<W>(y, e, IO & MCG_IO_Y_BF16);
+    };
+    auto finish = [&](long long i, V v) {
+        const int c = (int)(i % CW);
+        if (!fixed_c) consts(c);
+#pragma unroll
+        for (int k = 0; k < W; ++k) v[k] = act_fwd(ss ? fmaf(v[k], sc[k], sh[k]) : v[k], act);
+        if (addend) v += loadv<W>(addend, i * W, 0);
+        else if (sigma > 0.f) {
+#pragma unroll
+            for (int q = 0; q < W / 4; ++q) {
+                const f32x4 z = randn4((uint64_t)(i * (W / 4) + q), seed, stream_id);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) if (W == 8 || c * 4 + k < c_valid) v[q * 4 + k] = fmaf(sigma, z[k], v[q * 4 + k]);
+            }
+        }
+        storev<W>(out, i * W, v, IO & (MCG_IO_OUT_BF16 | MCG_IO_OUT_SPLIT));
+    };
+    for_each_pair(n, load, finish);
+}
+
+// gx = coef0 * (g*mask - x_hat*coef1 - coef2)    (BN)   or, W = 4 only,   gx = g*mask(y) / g*(1-y^2)  (no BN: stats == nullptr)
+template <int W, int IO>
+__global__ __launch_bounds__(NT) void bn_act_bwd_apply_kernel(long long n, int C, const float* __restrict__ g,
                                                               const float* __restrict__ y, const float* __restrict__ stats,
                                                               const float* __restrict__ coef, int act, float* __restrict__ gx) {
-    constexpr int io = IO;
-    const int C4 = C >> 2;
-    constexpr int out16 = io & MCG_IO_OUT_BF16;
-    const long long stride = (long long)gridDim.x * NT;
-    const bool fixed_c = stride % C4 == 0;                      // (as bn_act_fwd_kernel: the seven per-channel vectors once per thread)
-    f32x4 mean = {0, 0, 0, 0}, istd = mean, sc = mean, sh = mean, k0 = mean, k1 = mean, k2 = mean;
-    auto consts = [&](int c4) {
-        if (!stats) return;
-        mean = *reinterpret_cast<const f32x4*>(stats + c4 * 4);
-        istd = *reinterpret_cast<const f32x4*>(stats + C + c4 * 4);
-        sc = *reinterpret_cast<const f32x4*>(stats + 2 * C + c4 * 4);
-        sh = *reinterpret_cast<const f32x4*>(stats + 3 * C + c4 * 4);
-        k0 = *reinterpret_cast<const f32x4*>(coef + c4 * 4);
-        k1 = *reinterpret_cast<const f32x4*>(coef + C + c4 * 4);
-        k2 = *reinterpret_cast<const f32x4*>(coef + 2 * C + c4 * 4);
+    using V = vecf<W>;
+    struct GY { V g, y; };
+    const int CW = C >> LOG2<W>;
+    const bool bn = W == 8 || stats != nullptr;
+    const bool fixed_c = fixed_group(CW);                       // (the seven per-channel vectors once per thread)
+    V mean = {}, istd = {}, sc = {}, sh = {}, k0 = {}, k1 = {}, k2 = {};
+    auto consts = [&](int c) {
+        if (!bn) return;
+        mean = cvec<W>(stats, c); istd = cvec<W>(stats + C, c); sc = cvec<W>(stats + 2 * C, c); sh = cvec<W>(stats + 3 * C, c);
+        k0 = cvec<W>(coef, c); k1 = cvec<W>(coef + C, c); k2 = cvec<W>(coef + 2 * C, c);
     };
-    consts((int)(((long long)blockIdx.x * NT + threadIdx.x) % C4));
-    auto finish = [&](long long i, const f32x4& gv, const f32x4& yv) {
-        if (!fixed_c) consts((int)(i % C4));
-        f32x4 o;
-        if (stats) {
+    consts(first_group(CW));
+    auto load = [&](long long i) { return GY{loadv<W>(g, i * W, IO & MCG_IO_G_BF16), loadv<W>(y, i * W, IO & MCG_IO_Y_BF16)}; };
+    auto finish = [&](long long i, const GY& in) {
+        if (!fixed_c) consts((int)(i % CW));
+        V o;
+        if (bn) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float gb = gv[k] * act_mask(fmaf(yv[k], sc[k], sh[k]), act);
-                float xh = (yv[k] - mean[k]) * istd[k];
+            for (int k = 0; k < W; ++k) {
+                const float gb = in.g[k] * act_mask(fmaf(in.y[k], sc[k], sh[k]), act);
+                const float xh = (in.y[k] - mean[k]) * istd[k];
                 o[k] = k0[k] * (gb - xh * k1[k] - k2[k]);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                o[k] = act == MCG_ACT_TANH ? gv[k] * (1.f - yv[k] * yv[k]) : gv[k] * act_mask(yv[k], act);
+            for (int k = 0; k < W; ++k) o[k] = act == MCG_ACT_TANH ? in.g[k] * (1.f - in.y[k] * in.y[k]) : in.g[k] * act_mask(in.y[k], act);
         }
-        store4(gx, i, o, out16);
+        storev<W>(gx, i * W, o, IO & (MCG_IO_OUT_BF16 | MCG_IO_OUT_SPLIT));
     };
-    for (long long i0 = (long long)blockIdx.x * NT + threadIdx.x; i0 < n4; i0 += 2 * stride) {      // (as bn_act_fwd_kernel)
-        const long long i1 = i0 + stride < n4 ? i0 + stride : i0;
-        const f32x4 g0 = load4(g, i0 * 4, io & MCG_IO_G_BF16), y0 = load4(y, i0 * 4, io & MCG_IO_Y_BF16);
-        const f32x4 g1 = load4(g, i1 * 4, io & MCG_IO_G_BF16), y1 = load4(y, i1 * 4, io & MCG_IO_Y_BF16);
-        finish(i0, g0, y0);
-        if (i1 != i0) finish(i1, g1, y1);
-    }
-}
-
-// The two kernels above with eight channels per thread (bf16 networks, C % 8 == 0, dense y): the same arithmetic per element, 16-byte
-// accesses of the bf16 tensors.  Noise keeps its element order: counters 2 i and 2 i + 1 of the stream for the eight elements of group i.
-template <int IO>
-__global__ __launch_bounds__(NT) void bn_act_fwd8_kernel(long long n8, int C, const float* __restrict__ y, const float* __restrict__ ss, int act,
-                                                         const float* __restrict__ addend, float sigma, uint64_t seed, uint64_t stream_id,
-                                                         float* __restrict__ out) {
-    constexpr int io = IO;
-    const int C8 = C >> 3;
-    const long long stride = (long long)gridDim.x * NT;
-    const bool fixed_c = stride % C8 == 0;
-    f32x8 sc = {1, 1, 1, 1, 1, 1, 1, 1}, sh = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto consts = [&](int c8) { if (ss) { sc = cvec8(ss, c8); sh = cvec8(ss + C, c8); } };
-    consts((int)(((long long)blockIdx.x * NT + threadIdx.x) % C8));
-    auto finish = [&](long long i, f32x8 v) {
-        if (!fixed_c) consts((int)(i % C8));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = act_fwd(ss ? fmaf(v[k], sc[k], sh[k]) : v[k], act);
-        if (addend) v += load8(addend, i * 8, 0);
-        else if (sigma > 0.f) {
-            const f32x4 z0 = randn4((uint64_t)(2 * i), seed, stream_id), z1 = randn4((uint64_t)(2 * i + 1), seed, stream_id);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { v[k] = fmaf(sigma, z0[k], v[k]); v[4 + k] = fmaf(sigma, z1[k], v[4 + k]); }
-        }
-        store8(out, i * 8, v, io & (MCG_IO_OUT_BF16 | MCG_IO_OUT_SPLIT));
-    };
-    for (long long i0 = (long long)blockIdx.x * NT + threadIdx.x; i0 < n8; i0 += 2 * stride) {
-        const long long i1 = i0 + stride < n8 ? i0 + stride : i0;
-        const f32x8 v0 = load8(y, i0 * 8, io & MCG_IO_Y_BF16), v1 = load8(y, i1 * 8, io & MCG_IO_Y_BF16);
-        finish(i0, v0);
-        if (i1 != i0) finish(i1, v1);
-    }
-}
-
-template <int IO>
-__global__ __launch_bounds__(NT) void bn_act_bwd_apply8_kernel(long long n8, int C, const float* __restrict__ g, const float* __restrict__ y,
-                                                               const float* __restrict__ stats, const float* __restrict__ coef, int act,
-                                                               float* __restrict__ gx) {
-    constexpr int io = IO;
-    const int C8 = C >> 3;
-    const long long stride = (long long)gridDim.x * NT;
-    const bool fixed_c = stride % C8 == 0;
-    f32x8 mean, istd, sc, sh, k0, k1, k2;
-    auto consts = [&](int c8) {
-        mean = cvec8(stats, c8); istd = cvec8(stats + C, c8); sc = cvec8(stats + 2 * C, c8); sh = cvec8(stats + 3 * C, c8);
-        k0 = cvec8(coef, c8); k1 = cvec8(coef + C, c8); k2 = cvec8(coef + 2 * C, c8);
-    };
-    consts((int)(((long long)blockIdx.x * NT + threadIdx.x) % C8));
-    auto finish = [&](long long i, const f32x8& gv, const f32x8& yv) {
-        if (!fixed_c) consts((int)(i % C8));
-        f32x8 o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float gb = gv[k] * act_mask(fmaf(yv[k], sc[k], sh[k]), act);
-            const float xh = (yv[k] - mean[k]) * istd[k];
-            o[k] = k0[k] * (gb - xh * k1[k] - k2[k]);
-        }
-        store8(gx, i * 8, o, io & (MCG_IO_OUT_BF16 | MCG_IO_OUT_SPLIT));
-    };
-    for (long long i0 = (long long)blockIdx.x * NT + threadIdx.x; i0 < n8; i0 += 2 * stride) {
-        const long long i1 = i0 + stride < n8 ? i0 + stride : i0;
-        const f32x8 g0 = load8(g, i0 * 8, io & MCG_IO_G_BF16), y0 = load8(y, i0 * 8, io & MCG_IO_Y_BF16);
-        const f32x8 g1 = load8(g, i1 * 8, io & MCG_IO_G_BF16), y1 = load8(y, i1 * 8, io & MCG_IO_Y_BF16);
-        finish(i0, g0, y0);
-        if (i1 != i0) finish(i1, g1, y1);
-    }
+    for_each_pair(n, load, finish);
 }
 
 constexpr int EW_GRID = 2048;        // max blocks of an element-wise pass (grid-stride loops)
@@ -1357,7 +1238,7 @@ bool unsupported_c(int C) { return (C >> 2) > NT || (NT % (C >> 2)) != 0; }
 
 __global__ __launch_bounds__(NT) void split_planes_kernel(long long n8, long long run, const float* __restrict__ src, __bf16* __restrict__ dst) {
     for (long long i = blockIdx.x * (long long)NT + threadIdx.x; i < n8; i += (long long)gridDim.x * NT)
-        store_split8(dst, i * 8, run, load8(src, i * 8, 0));
+        store_split8(dst, i * 8, run, loadv<8>(src, i * 8, 0));
 }
 
 // mcg_split_planes_multi: up to 32 (source, run, destination) segments in one launch.  A BLOCK belongs to one segment (found in the
@@ -1374,7 +1255,54 @@ __global__ __launch_bounds__(NT) void split_planes_multi_kernel(SplitSegs sg) {
     __bf16* __restrict__ dst = sg.dst[s];
     const long long run = sg.run[s], n8 = sg.n8[s];
     for (long long i = (long long)((int)blockIdx.x - b0) * NT + threadIdx.x; i < n8; i += (long long)nb * NT)
-        store_split8(dst, i * 8, run, load8(src, i * 8, 0));
+        store_split8(dst, i * 8, run, loadv<8>(src, i * 8, 0));
+}
+
+// ---- launches of the BatchNorm / activation kernels for a run-time set of MCG_IO_* flags (compile-time in the kernels) ----
+template <int W> using width = std::integral_constant<int, W>;
+
+// f(std::integral_constant<int, IO>) for the IO of the list that equals io; the last of the list takes every other value
+template <int IO0, int... IOs, class F>
+void with_io(int io, F f) {
+    if constexpr (sizeof...(IOs) == 0) f(std::integral_constant<int, IO0>{});
+    else if (io == IO0) f(std::integral_constant<int, IO0>{});
+    else with_io<IOs...>(io, f);
+}
+
+// eight channels per thread: a bf16 (or split) tensor in the call, C % 8 == 0 and a channel-group count the block size divides
+bool wide_c(int io, int C) { return (io & 15) != 0 && (C & 7) == 0 && (C >> 3) <= NT && NT % (C >> 3) == 0; }
+bool split_out_ok(int io, int C, const float* stats) {      // MCG_IO_OUT_SPLIT: fp32 inputs, BatchNorm behind it, C % 16 == 0
+    return io == MCG_IO_OUT_SPLIT && stats && wide_c(io, C) && (C & 15) == 0;
+}
+// gx_bf16 of the backward entry points: MCG_IO_* flags (OUT = gx, Y = y, G = g_out).  In place only between tensors of one
+// element type; the split output never in place
+int check_bwd_io(const void* gx, const void* g_out, int io, int C, const float* stats) {
+    if (gx == g_out && !(io & MCG_IO_OUT_BF16) != !(io & MCG_IO_G_BF16)) return MCG_ERR_BAD_ARG;
+    if ((io & MCG_IO_OUT_SPLIT) && (gx == g_out || !split_out_ok(io, C, stats))) return MCG_ERR_UNSUPPORTED;
+    return MCG_OK;
+}
+double bessel_adjust(long long M) { return (double)M / (M - 1.0 > 1.0 ? M - 1.0 : 1.0); }     // running variance: m / max(m - 1, 1)
+
+void launch_bwd_partial(int io, int blocks, hipStream_t s, long long M, int C, long long rows_per_block, const float* g_out,
+                        const float* y, const float* stats, int act, float* part) {
+    const int in = io & (MCG_IO_Y_BF16 | MCG_IO_G_BF16);
+    auto launch = [&](auto w, auto ioc) {
+        hipLaunchKernelGGL((col_partial_kernel<1, decltype(w)::value, decltype(ioc)::value>), dim3(blocks), dim3(NT), 0, s, M, C, rows_per_block,
+                           g_out, y, stats, act, part);
+    };
+    if (stats && in && wide_c(io, C)) with_io<2, 4, 6>(in, [&](auto ioc) { launch(width<8>{}, ioc); });
+    else with_io<0, 2, 4, 6>(in, [&](auto ioc) { launch(width<4>{}, ioc); });
+}
+void launch_bwd_apply(int io, hipStream_t s, long long M, int C, const float* g_out, const float* y, const float* stats,
+                      const float* coef, int act, float* gx) {
+    auto launch = [&](auto w, auto ioc) {
+        constexpr int W = decltype(w)::value;
+        const long long n = M * (C >> LOG2<W>);
+        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<W, decltype(ioc)::value>), dim3(ew_grid(n)), dim3(NT), 0, s, n, C, g_out, y, stats, coef, act, gx);
+    };
+    if (io & MCG_IO_OUT_SPLIT) launch(width<8>{}, std::integral_constant<int, MCG_IO_OUT_SPLIT>{});
+    else if (stats && wide_c(io, C)) with_io<1, 2, 3, 4, 5, 6, 7>(io & 7, [&](auto ioc) { launch(width<8>{}, ioc); });
+    else with_io<0, 1, 2, 3, 4, 5, 6, 7>(io & 7, [&](auto ioc) { launch(width<4>{}, ioc); });
 }
 
 }  // namespace
@@ -1394,8 +1322,7 @@ extern "C" int mcg_bn_stats(int64_t M, int C, const float* y, const float* gamma
     PartPlan pl = plan_partial(M, C);
     float* part = (float*)workspace;
     hipLaunchKernelGGL(col_partial_kernel<0>, dim3(pl.blocks), dim3(NT), 0, s, (long long)M, C, pl.rows_per_block, y, nullptr, nullptr, 0, part);
-    double adjust = (double)M / (M - 1.0 > 1.0 ? M - 1.0 : 1.0);
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_SL), 0, s, pl.blocks, C, 1.0 / (double)M, adjust,
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_SL), 0, s, pl.blocks, C, 1.0 / (double)M, bessel_adjust(M),
                        part, gamma, beta, stats, avg_mean, avg_var, eps, decay, 0LL);
     return launch_status();
 }
@@ -1404,94 +1331,42 @@ extern "C" int mcg_bn_stats_from_partials(int64_t M, int C, const float* part, i
                                           float* stats, float* avg_mean, float* avg_var, float eps, float decay, void* workspace, void* stream) {
     if (!part || !gamma || !beta || !stats || M <= 0 || bad_c(C) || n_slots <= 0 || slot_stride < 2 * C) return MCG_ERR_BAD_ARG;
     if ((avg_mean == nullptr) != (avg_var == nullptr)) return MCG_ERR_BAD_ARG;
-    double adjust = (double)M / (M - 1.0 > 1.0 ? M - 1.0 : 1.0);
     const Folded f = fold_slots(part, n_slots, slot_stride, C, (float*)workspace, (hipStream_t)stream);
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_SL), 0, (hipStream_t)stream, f.n, C, 1.0 / (double)M,
-                       adjust, f.part, gamma, beta, stats, avg_mean, avg_var, eps, decay, f.stride);
+                       bessel_adjust(M), f.part, gamma, beta, stats, avg_mean, avg_var, eps, decay, f.stride);
     return launch_status();
 }
 
 extern "C" int mcg_bn_act_fwd(int64_t M, int C, int c_valid, const float* y, int64_t y_rows_per_item, int64_t y_item_stride,
                               const float* scale_shift, int act, const float* addend,
                               float sigma, uint64_t seed, uint64_t stream_id, void* out, int out_bf16, void* stream) {
-    if (!y || !out || M <= 0 || C <= 0 || (C & 3)) return MCG_ERR_BAD_ARG;
+    if (!y || !out || M <= 0 || bad_c(C)) return MCG_ERR_BAD_ARG;
     if (y_rows_per_item < 0 || (y_rows_per_item > 0 && (M % y_rows_per_item || (y_item_stride & 3)))) return MCG_ERR_BAD_ARG;
-    long long n4 = (long long)M * (C >> 2);
     if (out_bf16 & ~(MCG_IO_OUT_BF16 | MCG_IO_Y_BF16 | MCG_IO_OUT_SPLIT)) return MCG_ERR_BAD_ARG;
     if ((out_bf16 & MCG_IO_OUT_SPLIT) && out_bf16 != MCG_IO_OUT_SPLIT) return MCG_ERR_BAD_ARG;
-#define MCG_FWD(IO_) hipLaunchKernelGGL(bn_act_fwd_kernel<IO_>, dim3(ew_grid(n4)), dim3(NT), 0, (hipStream_t)stream, n4, C, c_valid, y, \
-                       (long long)y_rows_per_item * (C >> 2), (long long)y_item_stride, scale_shift, act,                             \
-                       addend, sigma, seed, stream_id, (float*)out)
-    // bf16 networks (C % 8 == 0, dense y, every channel valid, a channel-group count the block size divides): eight channels per thread
-    const bool wide = out_bf16 != 0 && (C & 7) == 0 && y_rows_per_item == 0 && c_valid == C && NT % (C >> 3 < NT ? C >> 3 : NT) == 0 && (C >> 3) <= NT;
-#define MCG_FWD8(IO_) hipLaunchKernelGGL(bn_act_fwd8_kernel<IO_>, dim3(ew_grid(n4 / 2)), dim3(NT), 0, (hipStream_t)stream, n4 / 2, C, y, scale_shift, act, \
-                       addend, sigma, seed, stream_id, (float*)out)
-    if (out_bf16 == MCG_IO_OUT_SPLIT) {                        // the eight-channel kernel only (a 16-byte piece of each plane per thread)
-        if (!wide || (C & 15)) return MCG_ERR_UNSUPPORTED;
-        MCG_FWD8(8);
-    } else if (wide) { switch (out_bf16) { case 1: MCG_FWD8(1); break; case 2: MCG_FWD8(2); break; default: MCG_FWD8(3); } }
-    else
-    switch (out_bf16) { case 0: MCG_FWD(0); break; case 1: MCG_FWD(1); break; case 2: MCG_FWD(2); break; default: MCG_FWD(3); }
-#undef MCG_FWD8
-#undef MCG_FWD
+    // the eight-wide kernel takes dense y with every channel valid; the split output exists there only (a 16-byte piece of each plane per thread)
+    const bool wide = wide_c(out_bf16, C) && y_rows_per_item == 0 && c_valid == C;
+    if (out_bf16 == MCG_IO_OUT_SPLIT && (!wide || (C & 15))) return MCG_ERR_UNSUPPORTED;
+    auto launch = [&](auto w, auto ioc) {
+        constexpr int W = decltype(w)::value;
+        const long long n = (long long)M * (C >> LOG2<W>);
+        hipLaunchKernelGGL((bn_act_fwd_kernel<W, decltype(ioc)::value>), dim3(ew_grid(n)), dim3(NT), 0, (hipStream_t)stream, n, C, c_valid, y,
+                           (long long)y_rows_per_item * (C >> LOG2<W>), (long long)y_item_stride, scale_shift, act, addend, sigma, seed, stream_id,
+                           (float*)out);
+    };
+    if (wide) with_io<1, 2, 8, 3>(out_bf16, [&](auto ioc) { launch(width<8>{}, ioc); });
+    else with_io<0, 1, 2, 3>(out_bf16, [&](auto ioc) { launch(width<4>{}, ioc); });
     return launch_status();
-}
-
-// launches of the two BatchNorm-backward kernels for a run-time set of MCG_IO_* flags (compile-time in the kernels)
-static bool wide_c(int io, int C) { return (io & 15) != 0 && (C & 7) == 0 && (C >> 3) <= NT && NT % (C >> 3) == 0; }
-static bool split_out_ok(int io, int C, const float* stats) {      // MCG_IO_OUT_SPLIT: fp32 inputs, BatchNorm behind it, C % 16 == 0
-    return io == MCG_IO_OUT_SPLIT && stats && wide_c(io, C) && (C & 15) == 0;
-}
-
-static void launch_bwd_partial(int io, int blocks, hipStream_t s, long long M, int C, long long rows_per_block, const float* g_out,
-                               const float* y, const float* stats, int act, float* part) {
-    if (stats && (io & (MCG_IO_Y_BF16 | MCG_IO_G_BF16)) && wide_c(io, C)) {
-#define MCG_CP8(IO_) hipLaunchKernelGGL((col_partial8_kernel<IO_>), dim3(blocks), dim3(NT), 0, s, M, C, rows_per_block, g_out, y, stats, act, part)
-        switch (io & (MCG_IO_Y_BF16 | MCG_IO_G_BF16)) {
-            case MCG_IO_Y_BF16: MCG_CP8(MCG_IO_Y_BF16); break;
-            case MCG_IO_G_BF16: MCG_CP8(MCG_IO_G_BF16); break;
-            default: MCG_CP8(MCG_IO_Y_BF16 | MCG_IO_G_BF16);
-        }
-#undef MCG_CP8
-        return;
-    }
-#define MCG_CP(IO_) hipLaunchKernelGGL((col_partial_kernel<1, IO_>), dim3(blocks), dim3(NT), 0, s, M, C, rows_per_block, g_out, y, stats, act, part)
-    switch (io & (MCG_IO_Y_BF16 | MCG_IO_G_BF16)) {
-        case 0: MCG_CP(0); break;
-        case MCG_IO_Y_BF16: MCG_CP(MCG_IO_Y_BF16); break;
-        case MCG_IO_G_BF16: MCG_CP(MCG_IO_G_BF16); break;
-        default: MCG_CP(MCG_IO_Y_BF16 | MCG_IO_G_BF16);
-    }
-#undef MCG_CP
-}
-static void launch_bwd_apply(int io, hipStream_t s, long long n4, int C, const float* g_out, const float* y, const float* stats,
-                             const float* coef, int act, float* gx) {
-    if (io & MCG_IO_OUT_SPLIT) {
-        hipLaunchKernelGGL(bn_act_bwd_apply8_kernel<MCG_IO_OUT_SPLIT>, dim3(ew_grid(n4 / 2)), dim3(NT), 0, s, n4 / 2, C, g_out, y, stats, coef, act, gx);
-        return;
-    }
-    if (stats && wide_c(io, C)) {
-#define MCG_AP8(IO_) case IO_: hipLaunchKernelGGL(bn_act_bwd_apply8_kernel<IO_>, dim3(ew_grid(n4 / 2)), dim3(NT), 0, s, n4 / 2, C, g_out, y, stats, coef, act, gx); break
-        switch (io & 7) { MCG_AP8(1); MCG_AP8(2); MCG_AP8(3); MCG_AP8(4); MCG_AP8(5); MCG_AP8(6); default: MCG_AP8(7); }
-#undef MCG_AP8
-        return;
-    }
-#define MCG_AP(IO_) case IO_: hipLaunchKernelGGL(bn_act_bwd_apply_kernel<IO_>, dim3(ew_grid(n4)), dim3(NT), 0, s, n4, C, g_out, y, stats, coef, act, gx); break
-    switch (io & 7) { MCG_AP(0); MCG_AP(1); MCG_AP(2); MCG_AP(3); MCG_AP(4); MCG_AP(5); MCG_AP(6); MCG_AP(7); }
-#undef MCG_AP
 }
 
 extern "C" int mcg_bn_act_bwd(int64_t M, int C, const float* g_out, const float* y, const float* stats, const float* gamma, int act,
                               void* gx, int gx_bf16, float* dgamma, float* dbeta, void* workspace, void* stream) {
-    if (!g_out || !y || !gx || M <= 0 || C <= 0 || (C & 3)) return MCG_ERR_BAD_ARG;
-    // gx_bf16: MCG_IO_* flags (OUT = gx, Y = y, G = g_out).  In place only between tensors of one element type
-    if (gx == (const void*)g_out && !(gx_bf16 & MCG_IO_OUT_BF16) != !(gx_bf16 & MCG_IO_G_BF16)) return MCG_ERR_BAD_ARG;
-    if ((gx_bf16 & MCG_IO_OUT_SPLIT) && (gx == (const void*)g_out || !split_out_ok(gx_bf16, C, stats))) return MCG_ERR_UNSUPPORTED;
+    if (!g_out || !y || !gx || M <= 0 || bad_c(C)) return MCG_ERR_BAD_ARG;
+    if (const int bad = check_bwd_io(gx, g_out, gx_bf16, C, stats)) return bad;
     hipStream_t s = (hipStream_t)stream;
-    long long n4 = (long long)M * (C >> 2);
     float* coef = nullptr;
     if (stats) {
-        if (!gamma || !workspace || bad_c(C)) return MCG_ERR_BAD_ARG;
+        if (!gamma || !workspace) return MCG_ERR_BAD_ARG;
         if (unsupported_c(C)) return MCG_ERR_UNSUPPORTED;
         PartPlan pl = plan_partial(M, C);
         float* part = (float*)workspace;
@@ -1500,7 +1375,7 @@ extern "C" int mcg_bn_act_bwd(int64_t M, int C, const float* g_out, const float*
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_SL), 0, s, pl.blocks, C, 1.0 / (double)M, part, stats, gamma,
                            coef, dgamma, dbeta, 0LL);
     }
-    launch_bwd_apply(gx_bf16, s, n4, C, g_out, y, stats, coef, act, (float*)gx);
+    launch_bwd_apply(gx_bf16, s, (long long)M, C, g_out, y, stats, coef, act, (float*)gx);
     return launch_status();
 }
 
@@ -1508,15 +1383,13 @@ extern "C" int mcg_bn_act_bwd_from_partials(int64_t M, int C, const float* g_out
                                             const float* part, int n_slots, int slot_stride, void* gx, int gx_bf16, float* dgamma, float* dbeta,
                                             void* workspace, void* stream) {
     if (!g_out || !y || !gx || !stats || !gamma || !part || !workspace || M <= 0 || bad_c(C) || n_slots <= 0 || slot_stride < 2 * C) return MCG_ERR_BAD_ARG;
-    if (gx == (const void*)g_out && !(gx_bf16 & MCG_IO_OUT_BF16) != !(gx_bf16 & MCG_IO_G_BF16)) return MCG_ERR_BAD_ARG;
-    if ((gx_bf16 & MCG_IO_OUT_SPLIT) && (gx == (const void*)g_out || !split_out_ok(gx_bf16, C, stats))) return MCG_ERR_UNSUPPORTED;
+    if (const int bad = check_bwd_io(gx, g_out, gx_bf16, C, stats)) return bad;
     hipStream_t s = (hipStream_t)stream;
     float* coef = (float*)workspace + (long long)MAX_PART * 2 * C;
     const Folded f = fold_slots(part, n_slots, slot_stride, C, (float*)workspace, s);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_SL), 0, s, f.n, C, 1.0 / (double)M, f.part, stats, gamma,
                        coef, dgamma, dbeta, f.stride);
-    long long n4 = (long long)M * (C >> 2);
-    launch_bwd_apply(gx_bf16, s, n4, C, g_out, y, stats, coef, act, (float*)gx);
+    launch_bwd_apply(gx_bf16, s, (long long)M, C, g_out, y, stats, coef, act, (float*)gx);
     return launch_status();
 }
 
@@ -1542,8 +1415,7 @@ extern "C" int mcg_bn_stats_from_sums(int64_t M_total, int C, const double* sums
                                       float* avg_mean, float* avg_var, float eps, float decay, void* stream) {
     if (!sums || !gamma || !beta || !stats || M_total <= 0 || C <= 0) return MCG_ERR_BAD_ARG;
     if ((avg_mean == nullptr) != (avg_var == nullptr)) return MCG_ERR_BAD_ARG;
-    double adjust = (double)M_total / (M_total - 1.0 > 1.0 ? M_total - 1.0 : 1.0);
-    hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, C, 1.0 / (double)M_total, adjust, sums,
+    hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, C, 1.0 / (double)M_total, bessel_adjust(M_total), sums,
                        gamma, beta, stats, avg_mean, avg_var, eps, decay);
     return launch_status();
 }
@@ -1566,13 +1438,12 @@ extern "C" int mcg_bn_act_bwd_from_sums(int64_t M, int64_t M_total, int C, const
                                         int gx_bf16, float* dgamma, float* dbeta, void* workspace, void* stream) {
     if (!g_out || !y || !gx || !stats || !gamma || !local_sums || !global_sums || !workspace || M <= 0 || M_total < M || bad_c(C)) return MCG_ERR_BAD_ARG;
     if (gx_bf16 & ~7) return MCG_ERR_BAD_ARG;
-    if (gx == (const void*)g_out && !(gx_bf16 & MCG_IO_OUT_BF16) != !(gx_bf16 & MCG_IO_G_BF16)) return MCG_ERR_BAD_ARG;
+    if (const int bad = check_bwd_io(gx, g_out, gx_bf16, C, stats)) return bad;
     hipStream_t s = (hipStream_t)stream;
     float* coef = (float*)workspace + (long long)MAX_PART * 2 * C;
     hipLaunchKernelGGL(bn_bwd_from_sums_kernel, dim3((C + 63) / 64), dim3(64), 0, s, C, 1.0 / (double)M_total, local_sums, global_sums, stats, gamma,
                        coef, dgamma, dbeta);
-    long long n4 = (long long)M * (C >> 2);
-    launch_bwd_apply(gx_bf16, s, n4, C, g_out, y, stats, coef, act, (float*)gx);
+    launch_bwd_apply(gx_bf16, s, (long long)M, C, g_out, y, stats, coef, act, (float*)gx);
     return launch_status();
 }
 

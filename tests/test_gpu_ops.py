@@ -394,6 +394,189 @@ def test_batchnorm_activation_fwd_bwd(hl, C, M, act):
     assert rel_l2(cs, g_out.sum(0) + 1) < 1e-5
 
 
+def _act64(v, act):
+    return (v, np.maximum(v, 0), np.where(v >= 0, v, 0.2 * v), np.tanh(v))[act]
+
+
+def _bn_edge_fwd_bwd(hl, M, C, bf16, bn, act, seed, scale_shift=False, addend=False, sigma=0.0, split=False):
+    """Every form of bn_act_fwd / bn_act_bwd that the library accepts at one shape.  The all-fp32 form is held against float64;
+    every other form -- bf16 output, bf16 inputs (the same numbers as the fp32 run's), split output -- against that, bit for bit."""
+    rng = np.random.RandomState(seed)
+    bf, f32 = torch.bfloat16, torch.float32
+    y, g = dev(rng.randn(M, C) * 1.5 + 0.3), dev(rng.randn(M, C))
+    gamma, beta = 1 + 0.1 * rng.randn(C), 0.1 * rng.randn(C)
+    yb = y.to(bf)
+    if bf16:
+        y = yb.float()
+    y64 = y.double().cpu().numpy()
+    ws = torch.empty(hl.bn_workspace_floats(C), device="cuda")
+    stats = None
+    if bn:
+        stats, am, av = torch.empty(4 * C, device="cuda"), torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
+        hl.bn_stats(M, C, y, dev(gamma), dev(beta), stats, am, av, ws)
+        mean, var = y64.mean(0), y64.var(0) + 2e-5
+        istd = 1 / np.sqrt(var)
+        sc, sh = gamma * istd, beta - mean * gamma * istd
+        for got, want in zip(stats.view(4, C), (mean, istd, sc, sh)):
+            assert rel_l2(got, want) < 1e-5
+        assert rel_l2(am, 0.1 * mean) < 1e-5 and rel_l2(av, 0.9 + 0.1 * var * M / max(M - 1, 1)) < 1e-5
+        ss = stats[2 * C:]
+    elif scale_shift:
+        sc, sh = 1 + 0.1 * rng.randn(C), 0.1 * rng.randn(C)
+        ss = dev(np.concatenate([sc, sh]))
+    else:
+        sc, sh, ss = np.ones(C), np.zeros(C), None
+    pre = y64 * sc + sh
+    # the incoming gradient is zero where the pre-activation lies within 1e-4 of the activation's kink: the sign of an fp32 value
+    # that close to zero is not the float64 value's, and one flipped mask is worth more than BWD_TOL of the whole tensor
+    g = g * dev(np.abs(pre) > 1e-4)
+    gb = g.to(bf)
+    if bf16:
+        g = gb.float()
+    g64 = g.double().cpu().numpy()
+    forms = [(False, f32), (False, bf)] + ([(True, f32), (True, bf)] if bf16 else [])      # (inputs held in bf16, output type)
+
+    add = dev(0.2 * rng.randn(M, C)) if addend else None
+
+    def fwd(in16, odt, sig=0.0, split_out=False):
+        o = torch.full((M, 4 * C), 7.0, device="cuda", dtype=bf) if split_out else torch.empty((M, C), device="cuda", dtype=odt)
+        hl.bn_act_fwd(M, C, yb if in16 else y, ss, act, o, addend=add, sigma=sig, seed=11, stream_id=5, split_out=split_out)
+        return o
+
+    o32 = fwd(False, f32)
+    assert rel_l2(o32, _act64(pre, act) + (add.double().cpu().numpy() if addend else 0)) < FWD_TOL
+    for sig in (0.0, sigma) if sigma else (0.0,):
+        base = fwd(False, f32, sig)
+        if sig:             # element e takes normal e of the stream (fma(sigma, z, v) here, sigma * z rounded first in mcg_randn:
+            z = torch.empty(M * C, device="cuda")                       # 1.5 ulp of |v| < 32 apart at the most)
+            hl.randn(z, sig, 11, 5)
+            assert float((base - (o32 + z.view(M, C))).abs().max()) < 4e-6
+        for in16, odt in forms[1:]:
+            assert torch.equal(fwd(in16, odt, sig), base.to(odt)), ("fwd", in16, odt, sig)
+    if split:
+        want = hl.split_planes(o32, out=torch.full((M, 4 * C), 7.0, device="cuda", dtype=bf))
+        assert torch.equal(fwd(False, None, split_out=True).view(torch.int16), want.view(torch.int16))
+
+    gamma2 = dev(gamma * 1.01) if bn else None
+
+    def bwd(in16, odt, split_out=False):
+        o = torch.full((M, 4 * C), 7.0, device="cuda", dtype=bf) if split_out else torch.empty((M, C), device="cuda", dtype=odt)
+        dg, db = (torch.ones(C, device="cuda"), torch.ones(C, device="cuda")) if bn else (None, None)
+        hl.bn_act_bwd(M, C, gb if in16 else g, yb if in16 else y, stats, gamma2, act, o, dg, db, ws, split_out=split_out)
+        return o, dg, db
+
+    if not bn:
+        gx32 = bwd(False, f32)[0]
+        assert rel_l2(gx32, g64 * (1 - y64 * y64) if act == 3 else np.where(y64 > 0, g64, (0, 0, 0.2)[act] * g64)) < BWD_TOL
+        for in16, odt in forms[1:]:
+            assert torch.equal(bwd(in16, odt)[0], gx32.to(odt)), ("bwd", in16, odt)
+        return
+    gbn, xh = g64 * np.where(pre > 0, 1.0, (0, 0, 0.2)[act]), (y64 - mean) * istd
+    gg, gbeta = (gbn * xh).sum(0), gbn.sum(0)
+    gx_ref = 1.01 * gamma * istd * (gbn - (xh * gg + gbeta) / M)
+    for in16 in (False, True) if bf16 else (False,):
+        # fp32 and bf16 inputs sum the per-channel partials in different trees: each against float64, the bf16 output against
+        # the fp32 output of the same inputs
+        gx32, dg, db = bwd(in16, f32)
+        assert rel_l2(gx32, gx_ref) < BWD_TOL and rel_l2(dg, gg + 1) < BWD_TOL and rel_l2(db, gbeta + 1) < BWD_TOL, in16
+        gx16, dg16, db16 = bwd(in16, bf)
+        assert torch.equal(gx16, gx32.to(bf)) and torch.equal(dg16, dg) and torch.equal(db16, db), in16
+        if split and not in16:
+            # The split gradient comes from the eight-wide apply kernel, the fp32 one from the four-wide.  The compiler contracts
+            # gb - xh * k1 - k2 into other fused multiply-adds in the two, and in the eight-wide one it also fuses the last
+            # product k0 * (...) into the subtraction of the first plane, so mid and lo carry bits BELOW the fp32 value's last:
+            # the planes are neither split_planes(gx32) nor the split form of any fp32 tensor (measured at this shape: 35 of 592
+            # values differ from gx32, by up to 6 ulp; hi + mid + lo is no fp32 number for 518 of them).  The forward pass, whose
+            # fmaf is written out, is held to split_planes above.  Held here: the same per-channel sums; the first plane equal to
+            # the bf16 output of the same kernel, bit for bit; each further plane within half a bf16 ulp of the one before (what
+            # "the bf16 rounding of what the planes before left" means for the sizes); their sum against float64 and, to fp32
+            # accuracy, against gx32; the padding plane untouched.
+            gxs, dgs, dbs = bwd(False, None, split_out=True)
+            assert torch.equal(dgs, dg) and torch.equal(dbs, db)
+            hi, mid, lo, pad = (gxs.view(M, C // 16, 4, 16)[:, :, i].float() for i in range(4))
+            half_ulp = lambda t: torch.ldexp(torch.ones_like(t), torch.frexp(t).exponent - 9)      # of a bf16 value (8 significant bits)
+            assert bool((pad == 7.0).all()) and torch.equal(hi.reshape(M, C).to(bf), gx16)
+            assert bool((mid.abs() <= half_ulp(hi)).all()) and bool((lo.abs() <= half_ulp(mid)).all())
+            v = (hi.double() + mid.double() + lo.double()).reshape(M, C).cpu().numpy()
+            assert rel_l2(v, gx_ref) < BWD_TOL and rel_l2(v, gx32.double().cpu().numpy()) < FWD_TOL
+    if bf16:                # one input in bf16, the other the same numbers in fp32
+        for g_in, y_in in ((gb, y), (g, yb)):
+            o, dg, db = torch.empty((M, C), device="cuda"), torch.ones(C, device="cuda"), torch.ones(C, device="cuda")
+            hl.bn_act_bwd(M, C, g_in, y_in, stats, gamma2, act, o, dg, db, ws)
+            assert rel_l2(o, gx_ref) < BWD_TOL and rel_l2(dg, gg + 1) < BWD_TOL and rel_l2(db, gbeta + 1) < BWD_TOL
+
+
+EW_THREADS = 2048 * 256           # an element-wise grid is capped at this many threads: beyond as many channel groups a thread takes more than one
+BN_EDGE_CASES = {
+    "one-group": dict(M=1, C=4, bf16=False, bn=False, act=3),
+    "one-eight-wide-column": dict(M=37, C=8, bf16=True, bn=True, act=2),
+    "smallest-split-output": dict(M=37, C=16, bf16=False, bn=True, act=1, split=True),
+    "paired-trips-w4": dict(M=EW_THREADS + 300, C=4, bf16=False, bn=False, act=2, scale_shift=True, addend=True),
+    "paired-trips-w8": dict(M=EW_THREADS + 300, C=8, bf16=True, bn=True, act=2, sigma=0.2),
+    "moving-channel-group": dict(M=175000, C=12, bf16=False, bn=False, act=2, scale_shift=True),
+}
+
+
+@pytest.mark.parametrize("case", list(BN_EDGE_CASES) + ["padded-channel", "frame-view", "refusals"])
+def test_bn_elementwise_edge_shapes(hl, case):
+    """The smallest shapes at which each path of the BatchNorm / activation passes can go wrong: a single group (one thread, the
+    pair loop's tail branch), one eight-channel column (more row lanes than rows in the partial sums), the smallest split output,
+    more groups than a capped grid has threads (full pairs and half pairs in one launch, four and eight channels per thread), a
+    channel count whose groups move between a thread's trips (per-channel constants reloaded), the masked pad channel, the
+    frame-strided source view, and the shapes the library refuses."""
+    if case in BN_EDGE_CASES:
+        _bn_edge_fwd_bwd(hl, seed=list(BN_EDGE_CASES).index(case), **BN_EDGE_CASES[case])
+        return
+    torch.manual_seed(4)
+    if case == "padded-channel":
+        M, C = 1000, 4
+        y = torch.randn((M, C), device="cuda")
+        o3, o4 = torch.empty_like(y), torch.empty_like(y)
+        hl.bn_act_fwd(M, C, y, None, hl.ACT_LRELU, o3, sigma=0.2, seed=7, stream_id=3, c_valid=3)
+        hl.bn_act_fwd(M, C, y, None, hl.ACT_LRELU, o4, sigma=0.2, seed=7, stream_id=3, c_valid=4)
+        assert torch.equal(o3[:, :3], o4[:, :3]) and torch.equal(o3[:, 3], torch.where(y[:, 3] >= 0, y[:, 3], 0.2 * y[:, 3]))
+        assert not torch.equal(o3[:, 3], o4[:, 3])
+    elif case == "frame-view":
+        items, frames, rows, C = 6, 3, 5, 8                      # frame 1 of a [items][frames][rows][C] tensor
+        M = items * rows
+        ss = torch.cat([1 + 0.1 * torch.randn(C, device="cuda"), 0.1 * torch.randn(C, device="cuda")])
+        for dt in (torch.float32, torch.bfloat16):
+            clip = torch.randn((items, frames, rows, C), device="cuda").to(dt)
+            view, dense = clip[:, 1], clip[:, 1].contiguous()
+            assert view.data_ptr() == clip.data_ptr() + rows * C * clip.element_size() and not view.is_contiguous()
+            for sigma in (0.0, 0.2):
+                ov, od = torch.empty((M, C), device="cuda"), torch.empty((M, C), device="cuda")
+                hl.bn_act_fwd(M, C, view, ss, hl.ACT_LRELU, ov, sigma=sigma, seed=7, stream_id=3, rows_per_item=rows, item_stride=frames * rows * C)
+                hl.bn_act_fwd(M, C, dense.view(M, C), ss, hl.ACT_LRELU, od, sigma=sigma, seed=7, stream_id=3)
+                assert torch.equal(ov, od), (dt, sigma)
+                if sigma == 0.0:
+                    pre = dense.view(M, C).double().cpu().numpy() * ss[:C].double().cpu().numpy() + ss[C:].double().cpu().numpy()
+                    assert rel_l2(ov, _act64(pre, 2)) < FWD_TOL
+    else:
+        M = 64
+        ws = torch.empty(hl.bn_workspace_floats(64), device="cuda")
+        y, g = torch.randn((M, 24), device="cuda"), torch.randn((M, 24), device="cuda")
+        gamma, beta, stats = torch.ones(24, device="cuda"), torch.zeros(24, device="cuda"), torch.zeros(4 * 24, device="cuda")
+        with pytest.raises(hl.McgError, match="MCG_ERR_UNSUPPORTED"):           # 6 channel quads do not divide a block
+            hl.bn_stats(M, 24, y, gamma, beta, stats, None, None, ws)
+        with pytest.raises(hl.McgError, match="MCG_ERR_UNSUPPORTED"):
+            hl.bn_act_bwd(M, 24, g, y, stats, gamma, hl.ACT_LRELU, torch.empty_like(g), None, None, ws)
+        y8, s8 = torch.randn((M, 8), device="cuda"), torch.zeros((M, 32), device="cuda", dtype=torch.bfloat16)
+        with pytest.raises(hl.McgError, match="MCG_ERR_UNSUPPORTED"):           # split output wants C % 16 == 0
+            hl.bn_act_fwd(M, 8, y8, None, hl.ACT_RELU, s8, split_out=True)
+        assert not bool(s8.any())
+        C = 16                                                                   # split output over its own input gradient
+        store = torch.zeros(M * C * 2, device="cuda")
+        g16 = store[:M * C].view(M, C)
+        alias = torch.empty(0, dtype=torch.bfloat16, device="cuda").set_(store.untyped_storage(), 0, (M, 4 * C), (4 * C, 1))
+        assert alias.data_ptr() == g16.data_ptr()
+        y16 = torch.randn((M, C), device="cuda")
+        st = torch.cat([torch.zeros(C), torch.ones(C), torch.ones(C), torch.zeros(C)]).cuda()
+        with pytest.raises(hl.McgError, match="MCG_ERR_UNSUPPORTED"):
+            hl.bn_act_bwd(M, C, g16, y16, st, torch.ones(C, device="cuda"), hl.ACT_RELU, alias, None, None, ws, split_out=True)
+        assert not bool(store.any())
+
+
 def test_philox_noise_matches_oracle_stream(hl):
     n = 100003
     out = torch.empty(n, device="cuda")
