@@ -122,7 +122,8 @@ typedef struct mcg_conv_geom {
  * 3 = round 3 (mcg_randint, bf16 tensors in the synchronised-BatchNorm backward; round 2 changed mcg_bn_act_fwd / mcg_bn_act_bwd / mcg_adam_wd / mcg_conv_geom);
  * 6 = round 5 (mcg_split_planes_multi); 7 = round 6 (mcg_pack_clip_u8; nothing else changed);
  * 8 = the sampling path (mcg_bn_fold_deconv, mcg_clip_to_u8, MCG_ACT_RELU in mcg_conv_dgrad / mcg_conv_dgrad_ex; no argument list changed);
- *     still 8 with the averaged generator (mcg_adam_wd_ema, mcg_ema_multi added; no argument list changed). */
+ *     still 8 with the averaged generator (mcg_adam_wd_ema, mcg_ema_multi added; no argument list changed)
+ *     and with the differentiable augmentation (mcg_augment_* added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -341,6 +342,39 @@ int mcg_unpack_clip(int N, int C, int Cp, int T, int HW, const float* in, float*
  * model/updater.py:102). */
 int mcg_tanh_bwd_to_frames(int N, int T, int64_t frame_elems, const float* g_clip,
                            const float* x_clip, float* g_frames, void* stream);
+
+/* ---- differentiable augmentation of the discriminators' inputs -------------------------------------------------------------
+ * Zhao et al. 2020, "Differentiable Augmentation for Data-Efficient GAN Training", policy color,translation,cutout (no reference
+ * counterpart: model/updater.py:97-108 hands the clips to the discriminators as they are).  A clip is x[n][T][H][W][Cp], Cp = 4,
+ * with C = 1..3 valid channels; the pad channel is zero and stays zero.  Clip n has ONE parameter set for all its frames:
+ *   col[n] = (b, s, c, 0)                  brightness, saturation, contrast
+ *   geo[n] = (dx, dy, x0, x1, y0, y1, 0, 0) translation and the cutout rectangle (columns [x0, x1), rows [y0, y1), inside the frame)
+ * Forward, in the paper's order colour, translation, cutout (valid channels only):
+ *   v = x + b;   v = s v + (1 - s) mean_channels(v);   v = c v + (1 - c) m,   m = mean of x over the clip's T H W C elements + b
+ *   out(t, y, x) = v(t, y - dy, x - dx) if that source lies inside the frame and (y, x) outside the rectangle, else 0
+ * (b = 0, s = 1, c = 1, no shift, empty rectangle: out == x bit for bit).  The map is affine in x; mcg_augment_bwd is the adjoint of
+ * its linear part:
+ *   g1(t, sy, sx) = g_out(t, sy + dy, sx + dx) if that position lies inside the frame and outside the rectangle, else 0
+ *   g2 = c g1 + (1 - c) mean_clip(g1);   g_in = s g2 + (1 - s) mean_channels(g2)
+ * Each call is two launches: per-clip partial sums into `workspace` (mcg_augment_workspace_bytes(N) bytes, 8-byte aligned), then an
+ * apply pass that adds a clip's partial sums in a fixed order -- no float atomics, results are bit-reproducible run to run.
+ * The gather never forms an address outside the clip it reads.  MCG_ERR_BAD_ARG: a null pointer, C outside 1..3, a non-positive
+ * extent, in == out (a gather cannot run in place); MCG_ERR_UNSUPPORTED: Cp != 4 (or T*H*W > 2^28, N > 65535). */
+enum { MCG_AUG_COLOR = 1, MCG_AUG_TRANSLATION = 2, MCG_AUG_CUTOUT = 4 };
+int64_t mcg_augment_workspace_bytes(int N);
+int mcg_augment_fwd(int N, int C, int Cp, int T, int H, int W, const float* in, const int32_t* geo, const float* col,
+                    void* workspace, float* out, void* stream);
+int mcg_augment_bwd(int N, int C, int Cp, int T, int H, int W, const float* g_out, const int32_t* geo, const float* col,
+                    void* workspace, float* g_in, void* stream);
+/* The parameters of N clips from Philox4x32-10 keyed by (seed, stream_id) like every other draw: clip i takes the counters 2i and
+ * 2i + 1, i.e. the words w0..w7; with u(w) = (w >> 9) * 2^-23 (exact in fp32):
+ *   b = u(w0) - 0.5, s = 2 u(w1), c = u(w2) + 0.5;   dx = w3 % (2 (W/8) + 1) - W/8, dy likewise from w4 and H;
+ *   a W/2 x H/2 rectangle centred at cx = w5 % (W + 1), cy = w6 % (H + 1): columns [cx - W/4, cx - W/4 + W/2) clipped to [0, W),
+ *   rows likewise; w7 is not used.
+ * policy: a set of MCG_AUG_* flags; a component that is off gets its identity values (b = 0, s = c = 1; no shift; the empty
+ * rectangle 0, 0, 0, 0) but its words are consumed, so switching one component never changes another's draw.
+ * geo [N][8] int32, col [N][4] float as above. */
+int mcg_augment_draw(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, int32_t* geo, float* col, void* stream);
 
 /* ---- GRU motion-code recurrence (L.StatelessGRU, model/net.py:39-41,61-81) ------------------ */
 /* params: the six Linear links packed as [W_r|U_r|W_z|U_z|W|U], each (weights row-major

@@ -1305,6 +1305,177 @@ void launch_bwd_apply(int io, hipStream_t s, long long M, int C, const float* g_
     else with_io<0, 1, 2, 3, 4, 5, 6, 7>(io & 7, [&](auto ioc) { launch(width<4>{}, ioc); });
 }
 
+
+// ------------------------------------------------------------------------------------------
+// Differentiable augmentation of the discriminators' inputs (Zhao et al. 2020, policy color,translation,cutout; no reference
+// counterpart).  A clip is [T][H][W][4] with C <= 3 valid channels; one parameter set per clip: geo[8] = dx, dy, x0, x1, y0, y1, -, -
+// and col[4] = b, s, c, -.  The map is affine in x; mcg_augment_bwd is the adjoint of its linear part (include/mocogan_hip.h states
+// both).  Each direction is two launches: per-clip partial sums (doubles, one per block, AUG_MAX_BLOCKS slots per clip), then an
+// apply pass that folds the clip's slots in slot order -- no float atomics, results are bit-reproducible.
+// ------------------------------------------------------------------------------------------
+constexpr int AUG_MAX_BLOCKS = 64;           // partial-sum blocks (workspace slots) per clip
+constexpr int AUG_MIN_PIX = NT * 4;          // ... each of at least this many pixels
+
+struct AugPlan { int blocks; int pix_per_block; };
+AugPlan plan_augment(long long P) {
+    long long b = (P + AUG_MIN_PIX - 1) / AUG_MIN_PIX;
+    if (b > AUG_MAX_BLOCKS) b = AUG_MAX_BLOCKS;
+    AugPlan p;
+    p.pix_per_block = (int)((P + b - 1) / b);
+    p.blocks = (int)((P + p.pix_per_block - 1) / p.pix_per_block);
+    return p;
+}
+
+struct AugGeo { int dx, dy, x0, x1, y0, y1; };
+__device__ __forceinline__ AugGeo aug_geo(const int32_t* __restrict__ geo, int n) {
+    const int32_t* q = geo + 8 * (long long)n;
+    AugGeo a = {q[0], q[1], q[2], q[3], q[4], q[5]};
+    return a;
+}
+// the output position (y, x) is written from the clip: inside the frame and outside the cutout rectangle
+__device__ __forceinline__ bool aug_kept(const AugGeo& a, int y, int x, int H, int W) {
+    return y >= 0 && y < H && x >= 0 && x < W && !(x >= a.x0 && x < a.x1 && y >= a.y0 && y < a.y1);
+}
+// The gradient that reaches SOURCE pixel p = (t, sy, sx) of a clip: g at (t, sy + dy, sx + dx) where that position is kept, else 0.
+// The bounds are tested BEFORE the address is formed: a kept position lies inside the frame t of the same clip.
+__device__ __forceinline__ f32x4 aug_gather_bwd(const float* __restrict__ g_clip, const AugGeo& a, int p, int H, int W) {
+    const int sx = p % W, q = p / W, sy = q % H, t = q / H;
+    const int y = sy + a.dy, x = sx + a.dx;
+    f32x4 v = {};
+    if (aug_kept(a, y, x, H, W)) v = *reinterpret_cast<const f32x4*>(g_clip + ((long long)(t * H + y) * W + x) * 4);
+    return v;
+}
+__device__ __forceinline__ float aug_sum_valid(f32x4 v, int C) { return C == 3 ? (v[0] + v[1]) + v[2] : C == 2 ? v[0] + v[1] : v[0]; }
+
+// slot (n, block) = sum over the block's pixels and the C valid channels of x (forward) or of the gathered, masked g_out (BWD);
+// a thread adds its pixels in index order, the block's threads are combined by a fixed tree
+template <bool BWD>
+__global__ __launch_bounds__(NT) void augment_partial_kernel(int C, int P, int H, int W, int pix_per_block, const float* __restrict__ in,
+                                                             const int32_t* __restrict__ geo, double* __restrict__ part) {
+    __shared__ double red[NT];
+    const int n = blockIdx.y;
+    const float* clip = in + (long long)n * P * 4;
+    const AugGeo a = aug_geo(geo, n);
+    const int p0 = blockIdx.x * pix_per_block;
+    int p1 = p0 + pix_per_block; if (p1 > P) p1 = P;
+    double s = 0;
+    for (int p = p0 + threadIdx.x; p < p1; p += NT) {
+        const f32x4 v = BWD ? aug_gather_bwd(clip, a, p, H, W) : *reinterpret_cast<const f32x4*>(clip + (long long)p * 4);
+        s += (double)aug_sum_valid(v, C);
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = NT / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(long long)n * AUG_MAX_BLOCKS + blockIdx.x] = red[0];
+}
+
+// the clip's mean over its T*H*W*C valid elements from its slots, added in slot order (every thread of the launch the same way)
+__device__ __forceinline__ float aug_clip_mean(const double* __restrict__ part, int n, int nslots, double inv_count) {
+    double s = 0;
+    for (int k = 0; k < nslots; ++k) s += part[(long long)n * AUG_MAX_BLOCKS + k];
+    return (float)(s * inv_count);
+}
+
+// Every fused multiply-add of the two apply kernels is written out (adam_wd_elem's comment says why): s * v + (1 - s) * mu and
+// c * v + (1 - c) * m are fmaf(s, v, (1 - s) * mu) and fmaf(c, v, (1 - c) * m), so that b = 0, s = 1, c = 1 returns v itself.
+__global__ __launch_bounds__(NT) void augment_fwd_apply_kernel(int C, int P, int H, int W, int nslots, double inv_count,
+                                                               const float* __restrict__ in, const int32_t* __restrict__ geo,
+                                                               const float* __restrict__ col, const double* __restrict__ part,
+                                                               float* __restrict__ out) {
+    const int n = blockIdx.y;
+    const float* clip = in + (long long)n * P * 4;
+    float* oclip = out + (long long)n * P * 4;
+    const AugGeo a = aug_geo(geo, n);
+    const float b = col[4 * n], s = col[4 * n + 1], c = col[4 * n + 2];
+    const float m = aug_clip_mean(part, n, nslots, inv_count) + b;        // the clip mean after brightness (saturation keeps it)
+    const float ms = 1.f - s, cm = (1.f - c) * m, fc = (float)C;
+    for (int p = blockIdx.x * NT + threadIdx.x; p < P; p += gridDim.x * NT) {
+        const int x = p % W, q = p / W, y = q % H, t = q / H;
+        const int sy = y - a.dy, sx = x - a.dx;
+        f32x4 o = {};
+        // (the source is tested before its address is formed: it then lies in frame t of this clip)
+        if (sy >= 0 && sy < H && sx >= 0 && sx < W && aug_kept(a, y, x, H, W)) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(clip + ((long long)(t * H + sy) * W + sx) * 4);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = k < C ? v[k] + b : 0.f;
+            const float mu = aug_sum_valid(v, C) / fc;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) if (k < C) o[k] = fmaf(c, fmaf(s, v[k], ms * mu), cm);
+        }
+        *reinterpret_cast<f32x4*>(oclip + (long long)p * 4) = o;
+    }
+}
+
+__global__ __launch_bounds__(NT) void augment_bwd_apply_kernel(int C, int P, int H, int W, int nslots, double inv_count,
+                                                               const float* __restrict__ g_out, const int32_t* __restrict__ geo,
+                                                               const float* __restrict__ col, const double* __restrict__ part,
+                                                               float* __restrict__ g_in) {
+    const int n = blockIdx.y;
+    const float* clip = g_out + (long long)n * P * 4;
+    float* oclip = g_in + (long long)n * P * 4;
+    const AugGeo a = aug_geo(geo, n);
+    const float s = col[4 * n + 1], c = col[4 * n + 2];
+    const float ms = 1.f - s, cm = (1.f - c) * aug_clip_mean(part, n, nslots, inv_count), fc = (float)C;
+    for (int p = blockIdx.x * NT + threadIdx.x; p < P; p += gridDim.x * NT) {
+        f32x4 v = aug_gather_bwd(clip, a, p, H, W);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = k < C ? fmaf(c, v[k], cm) : 0.f;
+        const float mu = aug_sum_valid(v, C) / fc;
+        f32x4 o = {};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) if (k < C) o[k] = fmaf(s, v[k], ms * mu);
+        *reinterpret_cast<f32x4*>(oclip + (long long)p * 4) = o;
+    }
+}
+
+// clip i: Philox counters 2i, 2i + 1 of the stream -> words w0..w7 (w7 unused); a component the policy leaves out gets its
+// identity values, its words are consumed all the same
+__global__ __launch_bounds__(NT) void augment_draw_kernel(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id,
+                                                          int32_t* __restrict__ geo, float* __restrict__ col) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= N) return;
+    uint32_t w[8], r[4];
+    for (int h = 0; h < 2; ++h) {
+        const uint64_t ctr = 2ull * (uint64_t)i + h;
+        mcg::philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32), (uint32_t)seed,
+                           (uint32_t)(seed >> 32), r);
+        for (int k = 0; k < 4; ++k) w[4 * h + k] = r[k];
+    }
+    auto u = [](uint32_t v) { return (float)(v >> 9) * 1.1920928955078125e-07f; };       // 23 bits x 2^-23: exact in fp32
+    float b = 0.f, s = 1.f, c = 1.f;
+    int dx = 0, dy = 0, x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+    if (policy & MCG_AUG_COLOR) { b = u(w[0]) - 0.5f; s = 2.f * u(w[1]); c = u(w[2]) + 0.5f; }
+    if (policy & MCG_AUG_TRANSLATION) {
+        dx = (int)(w[3] % (uint32_t)(2 * (W / 8) + 1)) - W / 8;
+        dy = (int)(w[4] % (uint32_t)(2 * (H / 8) + 1)) - H / 8;
+    }
+    if (policy & MCG_AUG_CUTOUT) {
+        const int cx = (int)(w[5] % (uint32_t)(W + 1)), cy = (int)(w[6] % (uint32_t)(H + 1));
+        x0 = cx - W / 4; x1 = x0 + W / 2; y0 = cy - H / 4; y1 = y0 + H / 2;
+        x0 = x0 < 0 ? 0 : x0; x1 = x1 > W ? W : x1; y0 = y0 < 0 ? 0 : y0; y1 = y1 > H ? H : y1;
+    }
+    int32_t* q = geo + 8 * (long long)i;
+    q[0] = dx; q[1] = dy; q[2] = x0; q[3] = x1; q[4] = y0; q[5] = y1; q[6] = 0; q[7] = 0;
+    float* f = col + 4 * (long long)i;
+    f[0] = b; f[1] = s; f[2] = c; f[3] = 0.f;
+}
+
+int check_augment(int N, int C, int Cp, int T, int H, int W, const void* in, const void* geo, const void* col, const void* ws, const void* out) {
+    if (!in || !geo || !col || !ws || !out || N <= 0 || T <= 0 || H <= 0 || W <= 0 || C < 1 || C > 3) return MCG_ERR_BAD_ARG;
+    if (in == out) return MCG_ERR_BAD_ARG;                                     // a gather: never in place
+    if (Cp != 4) return MCG_ERR_UNSUPPORTED;
+    if ((long long)T * H * W > (1LL << 28) || N > 65535) return MCG_ERR_UNSUPPORTED;     // pixel indices of a clip are ints; N is gridDim.y
+    return MCG_OK;
+}
+int augment_apply_blocks(int N, long long P) {
+    long long b = (P + NT - 1) / NT, cap = EW_GRID / N;
+    if (cap < 1) cap = 1;
+    return (int)(b > cap ? cap : b);
+}
+
 }  // namespace
 
 extern "C" int mcg_version(void) { return MCG_ABI_VERSION; }
@@ -1706,5 +1877,37 @@ extern "C" int mcg_randint(int64_t n, int modulus, uint64_t seed, uint64_t strea
 extern "C" int mcg_randn(int64_t n, float sigma, uint64_t seed, uint64_t stream_id, float* out, void* stream) {
     if (!out || n <= 0) return MCG_ERR_BAD_ARG;
     hipLaunchKernelGGL(randn_kernel, dim3(ew_grid((n + 3) / 4)), dim3(NT), 0, (hipStream_t)stream, (long long)n, sigma, seed, stream_id, out);
+    return launch_status();
+}
+
+extern "C" int64_t mcg_augment_workspace_bytes(int N) { return N > 0 ? (int64_t)N * AUG_MAX_BLOCKS * (int64_t)sizeof(double) : 0; }
+
+extern "C" int mcg_augment_draw(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, int32_t* geo, float* col, void* stream) {
+    if (!geo || !col || N <= 0 || H <= 0 || W <= 0 || policy < 0 || policy > 7) return MCG_ERR_BAD_ARG;
+    hipLaunchKernelGGL(augment_draw_kernel, dim3((N + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, N, H, W, policy, seed, stream_id, geo, col);
+    return launch_status();
+}
+
+extern "C" int mcg_augment_fwd(int N, int C, int Cp, int T, int H, int W, const float* in, const int32_t* geo, const float* col,
+                               void* workspace, float* out, void* stream) {
+    if (int e = check_augment(N, C, Cp, T, H, W, in, geo, col, workspace, out)) return e;
+    const int P = T * H * W;
+    const AugPlan pl = plan_augment(P);
+    hipLaunchKernelGGL(augment_partial_kernel<false>, dim3(pl.blocks, N), dim3(NT), 0, (hipStream_t)stream, C, P, H, W, pl.pix_per_block, in, geo,
+                       (double*)workspace);
+    hipLaunchKernelGGL(augment_fwd_apply_kernel, dim3(augment_apply_blocks(N, P), N), dim3(NT), 0, (hipStream_t)stream, C, P, H, W, pl.blocks,
+                       1.0 / ((double)P * C), in, geo, col, (const double*)workspace, out);
+    return launch_status();
+}
+
+extern "C" int mcg_augment_bwd(int N, int C, int Cp, int T, int H, int W, const float* g_out, const int32_t* geo, const float* col,
+                               void* workspace, float* g_in, void* stream) {
+    if (int e = check_augment(N, C, Cp, T, H, W, g_out, geo, col, workspace, g_in)) return e;
+    const int P = T * H * W;
+    const AugPlan pl = plan_augment(P);
+    hipLaunchKernelGGL(augment_partial_kernel<true>, dim3(pl.blocks, N), dim3(NT), 0, (hipStream_t)stream, C, P, H, W, pl.pix_per_block, g_out, geo,
+                       (double*)workspace);
+    hipLaunchKernelGGL(augment_bwd_apply_kernel, dim3(augment_apply_blocks(N, P), N), dim3(NT), 0, (hipStream_t)stream, C, P, H, W, pl.blocks,
+                       1.0 / ((double)P * C), g_out, geo, col, (const double*)workspace, g_in);
     return launch_status();
 }

@@ -92,6 +92,10 @@ SIGNATURES = {
     "mcg_randint": (_I, [_I64, _I, _U64, _U64, _P, _P]),
     "mcg_split_planes": (_I, [_I64, _I64, _P, _P, _P]),
     "mcg_split_planes_multi": (_I, [_I, _P, _P]),
+    "mcg_augment_workspace_bytes": (_I64, [_I]),
+    "mcg_augment_draw": (_I, [_I, _I, _I, _I, _U64, _U64, _P, _P, _P]),
+    "mcg_augment_fwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mcg_augment_bwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 8          # MCG_ABI_VERSION of include/mocogan_hip.h these prototypes were written against
@@ -957,3 +961,66 @@ def split_planes(src, run=16, out=None):
 
 def randn(out, sigma, seed, stream_id):
     _check(load().mcg_randn(out.numel(), sigma, seed, stream_id, _p(_dense(out)), _stream()), "mcg_randn")
+
+
+# ---- differentiable augmentation of the discriminators' inputs (include/mocogan_hip.h: mcg_augment_*) ----------------------------
+AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
+AUG_NAMES = {'color': AUG_COLOR, 'translation': AUG_TRANSLATION, 'cutout': AUG_CUTOUT}
+
+
+def parse_augment(policy):
+    """'color,translation,cutout' (any subset, any order), a mask of AUG_* flags, or None / '' / 0 (off) -> the mask (0 = off)"""
+    if policy is None:
+        return 0
+    if isinstance(policy, bool):
+        raise ValueError('an augmentation policy is a string of names or a mask, got %r' % (policy,))
+    if isinstance(policy, int):
+        if not 0 <= policy <= 7:
+            raise ValueError('an augmentation mask lies in 0..7, got %r' % (policy,))
+        return policy
+    if not isinstance(policy, str):
+        raise ValueError('an augmentation policy is a string of names or a mask, got %r' % (policy,))
+    mask = 0
+    for name in policy.split(','):
+        name = name.strip()
+        if not name:
+            continue
+        if name not in AUG_NAMES:
+            raise ValueError('unknown augmentation %r (known: %s)' % (name, ', '.join(sorted(AUG_NAMES))))
+        mask |= AUG_NAMES[name]
+    return mask
+
+
+def augment_workspace(n, device):
+    """the caller-owned scratch of augment_fwd / augment_bwd on n clips (mcg_augment_workspace_bytes)"""
+    return torch.empty(load().mcg_augment_workspace_bytes(n) // 8, dtype=torch.float64, device=device)
+
+
+def augment_draw(n, H, W, policy, seed, stream_id, geo=None, col=None, device=None):
+    """the parameters of n clips from Philox stream (seed, stream_id): geo int32 [n][8], col float [n][4]"""
+    if geo is None:
+        geo = torch.empty((n, 8), dtype=torch.int32, device=device)
+        col = torch.empty((n, 4), dtype=torch.float32, device=device)
+    if geo.numel() < 8 * n or col.numel() < 4 * n:
+        raise McgError("augment_draw: a parameter tensor is smaller than the clip count")
+    _check(load().mcg_augment_draw(n, H, W, policy, seed, stream_id, _p(_dense(geo), torch.int32), _p(_dense(col)), _stream()),
+           "mcg_augment_draw")
+    return geo, col
+
+
+def _augment(fn, name, x, c, geo, col, ws, out):
+    n, T, H, W, cp = x.shape
+    if out.shape != x.shape or geo.numel() < 8 * n or col.numel() < 4 * n or ws.numel() * ws.element_size() < load().mcg_augment_workspace_bytes(n):
+        raise McgError("%s: a tensor is smaller than the extents passed" % name)
+    _check(fn(n, c, cp, T, H, W, _p(_dense(x)), _p(_dense(geo), torch.int32), _p(_dense(col)), _p(ws, ws.dtype), _p(_dense(out)), _stream()), name)
+    return out
+
+
+def augment_fwd(x, c, geo, col, ws, out):
+    """x [n][T][H][W][4] with c valid channels -> out, the augmented clips (parameters geo / col, one set per clip)"""
+    return _augment(load().mcg_augment_fwd, "mcg_augment_fwd", x, c, geo, col, ws, out)
+
+
+def augment_bwd(g_out, c, geo, col, ws, g_in):
+    """the adjoint of augment_fwd's linear part: gradient w.r.t. the augmented clips -> gradient w.r.t. the clips"""
+    return _augment(load().mcg_augment_bwd, "mcg_augment_bwd", g_out, c, geo, col, ws, g_in)

@@ -164,7 +164,7 @@ class TrainStep:
     """Holds the three networks, their Adam hyper-parameters and runs update_core on device data."""
 
     def __init__(self, model, gen, dis_i, dis_v, hyper=None, exchange=None, seed=0, rank=0, precision=None, overlap=False, sync_bn=False,
-                 input_ready_early=False, ema_decay=None):
+                 input_ready_early=False, ema_decay=None, augment=None):
         assert model in ('normal', 'cgan', 'infogan')
         self.model, self.gen, self.dis_i, self.dis_v = model, gen, dis_i, dis_v
         if precision is not None:                                 # 'f32' | 'bf16': MFMA operand type of every conv GEMM
@@ -175,6 +175,10 @@ class TrainStep:
         # average of its parameters and running statistics (gen.ema; ema_rate is the schedule), advanced by its Adam launch
         if ema_decay is not None:
             gen.enable_ema(ema_decay)
+        # augment: None = off (no launch, no allocation, no stream id more); 'color,translation,cutout' (any subset) or a mask of
+        # hl.AUG_* flags: differentiable augmentation (Zhao et al. 2020) of the real and the generated clips in front of BOTH
+        # discriminators, one parameter set per clip; the generator's gradient goes back through its adjoint.  No reference counterpart.
+        self.augment = hl.parse_augment(augment)
         self.hyper = hyper or {'image_gen': AdamHyper(), 'image_dis': AdamHyper(), 'video_dis': AdamHyper()}
         self.exchange = exchange
         # sync_bn (opt-in): BatchNorm statistics and their backward sums are all-reduced over the ranks, i.e.
@@ -230,7 +234,8 @@ class TrainStep:
         return hl.concat_label_planes(x_dev, c, dl, labels, out)
 
     # ---- perf-mode randomness bookkeeping ----------------------------------------------------------
-    STREAMS_PER_RANK = 64        # Philox stream ids one rank may consume per iteration (uses 5 x 8)
+    STREAMS_PER_RANK = 64        # Philox stream ids one rank may consume per iteration (uses 5 x 8, and 40 / 41 with augmentation)
+    AUG_STREAM_REAL, AUG_STREAM_FAKE = 40, 41     # ... the augmentation parameters of the real / the generated clips
     MAX_RANKS = 64
 
     def frame_index(self, it, T):
@@ -259,7 +264,11 @@ class TrainStep:
         iteration (what `input_ready_early` promises for resident data, here per call and checked by the hardware).
         inject: parity mode -- dict with 't', 'noise_{i,v}_{real,fake}' (lists of 4 device tensors in
         device layout, pre-scaled) and 'gen' (latent draw dict); None = perf mode (Philox in-kernel,
-        frame index from a seeded host generator shared by all ranks, quirk Q7)."""
+        frame index from a seeded host generator shared by all ranks, quirk Q7).  With augmentation on, parity mode also needs
+        'augment': {'real': (geo, col), 'fake': (geo, col)} -- int32 [n][8] and float [n][4] device tensors (mcg_augment_draw's
+        form); perf mode draws them in-kernel on stream ids base + 40 / 41.  The result then also holds 'x_real_aug', 'x_fake_aug'
+        (what the discriminators saw, without label planes), 'gx_aug' (the gradient w.r.t. x_fake_aug) and 'augment' (the
+        parameters); 'x_fake' / 'gx_fake' stay the un-augmented clip and the gradient w.r.t. it."""
         gen, di, dv = self.gen, self.dis_i, self.dis_v
         u8 = x_real.dtype == torch.uint8
         if u8:
@@ -283,20 +292,44 @@ class TrainStep:
         cgan = self.model == 'cgan'
         with_ce = self.model == 'infogan'
         cp = dv.cp0
+        aug = self.augment
+        aug_par = None
+        if aug:
+            if inject is None:
+                aug_par = {}                                         # (drawn where the clips are augmented: stream ids base + 40 / 41)
+            elif 'augment' not in inject:
+                raise ValueError("augmentation is on: parity mode needs inject['augment'] = {'real': (geo, col), 'fake': (geo, col)}")
+            else:
+                aug_par = dict(inject['augment'])
+
+        def augmented(x, which, sid):
+            """x [n][T][H][W][4] -> its augmented copy with the parameters of `which` ('real' | 'fake'), on the current stream"""
+            if which not in aug_par:
+                aug_par[which] = hl.augment_draw(n, H, W, aug, seed, base + sid, device=self.device)
+            geo, col = aug_par[which]
+            return hl.augment_fwd(x, c_img, geo, col, hl.augment_workspace(n, self.device), torch.empty_like(x))
 
         # ------------------------------------------------ forward: real
-        if cgan:
-            # label planes are part of D's input: build the device-layout clip once, then add noise
-            tmp = torch.empty((n, T, H, W, lay.pad4(c_img)), device=self.device)
-            (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, lay.pad4(c_img), T, hw, x_real, tmp)
-            xr = self._concat_label_clip(tmp, t_real)
-            c_valid = c_img + gen.dim_zl
+        x_real_aug = None
+        if cgan or aug:
+            # label planes (cgan) are part of D's input, and the augmentation reads whole clips: build the device-layout clip once
+            # -- packed without noise, augmented, label planes appended (they are not augmented) -- then add noise
+            real = {}
+
+            def build_real():
+                tmp = torch.empty((n, T, H, W, lay.pad4(c_img)), device=self.device)
+                (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, lay.pad4(c_img), T, hw, x_real, tmp)
+                if aug:
+                    tmp = augmented(tmp, 'real', self.AUG_STREAM_REAL)
+                real['aug'] = tmp if aug else None
+                real['x'] = self._concat_label_clip(tmp, t_real) if cgan else tmp
+            c_valid_r = c_img + (gen.dim_zl if cgan else 0)
 
             def first_real_v(out, na):
-                hl.bn_act_fwd(n * T * hw, cp, xr, None, hl.ACT_NONE, out, c_valid=c_valid, **na)
+                hl.bn_act_fwd(n * T * hw, cp, real['x'], None, hl.ACT_NONE, out, c_valid=c_valid_r, **na)
 
             def first_real_i(out, na):
-                hl.bn_act_fwd(n * hw, cp, xr[:, t], None, hl.ACT_NONE, out, c_valid=c_valid, rows_per_item=hw,
+                hl.bn_act_fwd(n * hw, cp, real['x'][:, t], None, hl.ACT_NONE, out, c_valid=c_valid_r, rows_per_item=hw,
                               item_stride=T * hw * cp, **na)
         else:
             def first_real_v(out, na):
@@ -313,7 +346,10 @@ class TrainStep:
         main = torch.cuda.current_stream()
         real_chain = None
         # (not for 'f32x3': measured 2-3 % SLOWER at 32 / 64 / 128 clips -- its launches are tuned, form by form, at the 2n batch)
-        if CHAINS and self.side is not None and ex is None and dv.sync_bn is None and dv.precision != 'f32x3' and n >= CHAINS_MIN_N:
+        use_chain = CHAINS and self.side is not None and ex is None and dv.sync_bn is None and dv.precision != 'f32x3' and n >= CHAINS_MIN_N
+        if (cgan or aug) and not (aug and use_chain):
+            build_real()                                             # on the main stream: every reader is ordered behind it
+        if use_chain:
             cs = self._chain_stream
             if (self.input_ready_early or input_event is not None) and self._ev_dv_updated is not None and not cgan:
                 cs.wait_event(self._ev_dv_updated)                   # the previous iteration's Adam(D_V)
@@ -321,6 +357,19 @@ class TrainStep:
                     cs.wait_event(input_event)                       # x_real (otherwise ready by contract)
             else:
                 cs.wait_stream(main)                                 # x_real (and whatever produced it)
+            if aug:
+                # the augmented real clips are made on the chain stream, which may run ahead of the main stream (input_event /
+                # input_ready_early): its own reader follows in stream order; the main stream -- D_I's side stream and the
+                # one-batch readers are ordered behind it -- waits for the event
+                with torch.cuda.stream(cs):
+                    build_real()
+                    ev = torch.cuda.Event()
+                    ev.record(cs)
+                main.wait_event(ev)
+                for x in {id(v): v for v in real.values() if v is not None}.values():
+                    x.record_stream(main)
+                    if self.side is not None:
+                        x.record_stream(self.side)
             with torch.cuda.stream(cs), self._dv_chains[0]:
                 real_chain = dv.forward(n, first_real_v, noise=nz('noise_v_real'), rng=rngs(1))
             x_real.record_stream(cs)
@@ -328,7 +377,12 @@ class TrainStep:
         draw = inject['gen'] if inject is not None else gen.draw(n, (seed, base + 8 * 2))
         x_fake, s_gen = gen.forward(n, draw)
         t_fake = draw['labels']
-        xf = self._concat_label_clip(x_fake, t_fake) if cgan else x_fake
+        if cgan or aug:
+            x_real_aug = real['aug']
+        x_fake_aug = augmented(x_fake, 'fake', self.AUG_STREAM_FAKE) if aug else None
+        xf = x_fake_aug if aug else x_fake
+        if cgan:
+            xf = self._concat_label_clip(xf, t_fake)
         c_valid = c_img + (gen.dim_zl if cgan else 0)
 
         def first_fake_v(out, na):
@@ -433,6 +487,10 @@ class TrainStep:
             di.backward(s_fake_i, gi, False, gx=gx[:, t], gx_geom=gi_geom, gx_accumulate=True)
         if cgan:                                                     # label planes carry no gradient to G: the clip's channels alone
             gx = hl.concat_label_planes(gx, c_img, 0, None, torch.empty_like(x_fake))
+        gx_aug = None
+        if aug:                                                      # the adjoint of the generated clips' augmentation
+            gx_aug = gx
+            gx = hl.augment_bwd(gx_aug, c_img, *aug_par['fake'], hl.augment_workspace(n, self.device), torch.empty_like(gx_aug))
         late_g = []
         lo_g, hi_g = gen.grad_bucket_late()
         gen.backward(s_gen, gx, on_late_bucket=(lambda: late_g.append(ex.start(gen.fp.g[lo_g:hi_g]))) if ex else None)
@@ -442,7 +500,8 @@ class TrainStep:
                 ex.finish(h)
         adam_update(gen, self.hyper['image_gen'], gs)
         self.iteration += 1
-        return {'x_fake': x_fake, 't_fake': t_fake, 't': t, 'gx_fake': gx, 'saved_gen': s_gen, 'saved_fake_i': s_fake_i, 'saved_fake_v': s_fake_v,
+        res = {} if not aug else {'x_real_aug': x_real_aug, 'x_fake_aug': x_fake_aug, 'gx_aug': gx_aug, 'augment': aug_par}
+        return {**res, 'x_fake': x_fake, 't_fake': t_fake, 't': t, 'gx_fake': gx, 'saved_gen': s_gen, 'saved_fake_i': s_fake_i, 'saved_fake_v': s_fake_v,
                 'saved_i': s_i, 'saved_v': s_v,
                 'y_real_i': y_real_i, 'y_real_v': y_real_v, 'y_fake_i': y_fake_i, 'y_fake_v': y_fake_v}
 

@@ -35,6 +35,8 @@ class Updater:
         sync_bn = kwargs.pop('sync_bn', False)
         # None: off; D in [0, 1): image_gen.ema is the exponential moving average of the generator (step.ema_rate)
         ema_decay = kwargs.pop('ema_decay', None)
+        # None: off; 'color,translation,cutout' (any subset) or a mask: differentiable augmentation in front of both discriminators
+        augment = kwargs.pop('augment', None)
         if kwargs:
             raise TypeError('unexpected arguments: %s' % sorted(kwargs))
         self.iteration = 0
@@ -42,7 +44,7 @@ class Updater:
         hyper = {k: self._optimizers[k].hyper() for k in ('image_gen', 'image_dis', 'video_dis')}
         self._step = _step.TrainStep(self.model, self.image_gen.impl, self.image_dis.impl, self.video_dis.impl,
                                      hyper=hyper, exchange=exchange, seed=seed, rank=rank, overlap=overlap,
-                                     precision=precision, sync_bn=sync_bn, ema_decay=ema_decay)
+                                     precision=precision, sync_bn=sync_bn, ema_decay=ema_decay, augment=augment)
 
     # ---- StandardUpdater surface -------------------------------------------------------------------
     def get_optimizer(self, name):

@@ -60,6 +60,8 @@ def main():
     ap.add_argument('--overlap', type=int, default=1)
     ap.add_argument('--ema_decay', type=float, default=0.0, help="train.py's flag: 0 = off, D in (0, 1) = the generator's Adam launch "
                                                                   "keeps the averaged generator as well")
+    ap.add_argument('--augment', default='', help="train.py's flag: '' = off, a subset of color,translation,cutout = differentiable "
+                                                  "augmentation in front of both discriminators")
     ap.add_argument('--out', default=os.path.join(ROOT, 'bench_train.json'))
     args = ap.parse_args()
 
@@ -105,7 +107,7 @@ def main():
     updater = Updater(model=args.model, models=(gen, di, dv), video_length=T_, img_size=64, channel=channel, dim_zl=num_labels,
                       iterator=it, tensorboard_writer=T.NullWriter(), optimizer={'image_gen': opt(gen), 'image_dis': opt(di), 'video_dis': opt(dv)},
                       device=0, seed=0, overlap=bool(args.overlap), precision=args.mfma,
-                      **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}))
+                      **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}), **(dict(augment=args.augment) if args.augment else {}))
     out_dir = '/tmp/mcg_bench_train'
 
     def run_to(n):
@@ -122,7 +124,7 @@ def main():
     dt = time.perf_counter() - t0
     rec = {"path": "train.py object graph: Trainer + Updater.update_core + %s" % type(it).__name__, "data": args.data,
            "loader_workers": args.loader_workers, "dtype": args.mfma, "model": args.model, "batch": args.batchsize, "iters": args.iters,
-           "ema_decay": args.ema_decay, "side_streams": bool(args.overlap), "two_chain_iterations": mstep.chain_iterations - chains0,
+           "ema_decay": args.ema_decay, "augment": args.augment, "side_streams": bool(args.overlap), "two_chain_iterations": mstep.chain_iterations - chains0,
            "clips_per_s": round(args.batchsize * args.iters / dt, 1), "ms_per_iteration": round(dt / args.iters * 1e3, 3),
            "epochs_seen": updater.epoch, "dataset_clips": args.size}
     print(json.dumps(rec), flush=True)

@@ -75,9 +75,18 @@ def parse_args(argv=None):
                    help="0 (default): off.  D in (0, 1): keep an exponential moving average of the generator's weights and running "
                         "statistics (decay min(D, (1 + k) / (10 + k)) at its k-th update), advanced inside the generator's Adam launch, "
                         "and write it as image_gen_ema_epoch_*.npz beside image_gen_epoch_*.npz (generate_samples.py reads either)")
+    p.add_argument('--augment', default='',
+                   help="'' (default): off.  A comma-separated subset of color,translation,cutout: differentiable augmentation (Zhao et "
+                        "al. 2020) of the real and the generated clips in front of both discriminators, one random parameter set per "
+                        "clip; the generator's gradient is carried back through it")
     args = p.parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0:
         p.error('--ema_decay must lie in [0, 1)')
+    try:
+        from mocogan_chainer_amd.hiplib import parse_augment
+        parse_augment(args.augment)
+    except ValueError as e:
+        p.error('--augment: %s' % e)
     return args
 
 
@@ -162,7 +171,7 @@ def main(argv=None):
                       img_size=size, channel=channel, dim_zl=num_labels, iterator=train_iter,
                       tensorboard_writer=writer, optimizer=opts, device=args.gpu, seed=args.seed, exchange=exchange, rank=rank,
                       overlap=bool(args.overlap), precision=args.mfma, sync_bn=bool(args.sync_bn),
-                      ema_decay=args.ema_decay if args.ema_decay > 0 else None)
+                      ema_decay=args.ema_decay if args.ema_decay > 0 else None, augment=args.augment or None)
 
     save_path = Path('result') / args.save_name
     trainer = T.Trainer(updater, (args.max_epoch, 'epoch'), out=save_path)
