@@ -104,6 +104,12 @@ typedef struct mcg_conv_geom {
                                 * bf16-stored or MCG_PREC_SPLIT operands; dgrad: Ci >= 128, or Ci = 64 as a 256x64 tile with two buffers (bf16-stored / split); wgrad: Co >= 128) -- fewer FLOP per LDS byte, but the
                                 * epilogue of one block runs under the K loop of the other and small launches divide evenly;
                                 * MCG_PREC_SPLIT launches accept 0 / 7 / 8 / 10 (+ 1000 / 2000 in fprop and dgrad) and, in dgrad, 9;
+                                * 17 / 20 = MCG_PREC_SPLIT only: tile 7 / 10 with the DENSE LDS form -- the padding plane of the
+                                * split layout is not brought into LDS (three K-steps hold the live planes of 64 channels, or of 64
+                                * pixels in wgrad: 3/4 of the loads, K-steps and barriers).  Needs 64 | Ci (fprop) / 64 | Co (dgrad),
+                                * mcg_conv_dense_split_ok(); MCG_ERR_UNSUPPORTED otherwise, and with any other precision.  Where one
+                                * block writes an output tile the result is bit for bit that of the padded form of the same tile;
+                                * K splits (+ 1000 / 2000) cover whole triples of K-steps (mcg_conv_dense_split_chunk());
                                 * +100 / +200 also fixes the K-step depth to 32 / 64; +1000 / +2000
                                 * makes mcg_conv_fprop / mcg_conv_dgrad split the K range over 2 / 4 blocks per tile
                                 * (partial tiles are added atomically onto a cleared output; for long-K layers with
@@ -149,6 +155,15 @@ int mcg_conv_dgrad(const mcg_conv_geom* g, const float* y, const float* w, const
  * dw must have been zeroed (or hold the other pass' gradient): the kernel adds with fp32
  * atomics (split-K over pixels). */
 int mcg_conv_wgrad(const mcg_conv_geom* g, const float* x, const float* y, float* dw, void* stream);
+
+/* The dense LDS form of MCG_PREC_SPLIT launches (tile codes 17 / 20), host-side queries that launch nothing.
+ * pass: 0 = fprop, 1 = dgrad, 2 = wgrad.  g->tile is read by mcg_conv_dense_split_chunk only (its K-split digit).
+ * mcg_conv_dense_split_ok: 1 when the geometry admits the form in that pass, 0 when not (or on a bad argument).
+ * mcg_conv_dense_split_chunk: the part of the summed dimension one block of such a launch covers -- split elements (4 per
+ * channel: a triple of K-steps is 256) in fprop / dgrad without an epilogue, pixels (a triple is 64) in wgrad; 0 when the form
+ * does not apply. */
+int mcg_conv_dense_split_ok(const mcg_conv_geom* g, int pass);
+int mcg_conv_dense_split_chunk(const mcg_conv_geom* g, int pass);
 
 /* ---- fused epilogues of mcg_conv_fprop / mcg_conv_dgrad ---------------------------------------------------
  * What the reference does as separate Chainer function calls right after (forward) or before (backward) a

@@ -54,6 +54,7 @@ struct Geom {
     int cv;            // channels of x that carry data (mcg_conv_geom.ci_valid; == Ci when unspecified)
     int split;         // MCG_PREC_SPLIT launch (split_geom): every fourth 16-channel plane of the K dimension is zero and never
                        // multiplied -- the LDS-DMA loaders leave its slots out of range instead of fetching zeros
+    int dense;         // MCG_PREC_SPLIT launch in the dense LDS form (tile codes 17 / 20): the loaders skip the padding planes
 };
 
 // Fused epilogue of fprop / dgrad (mcg_conv_epilogue on the device side).  mode == 0: the plain store.
@@ -135,12 +136,24 @@ __device__ __forceinline__ constexpr int sw_cols16(int row, int chunks_per_row) 
     return sw_cols(row, chunks_per_row) | ((row >> 3) & 1) << 1;
 }
 
+// Dense LDS image of split operands (policy flag DN, gemm_bf16_v2_kernel<..., SPLIT = 2>).  The global layout keeps its padding
+// plane; the LDS tile does not: the 12 live 32-byte plane-quarters of four consecutive groups (64 channels, or 64 pixels of a
+// weight gradient) fill three ordinary 128-byte K-steps, a "triple".  Dense quarter d = 4 s + q (step s of the triple, quarter q
+// of the tile row / 16-row block q of a tile in global orientation) is plane d % 3 of group d / 3, i.e. padded quarter
+// (d / 3) * 4 + d % 3 of the 256-element triple.  Only the loads' source offsets differ from the padded form.
+__device__ __forceinline__ constexpr int dense_group(int d) { return (d * 11) >> 5; }        // d / 3 for d < 12
+__device__ __forceinline__ constexpr int dense_src(int d) { return dense_group(d) * 64 + (d - 3 * dense_group(d)) * 16; }   // element offset in the padded triple
+// per-thread state of a DN policy: its k offset inside the padded triple for each of the three dense steps (nothing otherwise)
+template <bool DN> struct DenseOff { static constexpr int akd[3] = {0, 0, 0}; };
+template <> struct DenseOff<true> { int akd[3]; };
+
 // ---------------- fprop ----------------
 // NT: threads per block (the slot convention with NT threads); SW: the K-contiguous 16-byte slot a thread LOADS is XOR-swizzled
 // by its tile row, ((row >> 1) & 7) -- the source-side half of the LDS-DMA kernels' bank-conflict-free tile image (the
 // destination of an LDS-DMA load is lane-linear, so the permutation goes on the source address; gemm_bf16_v2_kernel).
-template <int BM, int BN, int BK, int E_ = 4, bool ST = false, int NT = NTHREADS, bool SW = false>
-struct FpropP {
+template <int BM, int BN, int BK, int E_ = 4, bool ST = false, int NT = NTHREADS, bool SW = false, bool DN = false>
+struct FpropP : DenseOff<DN> {
+    using DenseOff<DN>::akd;
     static constexpr bool A_KC = true, B_KC = true;
     static constexpr int ORDER = 0;
     static constexpr int E = E_, ESZ = 16 / E_, EA = E_, EB = E_;
@@ -158,6 +171,7 @@ struct FpropP {
     int abase[NA];      // BYTE offset of the window origin (may be negative: padding)
     u32 amask[NA];      // bit kh*4+kw set <=> that tap of the row reads inside the image
     int ak;             // this thread's k offset inside a K-step (c4*4)
+                        // (DN: akd[s] replaces it in dense step s, and bbase holds the row only)
     u32 bbase[NB];      // byte offset of the filter row, OOB for rows beyond Co
     int krot;           // 3-D layers: the K axis is visited rotated by ((-to) & 3) temporal taps, to = the tile's first
                         // output frame.  The four tiles that need input frame F (to = F-3..F, neighbours on one XCD,
@@ -175,6 +189,10 @@ struct FpropP {
             const int q0 = m0 >> (g.lgWo + g.lgHo);
             const int to0 = q0 - div_To(g, q0) * g.To;
             krot = ((4 - (to0 & 3)) & 3) * 16 * g.Ci;
+        }
+        if constexpr (DN) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s) akd[s] = dense_src(4 * s + (ak >> 4)) + (ak & 15);
         }
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
@@ -196,9 +214,9 @@ struct FpropP {
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             int co = n0 + tid / KC4 + RSTEP * j;
-            bbase[j] = co < g.Co ? (u32)(co * K + ak) * (u32)ESZ : OOB;
+            bbase[j] = co < g.Co ? (u32)(co * K + (DN ? 0 : ak)) * (u32)ESZ : OOB;
         }
-        if (E == 8 && g.split && (ak >> 4) == 3) {               // this thread's slots are the zero plane of a split operand
+        if (!DN && E == 8 && g.split && (ak >> 4) == 3) {        // this thread's slots are the zero plane of a split operand
 #pragma unroll
             for (int j = 0; j < NA; ++j) amask[j] = 0u;
 #pragma unroll
@@ -237,17 +255,18 @@ struct FpropP {
     // Only for layers whose K-steps lie inside one filter tap (channel count a power of two and a multiple of BK: v2_ok).
     __device__ __amdgpu_buffer_rsrc_t a_rsrc() const { return xr; }
     __device__ __amdgpu_buffer_rsrc_t b_rsrc() const { return wr; }
-    template <class F> __device__ void each_a(int k0, F&& f) const {
+    // DN: k0 is the first K-step of a padded triple and s the dense step inside it
+    template <class F> __device__ void each_a(int k0, F&& f, int s = 0) const {
         const int kr = rotated(k0);
         const int tap = kr >> g.lgCi, ci0 = kr & (g.Ci - 1), sp = tap & 15;
-        const int off = ((((tap >> 4) * g.Hi + (sp >> 2)) * g.Wi + (sp & 3)) * g.Ci + ci0 + ak) * ESZ;
+        const int off = ((((tap >> 4) * g.Hi + (sp >> 2)) * g.Wi + (sp & 3)) * g.Ci + ci0 + (DN ? akd[s] : ak)) * ESZ;
 #pragma unroll
         for (int j = 0; j < NA; ++j) f(j, (((~amask[j]) >> sp) << 31) | (u32)(abase[j] + off), 0u);
     }
-    template <class F> __device__ void each_b(int k0, F&& f) const {
+    template <class F> __device__ void each_b(int k0, F&& f, int s = 0) const {
         const u32 kb = (u32)rotated(k0) * (u32)ESZ;
 #pragma unroll
-        for (int j = 0; j < NB; ++j) f(j, bbase[j], kb);
+        for (int j = 0; j < NB; ++j) f(j, DN ? bbase[j] + (u32)(akd[s] * ESZ) : bbase[j], kb);
     }
     // plain epilogue: the row part of an output address is computed once per accumulator row (row_off), not per element
     static constexpr bool HAS_ROW_OFF = true;
@@ -290,8 +309,9 @@ struct FpropP {
 };
 
 // ---------------- dgrad (one output-parity class per blockIdx.z) ----------------
-template <int BM, int BN, int BK, int E_ = 4, bool ST = false, int NT = NTHREADS, bool SW = false>
-struct DgradP {
+template <int BM, int BN, int BK, int E_ = 4, bool ST = false, int NT = NTHREADS, bool SW = false, bool DN = false>
+struct DgradP : DenseOff<DN> {
+    using DenseOff<DN>::akd;
     static constexpr bool A_KC = true, B_KC = false;
     static constexpr int ORDER = 1;
     static constexpr int E = E_, ESZ = 16 / E_, EA = E_, EB = E_;
@@ -329,6 +349,10 @@ struct DgradP {
         }
         krot = 0;
         if (g.kt == 4 && (4 * g.Co) % BK == 0) krot = (tmin & 3) * 4 * g.Co;      // whole K-steps must stay inside one temporal tap
+        if constexpr (DN) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s) akd[s] = dense_src(4 * s + (ak >> 4)) + (ak & 15);
+        }
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
             int m = m0 + tid / KC4 + RSTEP * j;
@@ -356,9 +380,10 @@ struct DgradP {
         for (int j = 0; j < NB; ++j) {
             bkrow[j] = tid / C4 + (NT / C4) * j;
             bfast[j] = bok ? (u32)(bkrow[j] * g.taps * g.Ci + bci) * (u32)ESZ : OOB;
-            if (E == 8 && g.split && (bkrow[j] >> 4) == 3) bfast[j] = OOB;       // the zero plane of a split filter
+            if (!DN && E == 8 && g.split && (bkrow[j] >> 4) == 3) bfast[j] = OOB;       // the zero plane of a split filter
+            if (DN) bfast[j] = bok ? (u32)bci * (u32)ESZ : OOB;                         // (the row is chosen per dense step: each_b)
         }
-        if (E == 8 && g.split && (ak >> 4) == 3) {               // ... and of the split y rows
+        if (!DN && E == 8 && g.split && (ak >> 4) == 3) {        // ... and of the split y rows
 #pragma unroll
             for (int j = 0; j < NA; ++j) amask[j] = 0u;
         }
@@ -366,20 +391,25 @@ struct DgradP {
     // LDS-DMA kernels (as FpropP::each_a / each_b; layers with Co a power of two and a multiple of BK)
     __device__ __amdgpu_buffer_rsrc_t a_rsrc() const { return yr; }
     __device__ __amdgpu_buffer_rsrc_t b_rsrc() const { return wr; }
-    template <class F> __device__ void each_a(int k0, F&& f) const {
+    template <class F> __device__ void each_a(int k0, F&& f, int s = 0) const {
         const int kr = rotated(k0);
         const int ts = kr >> g.lgCo, co0 = kr & (g.Co - 1);
-        const int off = (co0 + ak - (((ts >> 2) * g.Ho + ((ts >> 1) & 1)) * g.Wo + (ts & 1)) * g.Co) * ESZ;
+        const int off = (co0 + (DN ? akd[s] : ak) - (((ts >> 2) * g.Ho + ((ts >> 1) & 1)) * g.Wo + (ts & 1)) * g.Co) * ESZ;
 #pragma unroll
         for (int j = 0; j < NA; ++j) f(j, (((~amask[j]) >> ts) << 31) | (u32)(abase[j] + off), 0u);
     }
-    template <class F> __device__ void each_b(int k0r, F&& f) const {
+    template <class F> __device__ void each_b(int k0r, F&& f, int s = 0) const {
         const int k0 = rotated(k0r);
         const int ts = k0 >> g.lgCo, co0 = k0 & (g.Co - 1);
         const int tap = (ts >> 2) * 16 + ((1 - ph) + (ts & 2)) * 4 + (1 - pw) + 2 * (ts & 1);
         const u32 base = (u32)((co0 * g.taps + tap) * g.Ci) * (u32)ESZ;
 #pragma unroll
-        for (int j = 0; j < NB; ++j) f(j, bfast[j], base);
+        for (int j = 0; j < NB; ++j) {
+            if constexpr (DN) {       // k row r of dense step s: 16-row block r >> 4 is dense quarter 4 s + (r >> 4)
+                const int row = dense_src(4 * s + (bkrow[j] >> 4)) + (bkrow[j] & 15);
+                f(j, bfast[j] + (u32)(row * g.taps * g.Ci) * (u32)ESZ, base);
+            } else f(j, bfast[j], base);
+        }
     }
     __device__ int k_begin(int z) const { return (z >> 2) * kchunk; }
     __device__ int k_end(int z) const { int e = ((z >> 2) + 1) * kchunk; return e < K ? e : K; }
@@ -519,7 +549,8 @@ struct DgradP {
 // 16 pixels and the kernel's SPLIT phase forms the six products; k counts quarter pixels (K-steps of 64 = 16 pixels).
 // EA_ (MCG_PREC_BF16_Y16, register-staged kernels): elements per 16-byte slot of the A operand (y) when it differs from the B
 // operand's (x): 8 = y bf16 in memory beside an fp32 x.
-template <int BM, int BN, int BK, int E_ = 4, int NT = NTHREADS, bool SW = false, bool SPL = false, int EA_ = E_>
+// DN (with SPL): the dense form -- the k rows of a triple of K-steps are 12 blocks of 16 rows, 3 planes x 4 groups of 16 pixels.
+template <int BM, int BN, int BK, int E_ = 4, int NT = NTHREADS, bool SW = false, bool SPL = false, int EA_ = E_, bool DN = false>
 struct WgradP {
     static constexpr bool HAS_EPI = false;
     static constexpr bool HAS_ROW_OFF = false;
@@ -554,22 +585,27 @@ struct WgradP {
     // LDS-DMA kernels (as FpropP::each_a / each_b)
     __device__ __amdgpu_buffer_rsrc_t a_rsrc() const { return yr; }
     __device__ __amdgpu_buffer_rsrc_t b_rsrc() const { return xr; }
-    template <class F> __device__ void each_a(int k0, F&& f) const {
+    template <class F> __device__ void each_a(int k0, F&& f, int s = 0) const {
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-            if constexpr (SPL) {
+            if constexpr (SPL && DN) {
+                const int d = 4 * s + (akrow[j] >> 4), grp = dense_group(d), plane = d - 3 * grp;
+                const int pix = (k0 >> 2) + 16 * grp + (akrow[j] & 15);
+                f(j, pix < Mpix ? aoff + (u32)(pix * 4 * g.Co + plane * 16) * 2u : OOB, 0u);
+            } else if constexpr (SPL) {
                 const int plane = akrow[j] >> 4, pix = (k0 >> 2) + (akrow[j] & 15);
                 f(j, plane < 3 ? aoff + (u32)(pix * 4 * g.Co + plane * 16) * 2u : OOB, 0u);       // (pixels beyond Mpix: beyond the buffer)
             } else f(j, aoff + (u32)((k0 + akrow[j]) * g.Co) * (u32)ESZA, 0u);
         }
     }
-    template <class F> __device__ void each_b(int k0, F&& f) const {
+    template <class F> __device__ void each_b(int k0, F&& f, int s = 0) const {
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            int pix = SPL ? (k0 >> 2) + (bkrow[j] & 15) : k0 + bkrow[j];
+            const int dq = 4 * s + (bkrow[j] >> 4), dgrp = DN ? dense_group(dq) : 0;
+            int pix = SPL ? (k0 >> 2) + 16 * dgrp + (bkrow[j] & 15) : k0 + bkrow[j];
             bool ok = bok && pix < Mpix;
             if constexpr (SPL) {
-                const int plane = bkrow[j] >> 4;
+                const int plane = DN ? dq - 3 * dgrp : bkrow[j] >> 4;
                 const int wo = pix & (g.Wo - 1), ho = (pix >> g.lgWo) & (g.Ho - 1), q = pix >> (g.lgWo + g.lgHo);
                 const int n = div_To(g, q), to = q - n * g.To;
                 const int hi = 2 * ho - 1 + bkh, wi = 2 * wo - 1 + bkw;
@@ -1379,6 +1415,27 @@ __device__ __forceinline__ void rowwise_epilogue(const P& p, f32x16 (&acc)[TM][T
 // ------------------------------------------------------------------------------------------
 #define MCG_LDSP(p) ((__attribute__((address_space(3))) void*)(p))
 
+// Dense split form, wait bookkeeping.  Product P of a triple (0..23: group P / 6, product c = P % 6) multiplies planes up to
+// max(pa, pb) = {0, 1, 1, 2, 1, 2}[c] of its group, i.e. dense quarters up to 3 (P / 6) + that.  dense_need: the highest quarter
+// of step s that product P needs (-1: only carried ones); dense_had: the highest one the products P0 .. P0 + n - 1 needed.
+__device__ __forceinline__ constexpr int dense_need(int P, int s) {
+    const int c = P % 6, top = 3 * (P / 6) + (c == 0 ? 0 : (c == 3 || c == 5) ? 2 : 1);
+    return top / 4 == s ? top % 4 : -1;
+}
+// dense_at: the product of step s (0-based within the step) in front of which quarter q is read; dense_younger: how many
+// quarters after w have been read when product n of the step is about to issue.
+__device__ __forceinline__ constexpr int dense_at(int s, int q) { return (s == 1 && q == 3) ? 5 : (s == 2 && q >= 2) ? 3 : 0; }
+__device__ __forceinline__ constexpr int dense_younger(int s, int w, int n) {
+    int c = 0;
+    for (int q = w + 1; q < 4; ++q) c += dense_at(s, q) <= n ? 1 : 0;
+    return c;
+}
+__device__ __forceinline__ constexpr int dense_had(int P0, int n, int s) {
+    int h = -1;
+    for (int i = 0; i < n; ++i) { const int q = dense_need(P0 + i, s); h = q > h ? q : h; }
+    return h;
+}
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
@@ -1388,6 +1445,12 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // channels x 4 planes (hi, mid, lo, padding), i.e. the 128-byte K-step of a tile row is ONE group -- k chunk kc of the row is plane kc.
 // The MFMA phase then forms the six products hi.hi, hi.mid, mid.hi, hi.lo, mid.mid, lo.hi of a group (everything down to 2^-24
 // of the fp32 product) instead of the four chunk-by-chunk products of a bf16 K-step.  Loads, ring, images, epilogue: unchanged.
+// SPLIT == 2, the dense form (policies with DN): the padding plane never reaches LDS.  The loop body is a TRIPLE of ring steps that
+// holds the 12 live plane-quarters of four groups (see dense_src):
+//     step 0: hi g | mid g | lo g | hi g+1      step 1: mid g+1 | lo g+1 | hi g+2 | mid g+2      step 2: lo g+2 | hi g+3 | mid g+3 | lo g+3
+// Fragments that outlive their step stay in registers (hi g+1; hi, mid g+2).  The products keep the padded form's order per
+// accumulator -- group after group, six products each: 7 + 8 + 9 over the three steps -- so a tile written by one block is bit
+// for bit the padded form's.  Three quarters of the LDS-DMA instructions, K-steps and barriers for the same MFMAs.
 template <class P, int BM, int BN, int STAGES, int EPI = 0, int SPLIT = 0>
 __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     // P::E == 8: bf16 operands, BK = 64, v_mfma_f32_32x32x16_bf16.  P::E == 4: fp32 operands, BK = 32, v_mfma_f32_32x32x2_f32 --
@@ -1437,17 +1500,19 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     const int kend = p.k_end(z);
     const __amdgpu_buffer_rsrc_t ar = p.a_rsrc(), br = p.b_rsrc();
     // slot j of this thread is the 16-byte LDS position tid + NT2 * j of its tile: piece (wave, j) starts at wave KiB + 8 j KiB
-    auto issue = [&](int k, int buf) {
+    constexpr bool DENSE = SPLIT == 2;
+    constexpr int KADV = DENSE ? 4 * BK : BK;                    // k covered by one pass of the loop body (dense: a padded triple)
+    auto issue = [&](int k, int buf, int s = 0) {                // (s: dense step of the triple at k)
         unsigned char* sa = smem + buf * STAGE + wave * 1024;
         unsigned char* sb = sa + A_BYTES;
         const bool live = k < kend;
-        const int kk = live ? k : kend - BK;                     // past the end: the offsets are forced out of range (zeros land in
+        const int kk = live ? k : kend - KADV;                   // past the end: the offsets are forced out of range (zeros land in
         p.each_a(kk, [&](int j, u32 vo, u32 so) {                // a buffer nobody reads), which keeps the vmcnt arithmetic uniform
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, MCG_LDSP(sa + j * 8192), 16, live ? vo : OOB, so, 0, 0);
-        });
+        }, s);
         p.each_b(kk, [&](int j, u32 vo, u32 so) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(br, MCG_LDSP(sb + j * 8192), 16, live ? vo : OOB, so, 0, 0);
-        });
+        }, s);
     };
 
     // In the K loop the loads of a step are not issued in one burst (every LDS-DMA instruction holds its wave's issue for ~60-180
@@ -1455,11 +1520,11 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
     // step's four MFMA groups: offsets first (plain VALU), then PIECES / 4 loads in front of each group.
     static_assert(PIECES <= 8, "offset arrays");
     u32 dvo[8], dso[8];             // (a dependent bound, u32 dvo[PIECES], made the HOST pass drop the kernel's stub: hipcc 7.2)
-    auto plan = [&](int k) {
+    auto plan = [&](int k, int s = 0) {
         const bool live = k < kend;
-        const int kk = live ? k : kend - BK;
-        p.each_a(kk, [&](int j, u32 vo, u32 so) { dvo[j] = live ? vo : OOB; dso[j] = so; });
-        p.each_b(kk, [&](int j, u32 vo, u32 so) { dvo[NA + j] = live ? vo : OOB; dso[NA + j] = so; });
+        const int kk = live ? k : kend - KADV;
+        p.each_a(kk, [&](int j, u32 vo, u32 so) { dvo[j] = live ? vo : OOB; dso[j] = so; }, s);
+        p.each_b(kk, [&](int j, u32 vo, u32 so) { dvo[NA + j] = live ? vo : OOB; dso[NA + j] = so; }, s);
     };
     auto issue_part = [&](int buf, int part) {                 // pieces [part * PIECES / 4, (part + 1) * PIECES / 4) of the planned step
         unsigned char* sa = smem + buf * STAGE + wave * 1024;
@@ -1537,6 +1602,89 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
 
     int k_cur = p.next_valid(p.k_begin(z));
     if (block_idle(p, k_cur, kend, 0)) return;                   // (before the first LDS-DMA load is in flight)
+    constexpr bool TRA_ = !P::A_KC && !F32, TRB_ = !P::B_KC && !F32;   // operands read with the transposing read (inline asm)
+    // bf16 tiles: EVERY fragment read is inline asm (see ds128_issue) and counted here; NRD = LDS reads per k chunk, in issue order
+    // A (TM rows x 1 or 2 reads) then B.  (fp32 tiles: plain loads, counted by the compiler.)
+    constexpr int NRD = F32 ? 0 : (TRA_ ? 2 * TM : TM) + (TRB_ ? 2 * TN : TN);
+    if constexpr (DENSE) {
+        static_assert(!F32 && !M16, "dense split operands are bf16 planes on the 32x32x16 MFMA");
+#pragma unroll
+        for (int s = 0; s < STAGES - 1; ++s) issue(k_cur, s, s);                     // (STAGES - 1 <= 2: steps of the first triple)
+        int k_next = k_cur < kend ? p.next_valid(k_cur + KADV) : kend;
+        int buf = 0;
+        while (k_cur < kend) {
+            // dense quarter d of the triple (slot d): plane d % 3 of group d / 3, read from quarter d % 4 of step d / 4's buffer
+            bf16x8 qa[12][TM], qb[12][TN];
+            s16x4 qalo[12][TRA_ ? TM : 1], qahi[12][TRA_ ? TM : 1], qblo[12][TRB_ ? TN : 1], qbhi[12][TRB_ ? TN : 1];
+            static_for<0, 3>([&](auto s_) {
+                constexpr int s = decltype(s_)::value;
+                wait_vmcnt<(STAGES - 2) * PIECES>();             // as the padded loop: one barrier per ring step
+                __builtin_amdgcn_s_barrier();
+                constexpr int ahead = s + STAGES - 1;            // the step whose loads go out now: of this triple or of the next
+                int nbuf = buf + STAGES - 1; nbuf = nbuf >= STAGES ? nbuf - STAGES : nbuf;
+                plan(ahead >= 3 ? k_next : k_cur, ahead % 3);
+                const u32 sb32 = lds_addr(smem + buf * STAGE);
+                auto read_q = [&](auto q_) {                     // the fragments of quarter q of this step's buffer
+                    constexpr int q = decltype(q_)::value, d = 4 * s + q;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+                        if constexpr (P::A_KC) {
+                            if (i == 0) ds128_issue<0>(qa[d][0], sb32 + a_row + xo[q]);
+                            else if (i == 1) ds128_issue<4096>(qa[d][i], sb32 + a_row + xo[q]);
+                            else if (i == 2) ds128_issue<8192>(qa[d][i], sb32 + a_row + xo[q]);
+                            else ds128_issue<12288>(qa[d][i], sb32 + a_row + xo[q]);
+                        } else tr16_issue<q * 16 * (BM * 2), q * 16 * (BM * 2) + 4 * (BM * 2)>(qalo[d][i], qahi[d][i], sb32 + ta[i]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < TN; ++i) {
+                        if constexpr (P::B_KC) {
+                            if (i == 0) ds128_issue<0>(qb[d][0], sb32 + b_row + xo[q]);
+                            else if (i == 1) ds128_issue<4096>(qb[d][i], sb32 + b_row + xo[q]);
+                            else if (i == 2) ds128_issue<8192>(qb[d][i], sb32 + b_row + xo[q]);
+                            else ds128_issue<12288>(qb[d][i], sb32 + b_row + xo[q]);
+                        } else tr16_issue<q * 16 * (BN * 2), q * 16 * (BN * 2) + 4 * (BN * 2)>(qblo[d][i], qbhi[d][i], sb32 + tb[i]);
+                    }
+                };
+                // products P0 .. P0 + NP - 1 of the triple's 24 (group P / 6, product P % 6 in the padded form's order).  The quarters
+                // are read in order, in front of product dense_at(s, q) of the step: at most four quarters of fragments are alive at a
+                // time (the reads of a group's later planes go out when the previous group's last product has been issued).  A quarter
+                // is waited for in front of the first product that needs it; every quarter of the step is needed inside the step, so
+                // all reads of the buffer have landed before the next barrier hands it back to the loads.
+                constexpr int P0 = s == 0 ? 0 : s == 1 ? 7 : 15, NP = 7 + s;
+                static_for<0, NP>([&](auto n_) {
+                    constexpr int n = decltype(n_)::value, grp = (P0 + n) / 6, c = (P0 + n) % 6;
+                    constexpr int pa = (c == 0 || c == 1 || c == 3) ? 0 : (c == 2 || c == 4) ? 1 : 2;
+                    constexpr int pb = (c == 0 || c == 2 || c == 5) ? 0 : (c == 1 || c == 4) ? 1 : 2;
+                    constexpr int need = dense_need(P0 + n, s), had = dense_had(P0, n, s);      // highest quarter of this step needed now / waited for so far
+                    static_for<0, 4>([&](auto q_) { if constexpr (dense_at(s, decltype(q_)::value) == n) read_q(q_); });
+                    if constexpr (n < 4) { issue_part(nbuf, n); __builtin_amdgcn_sched_barrier(0); }
+                    static_for<had + 1, need + 1>([&](auto w_) {
+                        constexpr int w = decltype(w_)::value, d = 4 * s + w;
+                        constexpr int YOUNGER = dense_younger(s, w, n) * NRD;          // reads issued after quarter w's, up to here
+                        constexpr int BEHIND = YOUNGER < 15 ? YOUNGER : 15;
+#pragma unroll
+                        for (int i = 0; i < TM; ++i) {
+                            if constexpr (TRA_) qa[d][i] = tr16_wait<BEHIND>(qalo[d][i], qahi[d][i]);
+                            else ds128_wait<BEHIND>(qa[d][i]);
+                        }
+#pragma unroll
+                        for (int i = 0; i < TN; ++i) {
+                            if constexpr (TRB_) qb[d][i] = tr16_wait<BEHIND>(qblo[d][i], qbhi[d][i]);
+                            else ds128_wait<BEHIND>(qb[d][i]);
+                        }
+                    });
+#pragma unroll
+                    for (int a = 0; a < TM; ++a)
+#pragma unroll
+                        for (int b = 0; b < TN; ++b)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[3 * grp + pa][a], qb[3 * grp + pb][b], acc[a][b], 0, 0, 0);
+                });
+                buf = buf + 1 == STAGES ? 0 : buf + 1;
+            });
+            k_cur = k_next;
+            k_next = k_cur < kend ? p.next_valid(k_cur + KADV) : kend;
+        }
+    } else {
     int k_nx[STAGES - 1];                                        // the K-steps whose loads are (to be) in flight
     {
         int k = k_cur;
@@ -1547,7 +1695,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             k_nx[s] = k;
         }
     }
-    constexpr bool TRA_ = !P::A_KC && !F32, TRB_ = !P::B_KC && !F32;   // operands read with the transposing read (inline asm)
     typedef typename std::conditional<F32, f32x4, bf16x8>::type frag_t;
     bf16x8 fa16[2][M16 ? TM16 : 1], fb16[2][M16 ? HB : 1];
     s16x4 blo16[2][M16 ? HB : 1], bhi16[2][M16 ? HB : 1];
@@ -1568,9 +1715,6 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             else ds128_issue<(h * HB + j) * 2048>(fb16[h][j], sb32 + b_row16 + xk[c]);
         });
     };
-    // bf16 tiles: EVERY fragment read is inline asm (see ds128_issue) and counted here; NRD = LDS reads per k chunk, in issue order
-    // A (TM rows x 1 or 2 reads) then B.  (fp32 tiles: plain loads, counted by the compiler.)
-    constexpr int NRD = F32 ? 0 : (TRA_ ? 2 * TM : TM) + (TRB_ ? 2 * TN : TN);
     auto frags = [&](auto kc_, const unsigned char* sbase, u32 sb32) {      // 32x32 MFMA: the fragments of k chunk kc
         constexpr int kc = decltype(kc_)::value, slot = kc & 1;
 #pragma unroll
@@ -1743,6 +1887,7 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
         }
         }
         buf = buf1;
+    }
     }
     wait_vmcnt<0>();                                             // the (dummy) loads still in flight write LDS: drain them before the
     __syncthreads();                                             // epilogue reuses the buffers
@@ -2899,6 +3044,10 @@ Extents extents(const Geom& g) {
 }
 bool fits(long long elems, int esz) { return elems * esz < (1ll << 31); }
 
+// Tile codes of the dense LDS form of split operands: 17 / 20 = tile 7 / 10.  (No 18: with the fragments of a 256x256 tile's
+// carried planes gemm_bf16_v2_kernel<.., SPLIT = 2> needs 40-92 bytes of scratch at two waves per SIMD; that tile keeps the padded form.)
+bool dense_code(int t) { return t == 17 || t == 20; }
+
 int make_geom(const mcg_conv_geom* c, Geom& g) {
     if (!c) return MCG_ERR_BAD_ARG;
     g.N = c->N; g.Ti = c->Ti; g.Hi = c->Hi; g.Wi = c->Wi; g.Ci = c->Ci;
@@ -2912,8 +3061,10 @@ int make_geom(const mcg_conv_geom* c, Geom& g) {
     if (c->ci_valid < 0 || c->ci_valid > c->Ci) return MCG_ERR_BAD_ARG;
     g.cv = c->ci_valid ? c->ci_valid : c->Ci;
     if (g.prec != MCG_PREC_F32 && g.prec != MCG_PREC_BF16 && g.prec != MCG_PREC_BF16_STORE && g.prec != MCG_PREC_SPLIT) return MCG_ERR_BAD_ARG;
-    if (c->tile < 0 || c->tile % 100 > 10 || (c->tile / 100) % 10 > 2 || c->tile / 1000 > 2) return MCG_ERR_BAD_ARG;
-    g.tile = c->tile % 100; g.bk = ((c->tile / 100) % 10) * 32; g.ksplit = 1 << (c->tile / 1000);
+    if (c->tile < 0 || (c->tile % 100 > 10 && !dense_code(c->tile % 100)) || (c->tile / 100) % 10 > 2 || c->tile / 1000 > 2) return MCG_ERR_BAD_ARG;
+    g.dense = dense_code(c->tile % 100) ? 1 : 0;                 // 17 / 20: tile 7 / 10 with the dense LDS form of split operands
+    if (g.dense && g.prec != MCG_PREC_SPLIT) return MCG_ERR_UNSUPPORTED;
+    g.tile = c->tile % 100 - 10 * g.dense; g.bk = ((c->tile / 100) % 10) * 32; g.ksplit = 1 << (c->tile / 1000);
     g.lgHo = ilog2_exact(g.Ho); g.lgWo = ilog2_exact(g.Wo);
     g.lgCi = ilog2_exact(g.Ci); g.lgCo = ilog2_exact(g.Co);
     if (g.N <= 0 || g.Ci <= 0 || g.Co <= 0) return MCG_ERR_BAD_ARG;
@@ -2944,6 +3095,13 @@ bool split_ok(const Geom& g, SplitDim d) {
     if (d == SPLIT_PIX) return fits(n.x, 8) && fits(n.y, 8) && (n.y / g.Co) % 16 == 0;
     const int c = d == SPLIT_CI ? g.Ci : g.Co;
     return c >= 16 && (c & (c - 1)) == 0 && fits(d == SPLIT_CI ? n.x : n.y, 8) && fits(n.w, 8);
+}
+// The dense LDS form of a split launch (mcg_conv_geom.tile 17 / 20): a triple of K-steps holds four groups of 16 channels and
+// must lie inside one filter tap -- 64 | Ci (fprop), 64 | Co (dgrad).  Along the pixels (wgrad) a triple is 64 pixels, the last
+// one of a block may reach beyond them.  The K range of a block is a whole number of triples (256 split elements; 64 pixels).
+bool dense_ok(const Geom& g, SplitDim d) {
+    if (!split_ok(g, d)) return false;
+    return d == SPLIT_PIX || ((d == SPLIT_CI ? g.Ci : g.Co) & 63) == 0;
 }
 Geom split_geom(const Geom& g, SplitDim d) {
     const Extents n = extents(g);
@@ -3110,27 +3268,32 @@ bool v2_ok(const Geom& g, int kdim /* channel count along K: Ci (fprop), Co (dgr
     return (g.prec == MCG_PREC_BF16_STORE || g.prec == MCG_PREC_F32) && kdim >= 64 && (kdim & (kdim - 1)) == 0 && g.ksplit == 1;
 }
 constexpr size_t v2_lds(int BM, int BN, int STAGES) { return (size_t)STAGES * (BM + BN) * 128; }
+// K covered by one pass of the kernel's loop body, the unit of a K split: a K-step of 64, or the dense form's padded triple
+constexpr int V2_KSTEP(int SPLIT) { return SPLIT == 2 ? 256 : 64; }
 
 // K-steps of 64, >= 16 per block (split-K, tile codes + 1000 / + 2000: the few tiles of a late layer on more CUs); class 2
 // (BatchNorm's backward sums) with bf16-stored / split operands only
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_fprop_v2(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
-    using Pol = FpropP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true>;
+    if constexpr (SPLIT == 2 && BM == 256 && BN == 256) return MCG_ERR_UNSUPPORTED;     // (spills: see dense_code)
+    else {
+    using Pol = FpropP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true, SPLIT == 2>;
     return with_epi<PM == 2 ? 2 : 1>(e, [&](auto epi) -> int {
         Pol p; dim3 grid;
-        if (int st = plan_fprop<BM, BN>(p, grid, g, x, w, bias, y, e, ep, 64, 16, s)) return st;
+        if (int st = plan_fprop<BM, BN>(p, grid, g, x, w, bias, y, e, ep, V2_KSTEP(SPLIT), 1024 / V2_KSTEP(SPLIT), s)) return st;
         return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, epi, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
     });
+    }
 }
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_dgrad_v2(const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
     // not instantiated: 256x256 on split operands (three planes of fragments spill); 256x64 with two buffers on fp32 ones
     if constexpr ((SPLIT && BM == 256 && BN == 256) || (PM == 0 && BN == 64 && STAGES == 2)) return MCG_ERR_UNSUPPORTED;
     else {
-        using Pol = DgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true>;
+        using Pol = DgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, true, NT2, true, SPLIT == 2>;
         return with_epi<PM == 2 ? 2 : 1>(e, [&](auto epi) -> int {
             Pol p; dim3 grid;
-            if (int st = plan_dgrad<BM, BN>(p, grid, g, y, w, bias, x, act, acc, e, ep, 64, 16, s)) return st;
+            if (int st = plan_dgrad<BM, BN>(p, grid, g, y, w, bias, x, act, acc, e, ep, V2_KSTEP(SPLIT), 1024 / V2_KSTEP(SPLIT), s)) return st;
             return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, epi, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
         });
     }
@@ -3140,18 +3303,21 @@ int launch_dgrad_v2(const Geom& g, const float* y, const float* w, const float* 
 // splits would each add 128 x 256 atomics onto the SAME 0.5 MB of dw)
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_wgrad_v2(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
-    constexpr int BK = PM ? (SPLIT ? 16 : 64) : 32;              // PIXELS per K-step (split: 16 pixels x 4 planes = 64 k rows)
-    using Pol = WgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, NT2, true, SPLIT != 0>;
+    if constexpr (SPLIT == 2 && BM == 256 && BN == 256) return MCG_ERR_UNSUPPORTED;     // (spills: see dense_code)
+    else {
+    constexpr int BK = PM ? (SPLIT == 2 ? 64 : SPLIT ? 16 : 64) : 32;      // PIXELS per K-step (split: 16 pixels x 4 planes = 64 k rows; dense: per triple)
+    using Pol = WgradP<BM, BN, PM ? 64 : 32, PM ? 8 : 4, NT2, true, SPLIT != 0, PM ? 8 : 4, SPLIT == 2>;
     Pol p; dim3 grid;
-    plan_wgrad<BM, BN>(p, grid, g, x, y, dw, BK, 512, SPLIT ? 32 : 8);
+    plan_wgrad<BM, BN>(p, grid, g, x, y, dw, BK, 512, SPLIT == 2 ? 8 : SPLIT ? 32 : 8);
     return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
+    }
 }
 
 // operand form of an LDS-DMA launch -> (PM, SPLIT) of the launcher `fn`
-enum { FORM_F32, FORM_BF16S, FORM_SPLIT };
-int v2_form(const Geom& g) { return g.prec == MCG_PREC_SPLIT ? FORM_SPLIT : g.prec == MCG_PREC_F32 ? FORM_F32 : FORM_BF16S; }
+enum { FORM_F32, FORM_BF16S, FORM_SPLIT, FORM_DENSE };
+int v2_form(const Geom& g) { return g.prec == MCG_PREC_SPLIT ? (g.dense ? FORM_DENSE : FORM_SPLIT) : g.prec == MCG_PREC_F32 ? FORM_F32 : FORM_BF16S; }
 #define MCG_V2_FORMS(fn, BM, BN, STAGES, form, ...)                                                                     \
-    ((form) == FORM_SPLIT ? fn<BM, BN, STAGES, 2, 1>(__VA_ARGS__) : (form) == FORM_F32 ? fn<BM, BN, STAGES, 0>(__VA_ARGS__) : fn<BM, BN, STAGES, 2>(__VA_ARGS__))
+    ((form) == FORM_DENSE ? fn<BM, BN, STAGES, 2, 2>(__VA_ARGS__) : (form) == FORM_SPLIT ? fn<BM, BN, STAGES, 2, 1>(__VA_ARGS__) : (form) == FORM_F32 ? fn<BM, BN, STAGES, 0>(__VA_ARGS__) : fn<BM, BN, STAGES, 2>(__VA_ARGS__))
 
 // patch-stationary input gradient (tile code 9): one block per frame, all four output-parity classes
 bool dgrad_patch_ok(const Geom& g) {
@@ -3303,6 +3469,7 @@ int make_epi(const mcg_conv_epilogue* ep, const Geom& g, int pass, Epi& e) {
 //          (split, Co < 256: as 7)
 //   9      -                              dgrad_patch_kernel                         -
 //   10     LDS-DMA 128x128/2              128x128/2 (Ci = 64: 256x64/2, not fp32)    128x128/2
+//   17, 20 split operands only: as 7, 10 with the dense LDS form (SPLIT = 2; 64 | Ci)     (64 | Co)                  (any split wgrad)
 // dgrad, t = 0, Ci = 4 outside dgrad_c4_mfma_kernel's reach: dgrad_c4_kernel (VALU).  The LDS-DMA kernels take fp32,
 // bf16-stored or split operands (one dispatch on the form, MCG_V2_FORMS), tile 9 bf16-stored or split ones.
 
@@ -3324,6 +3491,7 @@ int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, cons
     int t = g.tile;
     if (split) {
         if ((t != 0 && t != 7 && t != 8 && t != 10) || !split_ok(g, SPLIT_CI) || e.out16) return MCG_ERR_UNSUPPORTED;
+        if (g.dense && !dense_ok(g, SPLIT_CI)) return MCG_ERR_UNSUPPORTED;
         if (!t) t = 7;
     } else if ((t == 0 || t == 6) && c4_fprop_ok(g, e)) {          // the 3-channel clip padded to 4: weight-stationary kernel
         if (ep) { ep->n_slots = 0; ep->slot_stride = e.slot_stride; }
@@ -3359,6 +3527,36 @@ extern "C" int mcg_conv_fprop_ex(const mcg_conv_geom* c, const float* x, const f
     if (ep) { ep->n_slots = 0; ep->slot_stride = 0; }
     return conv_fprop_impl(c, x, w, bias, y, ep, stream);
 }
+// ---- the dense split form: host-side queries (no launch) ----
+namespace {
+int dense_query_geom(const mcg_conv_geom* c, int pass, Geom& g) {
+    if (!c || pass < 0 || pass > 2) return MCG_ERR_BAD_ARG;
+    mcg_conv_geom cc = *c;
+    cc.precision = MCG_PREC_SPLIT;
+    if (!dense_code(cc.tile % 100)) cc.tile = 17 + (cc.tile / 1000) * 1000;
+    if (int st = make_geom(&cc, g)) return st;
+    if (!dense_ok(g, pass == 0 ? SPLIT_CI : pass == 1 ? SPLIT_CO : SPLIT_PIX)) return MCG_ERR_UNSUPPORTED;
+    if (pass == 1 && (g.Ci < 64 || (g.Ci & (g.Ci - 1)))) return MCG_ERR_UNSUPPORTED;
+    if (pass == 2 && (g.Co < 128 || (g.Co & 63) || g.Ci < 64 || (g.Ci & (g.Ci - 1)))) return MCG_ERR_UNSUPPORTED;
+    return MCG_OK;
+}
+}  // namespace
+extern "C" int mcg_conv_dense_split_ok(const mcg_conv_geom* c, int pass) {
+    Geom g;
+    return dense_query_geom(c, pass, g) == MCG_OK ? 1 : 0;
+}
+extern "C" int mcg_conv_dense_split_chunk(const mcg_conv_geom* c, int pass) {
+    Geom g;
+    if (dense_query_geom(c, pass, g) != MCG_OK) return 0;
+    if (pass == 2) {      // as launch_wgrad_v2<.., 2> plans it (the tile: 128x128 for code 20, 128x256 for 17)
+        const int bm = 128, bn = g.tile == 10 ? 128 : 256;
+        const int Mpix = g.N * g.To * g.Ho * g.Wo, tiles = ((g.Co + bm - 1) / bm) * ((g.taps * g.Ci + bn - 1) / bn);
+        return plan_pixsplit(Mpix, 64, wgrad_target(g, 512), tiles, 8).chunk;
+    }
+    const int K = pass == 0 ? g.taps * 4 * g.Ci : g.kt * 4 * 4 * g.Co;
+    return plan_ksplit(K, V2_KSTEP(2), g.ksplit, 1024 / V2_KSTEP(2)).chunk;
+}
+
 extern "C" int64_t mcg_conv_epilogue_part_bytes(const mcg_conv_geom* c, int pass, int groups) {
     if (!c || groups < 1 || groups > 2) return 0;
     const long long rows = pass == 0 ? (long long)c->N * c->To * c->Ho * c->Wo : (long long)c->N * c->Ti * c->Ho * c->Wo;
@@ -3390,6 +3588,7 @@ int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, cons
     int t = g.tile;
     if (split) {
         if ((t != 0 && t != 7 && t != 8 && t != 9 && t != 10) || !split_ok(g, SPLIT_CO) || e.out16) return MCG_ERR_UNSUPPORTED;
+        if (g.dense && !dense_ok(g, SPLIT_CO)) return MCG_ERR_UNSUPPORTED;
         if (!t) t = 7;
     } else {
         if ((t == 0 || t == 6) && g.prec != MCG_PREC_BF16_STORE && c4_dgrad_mfma_ok(g, e, bias, act, accumulate)) {

@@ -58,6 +58,8 @@ SIGNATURES = {
     "mcg_conv_fprop_ex": (_I, [_GP, _P, _P, _P, _P, _EP, _P]),
     "mcg_conv_dgrad_ex": (_I, [_GP, _P, _P, _P, _P, _EP, _P]),
     "mcg_conv_epilogue_part_bytes": (_I64, [_GP, _I, _I]),
+    "mcg_conv_dense_split_ok": (_I, [_GP, _I]),
+    "mcg_conv_dense_split_chunk": (_I, [_GP, _I]),
     "mcg_bn_stats_from_partials": (_I, [_I64, _I, _P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P]),
     "mcg_bn_act_bwd_from_partials": (_I, [_I64, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "mcg_colsum_from_partials": (_I, [_I, _P, _I, _I, _P, _P, _P]),
@@ -305,11 +307,18 @@ TILE_CANDIDATES = (0, 101, 102, 103, 201, 202, 203)     # (the long tiles 4 = 25
 FPROP_SPLIT_CANDIDATES = (1103, 1203, 1202, 2103, 2203, 2202)     # 2- / 4-way split-K: only when few tiles (see _tuned)
 WGRAD_SPLIT_CANDIDATES = (2007, 2008, 2010, 1010)      # LDS-DMA weight gradient with half / twice the pixel splits (few-tile layers)
 V2_CANDIDATES = (7, 8, 10)                              # gemm_bf16_v2_kernel (bf16-stored / split / fp32 operands): 256x128 / 256x256 (wgrad 128x256 / 256x256) one block per CU; 10 = 128x128, two blocks per CU
+DENSE_CANDIDATES = (17, 20)                             # MCG_PREC_SPLIT only: tiles 7 / 10 with the dense LDS form (no padding-plane slots; the library
+                                                        # refuses it where a triple of K-steps would straddle a tap: channels along the sum not a multiple of 64)
 _autotune = False
 _tile_cache = {}
 
 
 _PRETUNED = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_tiles_mi355x.json')
+# ... and the 'f32x3' launches of that table which take the DENSE LDS form instead (tile codes 17 / 20 in place of the table's
+# padded 7 / 8 / 9 / 10): [[key, dense code], ...], each measured faster than its padded entry by more than the padded form's own
+# spread (tools/ab_dense_split.py, profiles/dense_split_notes.md).  A list of its own, applied by set_autotune(True): the main
+# table and use_pretuned_table() stay the padded reference that the production-batch parity test pins against float64.
+_PRETUNED_DENSE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'dense_tiles_mi355x.json')
 
 
 def set_autotune(on, use_pretuned=True):
@@ -323,6 +332,8 @@ def set_autotune(on, use_pretuned=True):
         # 'f32x3' network takes (split on the bf16 pipe / fp32 MFMA) has no heuristic -- those entries are loaded either way,
         # otherwise such a network would silently run every GEMM on the fp32 kernels (round 4's advice)
         use_pretuned_table(only_split=not on)
+        if on:
+            use_dense_list()
 
 
 def autotune_on():
@@ -344,6 +355,20 @@ def use_pretuned_table(only_split=False):
     if os.path.exists(_PRETUNED) and os.environ.get('MCG_NO_PRETUNED') != '1':
         with open(_PRETUNED) as f:
             _merge_table(json.load(f), overwrite=False, only_split=only_split)
+
+
+def use_dense_list():
+    """Move the launches of dense_tiles_mi355x.json to their dense codes -- where the table holds the SHIPPED padded code for
+    them (a choice loaded from elsewhere, or tuned in this process, stays).  Part of set_autotune(True) with the shipped table;
+    MCG_DENSE_SPLIT=0 keeps the padded codes (A/B timing)."""
+    if not (os.path.exists(_PRETUNED) and os.path.exists(_PRETUNED_DENSE)) or os.environ.get('MCG_DENSE_SPLIT', '1') == '0':
+        return
+    with open(_PRETUNED) as f:
+        shipped = {tuple(k): int(v) for k, v in json.load(f)}
+    with open(_PRETUNED_DENSE) as f:
+        for k, v in json.load(f):
+            if _tile_cache.get(tuple(k), -1) == shipped.get(tuple(k)):
+                _tile_cache[tuple(k)] = int(v)
 
 
 def reset_tuning():
@@ -446,6 +471,21 @@ def split_pays(kind, g, run_plain, run_split):
     return bool(c)
 
 
+_PASS = {"fprop": 0, "dgrad": 1, "wgrad": 2}
+
+
+def dense_split_ok(kind, g):
+    """does the dense LDS form of the MCG_PREC_SPLIT launch (tile codes 17 / 20) exist for this pass and geometry?  The library's own
+    answer (mcg_conv_dense_split_ok); launches nothing."""
+    return bool(load().mcg_conv_dense_split_ok(C.byref(g), _PASS[kind]))
+
+
+def dense_split_chunk(kind, g):
+    """the part of the summed dimension one block of a dense split launch covers (g.tile: its K-split digit) -- split elements
+    (256 per triple of K-steps) in fprop / dgrad, pixels (64 per triple) in wgrad; 0 when the form does not apply"""
+    return int(load().mcg_conv_dense_split_chunk(C.byref(g), _PASS[kind]))
+
+
 def _geom_key(kind, g, extra=()):
     return (kind, g.N, g.Ti, g.Hi, g.Wi, g.Ci, g.Co, g.kt, g.x_perm_n, g.precision) + tuple(extra)
 
@@ -486,11 +526,13 @@ def _tuned(kind, g, extra, out_side, run_on):
             cands = cands + (10,)                           # the LDS-DMA kernel on fp32 operands, 128x128, two blocks per CU
         if g.precision == PREC_SPLIT:
             # (the LDS-DMA kernels are the only ones that multiply split operands; one 256-row block per CU: late layers need K splits)
-            cands = V2_CANDIDATES + ((1007, 2007, 1010, 2010) if kind in ("fprop", "dgrad") and out_elems <= (1 << 25) else ())
+            cands = V2_CANDIDATES + DENSE_CANDIDATES
+            if kind in ("fprop", "dgrad") and out_elems <= (1 << 25):
+                cands = cands + (1007, 2007, 1010, 2010, 1017, 2017, 1020, 2020)
             if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
                 # few (Co, tap x Ci) tiles -- the 2-D layers: many pixel splits then add onto the same small dw with float
                 # atomics; + 2000 halves / + 1000 doubles the number of splits (round 6)
-                cands = cands + WGRAD_SPLIT_CANDIDATES
+                cands = cands + WGRAD_SPLIT_CANDIDATES + (2017, 2020, 1020)
             if kind == "dgrad" and g.Ci == 64 and g.Ho == 16 and g.Wo == 16:
                 cands = cands + (9,)                        # the patch-stationary kernel (four parity classes per block)
         for cand in cands:
