@@ -19,6 +19,10 @@
 // loaders therefore use raw buffer loads (hardware range check: an out-of-range offset returns 0, so
 // padding / tile edges need one v_cndmask, no exec-mask branches), 32-bit byte offsets, and per-row
 // validity bit-masks over the 16 taps precomputed once per block.
+//
+// Device code written once and shared (what is still written more than once, and why: profiles/conv_gemm_dedup.md):
+//   FpropP     load_a / load_b go through each_a / each_b, its only address computation
+//   LDS-DMA    split_pa / split_pb (the six products of a split group), frag_wait (the counted wait for a quarter's fragments)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -228,13 +232,10 @@ struct FpropP : DenseOff<DN> {
     __device__ int next_valid(int k0) const { return k0; }
     __device__ int rotated(int k0) const { int k = k0 + krot; return k >= K ? k - K : k; }     // whole K-steps stay inside one tap
     __device__ void load_a(int k0, f32x4 (&r)[NA]) const {
+        static_assert(!DN, "register-staged loaders: each_a / each_b would give a dense policy its step-0 offsets");
         if constexpr (ST) {
-            if (g.lgCi >= 0 && (g.Ci & (BK - 1)) == 0) {
-                const int kr = rotated(k0);               // wave-uniform
-                const int tap = kr >> g.lgCi, ci0 = kr & (g.Ci - 1), sp = tap & 15;
-                const int off = ((((tap >> 4) * g.Hi + (sp >> 2)) * g.Wi + (sp & 3)) * g.Ci + ci0 + ak) * ESZ;
-#pragma unroll
-                for (int j = 0; j < NA; ++j) r[j] = bload(xr, (((~amask[j]) >> sp) << 31) | (u32)(abase[j] + off));
+            if (g.lgCi >= 0 && (g.Ci & (BK - 1)) == 0) {         // one tap per K-step: the wave-uniform decode of each_a
+                each_a(k0, [&](int j, u32 vo, u32) { r[j] = bload(xr, vo); });
                 return;
             }
         }
@@ -247,9 +248,8 @@ struct FpropP : DenseOff<DN> {
         for (int j = 0; j < NA; ++j) r[j] = bload(xr, (amask[j] >> sp) & 1u ? (u32)(abase[j] + off) : OOB);
     }
     __device__ void load_b(int k0, f32x4 (&r)[NB]) const {
-        const u32 kb = (u32)rotated(k0) * (u32)ESZ;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) r[j] = ST ? bload_s(wr, bbase[j], kb) : bload(wr, bbase[j] + kb);
+        static_assert(!DN, "register-staged loaders (see load_a)");
+        each_b(k0, [&](int j, u32 vo, u32 so) { r[j] = ST ? bload_s(wr, vo, so) : bload(wr, vo + so); });
     }
     // the same addresses for the LDS-DMA kernels: f(slot, per-lane byte offset (bit 31: out of range), wave-uniform byte offset).
     // Only for layers whose K-steps lie inside one filter tap (channel count a power of two and a multiple of BK: v2_ok).
@@ -1410,16 +1410,21 @@ __device__ __forceinline__ void rowwise_epilogue(const P& p, f32x16 (&acc)[TM][T
 //     -- an LDS-DMA load writes lane-linear, so the permutation is applied to the SOURCE chunk a lane loads (policy flag
 //     SW) and again to the address of the ds_read_b128; the 16-lane groups of a b128 read then touch 16 distinct slots of
 //     the 256-byte bank row (conflict-free: checked for both lane-group lists of the microarchitecture guide).
+// Shared by its three loop bodies (right below): split_pa / split_pb, frag_wait.  The fragment READS stay written out in each body
+// (shared, or as a static_for, the 128x128 split instantiations come out with another address split: profiles/conv_gemm_dedup.md).
 // Served by the policies above with NT = 512, SW = true, scalar tap decode.  Layers it covers: bf16-stored operands,
 // channel counts powers of two >= 64 (v2_ok); everything else stays on gemm_bf16_kernel.
 // ------------------------------------------------------------------------------------------
 #define MCG_LDSP(p) ((__attribute__((address_space(3))) void*)(p))
 
 // Dense split form, wait bookkeeping.  Product P of a triple (0..23: group P / 6, product c = P % 6) multiplies planes up to
-// max(pa, pb) = {0, 1, 1, 2, 1, 2}[c] of its group, i.e. dense quarters up to 3 (P / 6) + that.  dense_need: the highest quarter
+// max(split_pa(c), split_pb(c)) = {0, 1, 1, 2, 1, 2}[c] of its group, i.e. dense quarters up to 3 (P / 6) + that.  dense_need: the highest quarter
 // of step s that product P needs (-1: only carried ones); dense_had: the highest one the products P0 .. P0 + n - 1 needed.
+// The six products of a split group in issue order -- hi.hi, hi.mid, mid.hi, hi.lo, mid.mid, lo.hi: the plane of A / of B in product c
+__device__ __forceinline__ constexpr int split_pa(int c) { return (c == 0 || c == 1 || c == 3) ? 0 : (c == 2 || c == 4) ? 1 : 2; }
+__device__ __forceinline__ constexpr int split_pb(int c) { return (c == 0 || c == 2 || c == 5) ? 0 : (c == 1 || c == 4) ? 1 : 2; }
 __device__ __forceinline__ constexpr int dense_need(int P, int s) {
-    const int c = P % 6, top = 3 * (P / 6) + (c == 0 ? 0 : (c == 3 || c == 5) ? 2 : 1);
+    const int c = P % 6, top = 3 * (P / 6) + (split_pa(c) > split_pb(c) ? split_pa(c) : split_pb(c));
     return top / 4 == s ? top % 4 : -1;
 }
 // dense_at: the product of step s (0-based within the step) in front of which quarter q is read; dense_younger: how many
@@ -1439,6 +1444,19 @@ __device__ __forceinline__ constexpr int dense_had(int P0, int n, int s) {
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
+}
+
+// The wait for the T fragments of one operand of a k-quarter in gemm_bf16_v2_kernel's bf16 tiles (TR: read with the transposing
+// read pair, which the wait also joins).  Every wait count of the kernel (NRD, YOUNGER, BEHIND, dense_younger) assumes the issue
+// order "A rows, then B rows" within a quarter.
+// BEHIND: LDS reads issued after these fragments' (see tr16_wait)
+template <int BEHIND, bool TR, int T, int NL>
+__device__ __forceinline__ void frag_wait(bf16x8 (&d)[T], s16x4 (&lo)[NL], s16x4 (&hi)[NL]) {
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+        if constexpr (TR) d[i] = tr16_wait<BEHIND>(lo[i], hi[i]);
+        else ds128_wait<BEHIND>(d[i]);
+    }
 }
 
 // SPLIT (MCG_PREC_SPLIT: fp32 values as three bf16 terms, see mcg_split_planes): the operands' K dimension holds groups of 16
@@ -1653,8 +1671,7 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
                 constexpr int P0 = s == 0 ? 0 : s == 1 ? 7 : 15, NP = 7 + s;
                 static_for<0, NP>([&](auto n_) {
                     constexpr int n = decltype(n_)::value, grp = (P0 + n) / 6, c = (P0 + n) % 6;
-                    constexpr int pa = (c == 0 || c == 1 || c == 3) ? 0 : (c == 2 || c == 4) ? 1 : 2;
-                    constexpr int pb = (c == 0 || c == 2 || c == 5) ? 0 : (c == 1 || c == 4) ? 1 : 2;
+                    constexpr int pa = split_pa(c), pb = split_pb(c);
                     constexpr int need = dense_need(P0 + n, s), had = dense_had(P0, n, s);      // highest quarter of this step needed now / waited for so far
                     static_for<0, 4>([&](auto q_) { if constexpr (dense_at(s, decltype(q_)::value) == n) read_q(q_); });
                     if constexpr (n < 4) { issue_part(nbuf, n); __builtin_amdgcn_sched_barrier(0); }
@@ -1662,16 +1679,8 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
                         constexpr int w = decltype(w_)::value, d = 4 * s + w;
                         constexpr int YOUNGER = dense_younger(s, w, n) * NRD;          // reads issued after quarter w's, up to here
                         constexpr int BEHIND = YOUNGER < 15 ? YOUNGER : 15;
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) {
-                            if constexpr (TRA_) qa[d][i] = tr16_wait<BEHIND>(qalo[d][i], qahi[d][i]);
-                            else ds128_wait<BEHIND>(qa[d][i]);
-                        }
-#pragma unroll
-                        for (int i = 0; i < TN; ++i) {
-                            if constexpr (TRB_) qb[d][i] = tr16_wait<BEHIND>(qblo[d][i], qbhi[d][i]);
-                            else ds128_wait<BEHIND>(qb[d][i]);
-                        }
+                        frag_wait<BEHIND, TRA_>(qa[d], qalo[d], qahi[d]);
+                        frag_wait<BEHIND, TRB_>(qb[d], qblo[d], qbhi[d]);
                     });
 #pragma unroll
                     for (int a = 0; a < TM; ++a)
@@ -1826,21 +1835,12 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             static_for<0, 3>([&](auto pl_) {                     // (completion counted by hand; plane pl has 2 - pl planes of NRD reads behind it)
                 constexpr int pl = decltype(pl_)::value;
                 constexpr int BEHIND = (2 - pl) * NRD < 15 ? (2 - pl) * NRD : 15;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    if constexpr (TRA) sfa[pl][i] = tr16_wait<BEHIND>(salo[pl][i], sahi[pl][i]);
-                    else ds128_wait<BEHIND>(sfa[pl][i]);
-                }
-#pragma unroll
-                for (int i = 0; i < TN; ++i) {
-                    if constexpr (TRB) sfb[pl][i] = tr16_wait<BEHIND>(sblo[pl][i], sbhi[pl][i]);
-                    else ds128_wait<BEHIND>(sfb[pl][i]);
-                }
+                frag_wait<BEHIND, TRA>(sfa[pl], salo[pl], sahi[pl]);
+                frag_wait<BEHIND, TRB>(sfb[pl], sblo[pl], sbhi[pl]);
             });
             static_for<0, 6>([&](auto c_) {
                 constexpr int c = decltype(c_)::value;
-                constexpr int pa = (c == 0 || c == 1 || c == 3) ? 0 : (c == 2 || c == 4) ? 1 : 2;
-                constexpr int pb = (c == 0 || c == 2 || c == 5) ? 0 : (c == 1 || c == 4) ? 1 : 2;
+                constexpr int pa = split_pa(c), pb = split_pb(c);
                 if constexpr (c < 4) { issue_part(nbuf, c); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
@@ -1857,16 +1857,8 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             __builtin_amdgcn_sched_barrier(0);                   // (keeps these loads in front of this MFMA group)
             constexpr int YOUNGER = kc + 1 < 4 ? (NRD < 15 ? NRD : 15) : 0;     // the reads of the following chunk, issued after the ones used now
             if constexpr (!F32) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    if constexpr (TRA) fa[kc & 1][i] = tr16_wait<YOUNGER>(alo[kc & 1][i], ahi[kc & 1][i]);
-                    else ds128_wait<YOUNGER>(fa[kc & 1][i]);
-                }
-#pragma unroll
-                for (int i = 0; i < TN; ++i) {
-                    if constexpr (TRB) fb[kc & 1][i] = tr16_wait<YOUNGER>(blo[kc & 1][i], bhi[kc & 1][i]);
-                    else ds128_wait<YOUNGER>(fb[kc & 1][i]);
-                }
+                frag_wait<YOUNGER, TRA>(fa[kc & 1], alo[kc & 1], ahi[kc & 1]);
+                frag_wait<YOUNGER, TRB>(fb[kc & 1], blo[kc & 1], bhi[kc & 1]);
             }
             if constexpr (F32) {
 #pragma unroll
@@ -2079,8 +2071,7 @@ __global__ __launch_bounds__(NT2) void dgrad_patch_kernel(DgPatchPol p) {
                 });
                 static_for<0, 6>([&](auto c_) {
                     constexpr int c = decltype(c_)::value;
-                    constexpr int pa = (c == 0 || c == 1 || c == 3) ? 0 : (c == 2 || c == 4) ? 1 : 2;
-                    constexpr int pb_ = (c == 0 || c == 2 || c == 5) ? 0 : (c == 1 || c == 4) ? 1 : 2;
+                    constexpr int pa = split_pa(c), pb_ = split_pb(c);
 #pragma unroll
                     for (int a = 0; a < 2; ++a)
 #pragma unroll
