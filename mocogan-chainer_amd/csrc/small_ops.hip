@@ -365,6 +365,10 @@ __global__ __launch_bounds__(NT) void bn_act_fwd_kernel(long long n, int C, int 
 }
 
 // gx = coef0 * (g*mask - x_hat*coef1 - coef2)    (BN)   or, W = 4 only,   gx = g*mask(y) / g*(1-y^2)  (no BN: stats == nullptr)
+// The one fused multiply-add of the BN form is written out (as in adam_wd_elem): left to the compiler, g*mask - x_hat*coef1 stayed
+// unfused in the four-wide kernels, became fma(g, mask, -(x_hat*coef1)) in the eight-wide ones with IO 2, 4, 5, 6, 7 and
+// fma(-x_hat, coef1, g*mask) in those with IO 1, 3, 8 -- the bf16 output of one set of inputs was then not always the rounded
+// fp32 output of the same inputs (tests/test_gpu_sync_bn.py::test_flag_forms: 1 element of 2 150 400).
 template <int W, int IO>
 __global__ __launch_bounds__(NT) void bn_act_bwd_apply_kernel(long long n, int C, const float* __restrict__ g,
                                                               const float* __restrict__ y, const float* __restrict__ stats,
@@ -390,7 +394,7 @@ __global__ __launch_bounds__(NT) void bn_act_bwd_apply_kernel(long long n, int C
             for (int k = 0; k < W; ++k) {
                 const float gb = in.g[k] * act_mask(fmaf(in.y[k], sc[k], sh[k]), act);
                 const float xh = (in.y[k] - mean[k]) * istd[k];
-                o[k] = k0[k] * (gb - xh * k1[k] - k2[k]);
+                o[k] = k0[k] * (fmaf(-xh, k1[k], gb) - k2[k]);
             }
         } else {
 #pragma unroll

@@ -760,6 +760,17 @@ def bn_workspace_floats(C_max):
     return int(load().mcg_bn_workspace_bytes(0, C_max)) // 4
 
 
+def bn_sums(M, Cn, y, sums, ws):
+    """sums (float64)[2 Cn] = [sum y | sum y^2] over the M rows this rank holds (first half of synchronised BatchNorm's forward)"""
+    _check(load().mcg_bn_sums(M, Cn, _p(_dense(y)), _p(sums, torch.float64), _p(ws), _stream()), "mcg_bn_sums")
+
+
+def bn_stats_from_sums(M_total, Cn, sums, gamma, beta, stats, avg_mean, avg_var, eps=2e-5, decay=0.9):
+    """bn_stats' outputs from the sums of the M_total rows of the global batch (bn_sums of every rank, added)"""
+    _check(load().mcg_bn_stats_from_sums(M_total, Cn, _p(sums, torch.float64), _p(gamma), _p(beta), _p(stats), _p(avg_mean),
+                                         _p(avg_var), eps, decay, _stream()), "mcg_bn_stats_from_sums")
+
+
 def bn_stats(M, Cn, y, gamma, beta, stats, avg_mean, avg_var, ws, eps=2e-5, decay=0.9, sync=None):
     """sync: None, or an object with .world and .all_reduce_sum(tensor) (step.GradExchange): the statistics are then
     those of the global batch (every rank holds M rows)."""
@@ -768,10 +779,9 @@ def bn_stats(M, Cn, y, gamma, beta, stats, avg_mean, avg_var, ws, eps=2e-5, deca
                                    eps, decay, _p(ws), _stream()), "mcg_bn_stats")
         return
     sums = torch.empty(2 * Cn, dtype=torch.float64, device=y.device)
-    _check(load().mcg_bn_sums(M, Cn, _p(_dense(y)), _p(sums, torch.float64), _p(ws), _stream()), "mcg_bn_sums")
+    bn_sums(M, Cn, y, sums, ws)
     sync.all_reduce_sum(sums)
-    _check(load().mcg_bn_stats_from_sums(M * sync.world, Cn, _p(sums, torch.float64), _p(gamma), _p(beta), _p(stats), _p(avg_mean),
-                                         _p(avg_var), eps, decay, _stream()), "mcg_bn_stats_from_sums")
+    bn_stats_from_sums(M * sync.world, Cn, sums, gamma, beta, stats, avg_mean, avg_var, eps, decay)
 
 
 def _pout(out, split_out):
@@ -797,24 +807,40 @@ def bn_act_fwd(M, Cn, y, scale_shift, act, out, addend=None, sigma=0.0, seed=0, 
            "mcg_bn_act_fwd")
 
 
-def bn_act_bwd(M, Cn, g_out, y, stats, gamma, act, gx, dgamma, dbeta, ws, sync=None, split_out=False):
-    gp, gflag = _pout(gx, split_out)
-    g16 = gflag == IO_OUT_BF16
+def bn_bwd_sums(M, Cn, g_out, y, stats, act, sums, ws):
+    """sums (float64)[2 Cn] = [sum g' | sum g' x_hat] over this rank's M rows, g' = g_out * act'(y * scale + shift); g_out and y
+    fp32 or bf16 (first half of synchronised BatchNorm's backward)"""
     ip, i16 = _pany(_dense(g_out))
     yp, y16 = _pany(_dense(y))
+    _check(load().mcg_bn_bwd_sums(M, Cn, ip, yp, _p(stats), act, IO_Y_BF16 * y16 + IO_G_BF16 * i16, _p(sums, torch.float64), _p(ws),
+                                  _stream()), "mcg_bn_bwd_sums")
+
+
+def bn_act_bwd_from_sums(M, M_total, Cn, g_out, y, stats, gamma, act, local_sums, global_sums, gx, dgamma, dbeta, ws):
+    """bn_act_bwd's second half: gx of this rank's M rows from the sums of the M_total rows of the global batch; dgamma / dbeta
+    accumulate this rank's own sums (the gradient exchange adds the ranks')"""
+    gp, g16 = _pany(_dense(gx))
+    ip, i16 = _pany(_dense(g_out))
+    yp, y16 = _pany(_dense(y))
+    _check(load().mcg_bn_act_bwd_from_sums(M, M_total, Cn, ip, yp, _p(stats), _p(gamma), act, _p(local_sums, torch.float64),
+                                           _p(global_sums, torch.float64), gp, IO_OUT_BF16 * g16 + IO_Y_BF16 * y16 + IO_G_BF16 * i16,
+                                           _p(dgamma), _p(dbeta), _p(ws), _stream()), "mcg_bn_act_bwd_from_sums")
+
+
+def bn_act_bwd(M, Cn, g_out, y, stats, gamma, act, gx, dgamma, dbeta, ws, sync=None, split_out=False):
     if sync is None or sync.world == 1 or stats is None:
+        gp, gflag = _pout(gx, split_out)
+        ip, i16 = _pany(_dense(g_out))
+        yp, y16 = _pany(_dense(y))
         _check(load().mcg_bn_act_bwd(M, Cn, ip, yp, _p(stats), _p(gamma), act, gp, gflag + IO_Y_BF16 * y16 + IO_G_BF16 * i16,
                                      _p(dgamma), _p(dbeta), _p(ws), _stream()), "mcg_bn_act_bwd")
         return
     assert not split_out
     local = torch.empty(2 * Cn, dtype=torch.float64, device=y.device)
-    _check(load().mcg_bn_bwd_sums(M, Cn, ip, yp, _p(stats), act, IO_Y_BF16 * y16 + IO_G_BF16 * i16, _p(local, torch.float64), _p(ws),
-                                  _stream()), "mcg_bn_bwd_sums")
+    bn_bwd_sums(M, Cn, g_out, y, stats, act, local, ws)
     glob = local.clone()
     sync.all_reduce_sum(glob)
-    _check(load().mcg_bn_act_bwd_from_sums(M, M * sync.world, Cn, ip, yp, _p(stats), _p(gamma), act, _p(local, torch.float64),
-                                           _p(glob, torch.float64), gp, IO_OUT_BF16 * g16 + IO_Y_BF16 * y16 + IO_G_BF16 * i16,
-                                           _p(dgamma), _p(dbeta), _p(ws), _stream()), "mcg_bn_act_bwd_from_sums")
+    bn_act_bwd_from_sums(M, M * sync.world, Cn, g_out, y, stats, gamma, act, local, glob, gx, dgamma, dbeta, ws)
 
 
 def bn_stats_from_partials(M, Cn, part, n_slots, slot_stride, gamma, beta, stats, avg_mean, avg_var, ws, eps=2e-5, decay=0.9):

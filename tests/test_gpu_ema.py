@@ -191,6 +191,77 @@ def test_rate_one_stores_the_parameter_itself(hl, arena, n, offset):
     a.arena.check()
 
 
+def _grad_sums(W, n=10007, steps=3, seed=9):
+    """p0 and, per step, the fp32 SUM of W gradients drawn as tests/test_gpu_ops.py::test_adam_weight_decay draws its one"""
+    rng = np.random.RandomState(seed + W)
+    p0 = rng.randn(n).astype(np.float32)
+    sums = []
+    for _ in range(steps):
+        acc = np.zeros(n, np.float32)
+        for _ in range(W):
+            acc += (rng.randn(n) * 10.0 ** rng.uniform(-9, 0, n)).astype(np.float32)
+        sums.append(acc)
+    return p0, sums
+
+
+def _oracle_adam():
+    from oracle import updater as oupd
+    lr = lambda t: oupd.ADAM_ALPHA * np.sqrt(1 - oupd.ADAM_BETA2 ** t) / (1 - oupd.ADAM_BETA1 ** t)
+    return oupd, lr, (oupd.ADAM_BETA1, oupd.ADAM_BETA2, oupd.ADAM_EPS, oupd.WEIGHT_DECAY)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("W", [2, 3, 8])
+def test_fused_kernel_grad_scale_against_float64(hl, arena, W, offset):
+    """adam_wd_ema(grad_scale = 1 / W) on the fp32 sum of W gradients against the oracle's Adam in float64 on g_sum / W, on aligned
+    pointers (the 16-byte kernel) and one float past them (the scalar kernel): p to 1e-6 absolute, m and v to rel-L2 1e-6 (the
+    bounds of tests/test_gpu_ops.py::test_adam_grad_scale_against_float64, where they are derived)."""
+    oupd, lr, consts = _oracle_adam()
+    p0, sums = _grad_sums(W)
+    n = len(p0)
+    arena.reset()
+    a = _Alloc(arena, offset)
+    p, m, v, e, g = (a.put(torch.as_tensor(t)) for t in (p0, np.zeros(n, np.float32), np.zeros(n, np.float32), p0, np.zeros(n, np.float32)))
+    p64 = {'x/W': p0.astype(np.float64)}
+    st = oupd.new_adam_state(p64)
+    for t, g_sum in enumerate(sums, 1):
+        oupd.adam_wd_update(p64, {'x/W': g_sum.astype(np.float64) / W}, st)
+        g.copy_(torch.as_tensor(g_sum))
+        hl.adam_wd_ema(p, g, m, v, lr(t), *consts, e, 0.25, grad_scale=1.0 / W)
+        e_p = float(np.abs(p.cpu().double().numpy() - p64['x/W']).max())
+        e_m, e_v = rel_l2(m, torch.as_tensor(st['m']['x/W'])), rel_l2(v, torch.as_tensor(st['v']['x/W']))
+        print("PARITY adam_wd_ema W=%d offset %d step %d: max |p - p64| %.2e (1e-6), m %.2e, v %.2e (rel-L2, 1e-6)" % (W, offset, t, e_p, e_m, e_v))
+        assert e_p < 1e-6 and e_m < 1e-6 and e_v < 1e-6, (t, e_p, e_m, e_v)
+    arena.check()
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("W", [2, 8])
+def test_fused_kernel_grad_scale_equals_scaling_the_gradient(hl, arena, W, offset):
+    """grad_scale = 1 / W on g_sum and grad_scale = 1 on g_sum / W (exact: a power of two, nothing near the subnormal range) write
+    the same p, m, v, bf16 copy and average, bit for bit"""
+    _, lr, consts = _oracle_adam()
+    p0, sums = _grad_sums(W)
+    n = len(p0)
+    arena.reset()
+    a = _Alloc(arena, offset)
+    zero = torch.zeros(n)
+    mk = lambda: [a.put(torch.as_tensor(p0)), a.put(zero), a.put(zero), a.put(torch.as_tensor(p0) * 0.5), a.put(torch.zeros(n, dtype=torch.bfloat16)),
+                  a.put(zero)]
+    x, y = mk(), mk()                                                      # p, m, v, average, bf16 copy, gradient
+    for t, g_sum in enumerate(sums, 1):
+        scaled = g_sum / np.float32(W)
+        assert np.array_equal(scaled * np.float32(W), g_sum) and np.abs(scaled[scaled != 0]).min() > 1e-30
+        x[5].copy_(torch.as_tensor(g_sum)), y[5].copy_(torch.as_tensor(scaled))
+        hl.adam_wd_ema(x[0], x[5], x[1], x[2], lr(t), *consts, x[3], 0.25, grad_scale=1.0 / W, p16=x[4])
+        hl.adam_wd_ema(y[0], y[5], y[1], y[2], lr(t), *consts, y[3], 0.25, grad_scale=1.0, p16=y[4])
+        for name, u, w in zip(("p", "m", "v", "average", "p16"), x, y):
+            assert torch.equal(u.view(torch.int32 if u.dtype == torch.float32 else torch.int16),
+                               w.view(torch.int32 if w.dtype == torch.float32 else torch.int16)), (name, t)
+    assert not torch.equal(x[0].cpu(), torch.as_tensor(p0))
+    arena.check()
+
+
 def _segments(buf_src, buf_dst, sizes, gap=3):
     """(src, dst) views of the given sizes at ODD float offsets of two buffers, `gap` (or gap + 1) floats apart"""
     pairs, off = [], 1

@@ -482,11 +482,12 @@ def _bn_edge_fwd_bwd(hl, M, C, bf16, bn, act, seed, scale_shift=False, addend=Fa
         gx16, dg16, db16 = bwd(in16, bf)
         assert torch.equal(gx16, gx32.to(bf)) and torch.equal(dg16, dg) and torch.equal(db16, db), in16
         if split and not in16:
-            # The split gradient comes from the eight-wide apply kernel, the fp32 one from the four-wide.  The compiler contracts
-            # gb - xh * k1 - k2 into other fused multiply-adds in the two, and in the eight-wide one it also fuses the last
-            # product k0 * (...) into the subtraction of the first plane, so mid and lo carry bits BELOW the fp32 value's last:
-            # the planes are neither split_planes(gx32) nor the split form of any fp32 tensor (measured at this shape: 35 of 592
-            # values differ from gx32, by up to 6 ulp; hi + mid + lo is no fp32 number for 518 of them).  The forward pass, whose
+            # The split gradient comes from the eight-wide apply kernel, the fp32 one from the four-wide.  Both now compute
+            # fmaf(-xh, k1, gb) - k2 (written out in the kernel; the compiler used to contract gb - xh * k1 differently in the
+            # two), but in the eight-wide one the compiler still fuses the last product k0 * (...) into the subtraction of the
+            # first plane, so mid and lo carry bits BELOW the fp32 value's last: the planes are neither split_planes(gx32) nor the
+            # split form of any fp32 tensor (measured at this shape before the fma was written out: 35 of 592 values differ
+            # from gx32, by up to 6 ulp; hi + mid + lo is no fp32 number for 518 of them).  The forward pass, whose
             # fmaf is written out, is held to split_planes above.  Held here: the same per-channel sums; the first plane equal to
             # the bf16 output of the same kernel, bit for bit; each further plane within half a bf16 ulp of the one before (what
             # "the bf16 rounding of what the planes before left" means for the sizes); their sum against float64 and, to fp32
@@ -724,6 +725,118 @@ def test_adam_weight_decay(hl):
         lr_t = oupd.ADAM_ALPHA * np.sqrt(1 - oupd.ADAM_BETA2 ** t) / (1 - oupd.ADAM_BETA1 ** t)
         hl.adam_wd(pd, dev(g), md, vd, lr_t, oupd.ADAM_BETA1, oupd.ADAM_BETA2, oupd.ADAM_EPS, oupd.WEIGHT_DECAY)
         assert np.abs(pd.cpu().numpy() - p['x/W']).max() < 1e-6
+
+
+def _adam_grad_sums(W, n=10007, steps=3, seed=9):
+    """p0 and, per step, the fp32 SUM of W gradients drawn as test_adam_weight_decay draws its one (what the all-reduce hands to Adam)"""
+    rng = np.random.RandomState(seed + W)
+    p0 = rng.randn(n).astype(np.float32)
+    sums = []
+    for _ in range(steps):
+        acc = np.zeros(n, np.float32)
+        for _ in range(W):
+            acc += (rng.randn(n) * 10.0 ** rng.uniform(-9, 0, n)).astype(np.float32)
+        sums.append(acc)
+    return p0, sums
+
+
+def _offset_tensor(a, offset, dtype=torch.float32):
+    """a copy of `a` that starts `offset` elements past an aligned address"""
+    buf = torch.zeros(len(a) + offset, dtype=dtype, device="cuda")
+    out = buf[offset:]
+    out.copy_(torch.as_tensor(a).to(dtype))
+    assert out.data_ptr() % 16 == offset * out.element_size() % 16
+    return out
+
+
+def _adam_lr(t):
+    return oupd.ADAM_ALPHA * np.sqrt(1 - oupd.ADAM_BETA2 ** t) / (1 - oupd.ADAM_BETA1 ** t)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("W", [2, 3, 8])
+def test_adam_grad_scale_against_float64(hl, W, offset):
+    """grad_scale = 1 / W on the all-reduced SUM of W ranks' gradients is Adam on their mean: against the oracle's update in
+    float64, fed g_sum / W formed in float64.  p to test_adam_weight_decay's 1e-6 absolute; m and v to rel-L2 1e-6, ten times the
+    fp32 rounding (2^-24 = 6e-8 each) of the three fused operations behind each of them (g * gscale, the fma with wd * p, the
+    fma of the moment; for v the square in place of the scaling) -- three steps do not add up, (1 - beta) of the old error stays."""
+    p0, sums = _adam_grad_sums(W)
+    p = {'x/W': p0.astype(np.float64)}
+    st = oupd.new_adam_state(p)
+    n = len(p0)
+    pd, md, vd = _offset_tensor(p0, offset), _offset_tensor(np.zeros(n), offset), _offset_tensor(np.zeros(n), offset)
+    for t, g_sum in enumerate(sums, 1):
+        oupd.adam_wd_update(p, {'x/W': g_sum.astype(np.float64) / W}, st)
+        hl.adam_wd(pd, _offset_tensor(g_sum, offset), md, vd, _adam_lr(t), oupd.ADAM_BETA1, oupd.ADAM_BETA2, oupd.ADAM_EPS, oupd.WEIGHT_DECAY,
+                   grad_scale=1.0 / W)
+        e_p = np.abs(pd.cpu().double().numpy() - p['x/W']).max()
+        e_m, e_v = rel_l2(md, st['m']['x/W']), rel_l2(vd, st['v']['x/W'])
+        print("PARITY adam_wd W=%d offset %d step %d: max |p - p64| %.2e (1e-6), m %.2e, v %.2e (rel-L2, 1e-6)" % (W, offset, t, e_p, e_m, e_v))
+        assert e_p < 1e-6 and e_m < 1e-6 and e_v < 1e-6, (t, e_p, e_m, e_v)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("W", [2, 8])
+def test_adam_grad_scale_equals_scaling_the_gradient(hl, W, offset):
+    """1 / W is a power of two: g_sum * (1 / W) in the kernel and g_sum / W formed beforehand (then times 1.0f) are the same fp32
+    number -- no gradient here is near the subnormal range -- so p, m, v and the bf16 copy come out bit for bit the same."""
+    p0, sums = _adam_grad_sums(W)
+    n = len(p0)
+    a = [_offset_tensor(p0, offset), _offset_tensor(np.zeros(n), offset), _offset_tensor(np.zeros(n), offset),
+         _offset_tensor(np.zeros(n), offset, torch.bfloat16)]
+    b = [_offset_tensor(p0, offset), _offset_tensor(np.zeros(n), offset), _offset_tensor(np.zeros(n), offset),
+         _offset_tensor(np.zeros(n), offset, torch.bfloat16)]
+    for t, g_sum in enumerate(sums, 1):
+        scaled = g_sum / np.float32(W)
+        assert scaled.dtype == np.float32 and np.array_equal(scaled * np.float32(W), g_sum) and np.abs(scaled[scaled != 0]).min() > 1e-30
+        args = (_adam_lr(t), oupd.ADAM_BETA1, oupd.ADAM_BETA2, oupd.ADAM_EPS, oupd.WEIGHT_DECAY)
+        hl.adam_wd(a[0], _offset_tensor(g_sum, offset), a[1], a[2], *args, grad_scale=1.0 / W, p16=a[3])
+        hl.adam_wd(b[0], _offset_tensor(scaled, offset), b[1], b[2], *args, grad_scale=1.0, p16=b[3])
+        for name, x, y in zip(("p", "m", "v", "p16"), a, b):
+            assert torch.equal(x.view(torch.int32 if x.dtype == torch.float32 else torch.int16),
+                               y.view(torch.int32 if y.dtype == torch.float32 else torch.int16)), (name, t)
+    assert not torch.equal(a[0], torch.as_tensor(p0).cuda())
+
+
+@pytest.mark.parametrize("n", [1, 5, 1027, 4 * 256 * 2048 + 7])
+def test_randint_matches_oracle_stream(hl, n):
+    """hl.randint against oracle.philox.randint, exactly: one element, a partial counter, several blocks with a partial last
+    counter (n % 4 = 3), and more counters than a capped element-wise grid has threads (2048 x 256: a thread's second trip);
+    moduli 1, 6 (the label count), an odd one and the largest positive int32; a seed and a stream id that need all 64 bits.  The
+    n-element output lies between poisoned margins: the last counter's n % 4 words and nothing more are written."""
+    from guard import Arena
+    arena = Arena(((n * 4 + 255) // 256 * 256) + (4 << 16))
+    seed, stream = 0xFEDCBA9876543210, 0x8123456789ABCDEF
+    for modulus in (1, 6, 7, 2 ** 31 - 1):
+        arena.reset()
+        out = arena.empty((n,), torch.int32)
+        hl.randint(out, modulus, seed, stream)
+        arena.check()
+        ref = philox.randint(n, modulus, seed, stream)
+        got = out.cpu().numpy().astype(np.int64)
+        assert np.array_equal(got, ref), (modulus, int((got != ref).sum()), np.flatnonzero(got != ref)[:8])
+        assert ref.min() >= 0 and ref.max() < modulus
+    if n > 1000:                                    # (the stream is not a constant, and the four words of a counter differ)
+        assert len(np.unique(ref[:1000])) > 900
+    # another stream id or seed is another stream
+    if n == 1027:
+        out2 = torch.empty(n, dtype=torch.int32, device="cuda")
+        hl.randint(out2, 2 ** 31 - 1, seed, stream ^ (1 << 63))
+        assert not np.array_equal(out2.cpu().numpy(), ref) and np.array_equal(out2.cpu().numpy(), philox.randint(n, 2 ** 31 - 1, seed, stream ^ (1 << 63)))
+        hl.randint(out2, 2 ** 31 - 1, seed ^ (1 << 32), stream)
+        assert np.array_equal(out2.cpu().numpy(), philox.randint(n, 2 ** 31 - 1, seed ^ (1 << 32), stream))
+
+
+def test_randint_refusals(hl):
+    out = torch.full((8,), -7, dtype=torch.int32, device="cuda")
+    with pytest.raises(hl.McgError, match="MCG_ERR_BAD_ARG"):
+        hl.randint(out, 0, 1, 2)
+    with pytest.raises(hl.McgError, match="MCG_ERR_BAD_ARG"):
+        hl.randint(out, -6, 1, 2)
+    with pytest.raises(hl.McgError, match="MCG_ERR_BAD_ARG"):
+        hl.randint(out[:0], 6, 1, 2)
+    assert hl.load().mcg_randint(0, 6, 1, 2, hl._p(out, torch.int32), hl._stream()) == -1       # n = 0 with a real pointer
+    assert bool((out == -7).all())
 
 
 # ------------------------------------------------------------------------------------------------------------------
