@@ -129,7 +129,8 @@ typedef struct mcg_conv_geom {
  * 6 = round 5 (mcg_split_planes_multi); 7 = round 6 (mcg_pack_clip_u8; nothing else changed);
  * 8 = the sampling path (mcg_bn_fold_deconv, mcg_clip_to_u8, MCG_ACT_RELU in mcg_conv_dgrad / mcg_conv_dgrad_ex; no argument list changed);
  *     still 8 with the averaged generator (mcg_adam_wd_ema, mcg_ema_multi added; no argument list changed)
- *     and with the differentiable augmentation (mcg_augment_* added; no argument list changed). */
+ *     and with the differentiable augmentation (mcg_augment_* added; no argument list changed)
+ *     and with the sliced Wasserstein distance (mcg_swd_*, mcg_sort_* added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -465,6 +466,53 @@ int mcg_split_planes_multi(int nseg, const mcg_split_seg* segs, void* stream);
 /* out[i] = word (i & 3) of Philox counter (i >> 2) of the stream, modulo `modulus`: the generator's label draw
  * xp.random.randint(dim_zl, size=batchsize) (model/net.py:91-92) from the same keyed generator as the normals. */
 int mcg_randint(int64_t n, int modulus, uint64_t seed, uint64_t stream_id, int32_t* out, void* stream);
+
+/* ---- sliced Wasserstein distance between two sets of clips (csrc/metrics.hip) ----------------------------------------------
+ * Karras et al. 2018, "Progressive Growing of GANs", section 5 (no reference counterpart: the reference has no metric; its
+ * model/updater.py imports scipy.linalg for a Frechet score it never computes).  Random 7x7(x pt frames) patches of a three-level
+ * Laplacian pyramid are normalised per channel, projected on random unit directions, every direction is sorted, and the two sets'
+ * sorted projections are compared rank by rank.  The stages are separate entry points; mocogan-chainer_amd/metrics.py composes them.
+ * No float atomics anywhere: sums are per-block partials in double, added in a fixed order, so every result is bit-reproducible.
+ * One workspace serves every stage: mcg_swd_workspace_bytes(n, D, rows) bytes, 16-byte aligned, for descriptor matrices of n rows
+ * and D columns and `rows` sorted rows of length n (0 on a bad argument).
+ *
+ * mcg_swd_pyramid: uint8 clips [N][T][64][64][C], C = 1..3 (MCG_ERR_UNSUPPORTED for another frame size), bytes taken as fp32
+ *   0..255, to the levels l64 [N][T][64][64][4], l32 [N][T][32][32][4], l16 [N][T][16][16][4] (pad channels zero).  With
+ *   f = [1,4,6,4,1]/16 and scipy's 'mirror' boundary (d c b | a b c d | c b a): down(x) = (x * f(x)f)[::2, ::2]; up(x) = x at the
+ *   even positions of a zero image twice the size, * 4 f(x)f;  l64 = G64 - up(G32), l32 = G32 - up(G16), l16 = G16 (G64 the frame,
+ *   G32 = down(G64), G16 = down(G32)).  One workgroup per frame, all levels of a channel in LDS (31 KB), one launch.
+ * mcg_swd_gather: `level` is one of the three levels (hw = 64 / 32 / 16) of N clips whose global indices start at first_clip; writes
+ *   the N * P descriptor rows of those clips to `desc` (= row first_clip * P of the whole set's matrix), D = pt * 49 * C floats each.
+ *   Row j of clip i takes Philox counter g = i * P + j of (seed, stream_id); with its words w0, w1, w2: t0 = w0 % (T - pt + 1),
+ *   y0 = w1 % (hw - 6), x0 = w2 % (hw - 6); element ((dt*7 + dy)*7 + dx)*C + c = level[i][t0 + dt][y0 + dy][x0 + dx][c] -- exact
+ *   copies, and by the moduli no address outside the clip.  A set gathered in chunks equals the set gathered in one call.
+ * mcg_swd_channel_sums: sums [2*C] doubles = [sum over channel c | sum of squares over channel c] of desc [n][D] (element e of a row
+ *   belongs to channel e % C), the pattern of mcg_bn_sums.  A pass of its own over the whole matrix, so chunking cannot change it.
+ * mcg_swd_normalize: desc <- (desc - mean_c) / std_c (population std) in place, evaluated in double and rounded once.  A channel of
+ *   zero variance -- variance not above 1e-12 of the channel's mean square -- becomes zeros (ProGAN's NumPy would write NaN).
+ * mcg_swd_unit_columns: every column of dirs [D][K] (mcg_randn of D * K values) scaled to unit L2 norm (norm in double).
+ * mcg_swd_project: out[k][i] = sum_d desc[i][d] * dirs[d][k], direction-major [K][n_stride] (n_stride >= n; a direction is a
+ *   contiguous row for the sort), on v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation; any D (the tail is zero-filled).
+ * mcg_sort_rows: sorts `rows` independent rows data[r * row_stride .. + n) ascending, in place, keys only, any n >= 1; elements
+ *   n .. row_stride of a row are not touched.  Bitonic: steps inside mcg_sort_local_span() elements run in LDS, every wider step is
+ *   a launch of its own over the rows padded to a power of two with +inf in `workspace` (not needed, may be NULL, for
+ *   n <= mcg_sort_local_span()).  No kernel waits on another workgroup.  Values finite or +-inf; with NaN the order is
+ *   unspecified but every access stays inside the row (indices do not depend on values).  rows <= 65535.
+ * mcg_swd_distance: out[0] = mean over k < K, i < n of |a[k][i] - b[k][i]| for two sorted sets (differences and sums in double, fixed
+ *   order: out(a, b) == out(b, a) bit for bit and out(a, a) == 0).  n_a != n_b is MCG_ERR_BAD_ARG.
+ * MCG_ERR_BAD_ARG: a null pointer, a non-positive extent, C outside 1..3, pt > T, a stride below its extent. */
+int64_t mcg_swd_workspace_bytes(int64_t n, int D, int rows);
+int mcg_swd_pyramid(int N, int C, int T, int H, int W, const uint8_t* clips, float* l64, float* l32, float* l16, void* stream);
+int mcg_swd_gather(int N, int C, int T, int hw, const float* level, int64_t first_clip, int P, int pt, uint64_t seed,
+                   uint64_t stream_id, float* desc, void* stream);
+int mcg_swd_channel_sums(int64_t n, int D, int C, const float* desc, double* sums, void* workspace, void* stream);
+int mcg_swd_normalize(int64_t n, int D, int C, float* desc, const double* sums, void* stream);
+int mcg_swd_unit_columns(int D, int K, float* dirs, void* stream);
+int mcg_swd_project(int64_t n, int D, int K, const float* desc, const float* dirs, float* out, int64_t n_stride, void* stream);
+int mcg_sort_local_span(void);
+int mcg_sort_rows(int rows, int64_t n, float* data, int64_t row_stride, void* workspace, void* stream);
+int mcg_swd_distance(int K, int64_t n_a, int64_t n_b, const float* a, int64_t a_stride, const float* b, int64_t b_stride,
+                     double* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,16 @@ SIGNATURES = {
     "mcg_augment_draw": (_I, [_I, _I, _I, _I, _U64, _U64, _P, _P, _P]),
     "mcg_augment_fwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcg_augment_bwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mcg_swd_workspace_bytes": (_I64, [_I64, _I, _I]),
+    "mcg_swd_pyramid": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mcg_swd_gather": (_I, [_I, _I, _I, _I, _P, _I64, _I, _I, _U64, _U64, _P, _P]),
+    "mcg_swd_channel_sums": (_I, [_I64, _I, _I, _P, _P, _P, _P]),
+    "mcg_swd_normalize": (_I, [_I64, _I, _I, _P, _P, _P]),
+    "mcg_swd_unit_columns": (_I, [_I, _I, _P, _P]),
+    "mcg_swd_project": (_I, [_I64, _I, _I, _P, _P, _P, _I64, _P]),
+    "mcg_sort_local_span": (_I, []),
+    "mcg_sort_rows": (_I, [_I, _I64, _P, _I64, _P, _P]),
+    "mcg_swd_distance": (_I, [_I, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
 }
 
 ABI_VERSION = 8          # MCG_ABI_VERSION of include/mocogan_hip.h these prototypes were written against
@@ -1092,3 +1102,100 @@ def augment_fwd(x, c, geo, col, ws, out):
 def augment_bwd(g_out, c, geo, col, ws, g_in):
     """the adjoint of augment_fwd's linear part: gradient w.r.t. the augmented clips -> gradient w.r.t. the clips"""
     return _augment(load().mcg_augment_bwd, "mcg_augment_bwd", g_out, c, geo, col, ws, g_in)
+
+
+# ---- sliced Wasserstein distance (include/mocogan_hip.h: mcg_swd_*, mcg_sort_rows; composed by metrics.py) -------------------------
+SWD_LEVELS = (64, 32, 16)                                          # frame sizes of the pyramid levels l64, l32, l16
+
+
+def sort_local_span():
+    """the row length up to which mcg_sort_rows needs one launch and no workspace (mcg_sort_local_span)"""
+    return int(load().mcg_sort_local_span())
+
+
+def swd_workspace(n, d, rows, device):
+    """the caller-owned scratch of every swd_* stage on n x d descriptor matrices and `rows` sorted rows (mcg_swd_workspace_bytes)"""
+    nbytes = load().mcg_swd_workspace_bytes(n, d, rows)
+    if nbytes <= 0:
+        raise McgError("swd_workspace: bad sizes n=%r d=%r rows=%r" % (n, d, rows))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def _ws_ok(ws, n, d, rows):
+    return ws.numel() * ws.element_size() >= load().mcg_swd_workspace_bytes(n, d, rows)
+
+
+def swd_pyramid(clips):
+    """uint8 clips (N,T,64,64,C) -> the levels (l64, l32, l16), fp32 [N][T][h][h][4] with zero pad channels"""
+    if clips.dtype != torch.uint8 or clips.dim() != 5:
+        raise McgError("swd_pyramid: uint8 clips (N,T,H,W,C), got %s %s" % (clips.dtype, tuple(clips.shape)))
+    n, t, h, w, c = clips.shape
+    levels = [torch.empty(n, t, s, s, 4, dtype=torch.float32, device=clips.device) for s in SWD_LEVELS]
+    _check(load().mcg_swd_pyramid(n, c, t, h, w, _p(_dense(clips), torch.uint8), _p(levels[0]), _p(levels[1]), _p(levels[2]), _stream()),
+           "mcg_swd_pyramid")
+    return levels
+
+
+def swd_gather(level, c, first_clip, patches, patch_frames, seed, stream_id, out):
+    """the patches * N descriptor rows of the N clips of `level` ([N][T][h][h][4], c valid channels, global clip indices from
+    first_clip) into out [N * patches][patch_frames * 49 * c] (a view of the set's matrix at row first_clip * patches)"""
+    n, t, h = level.shape[0], level.shape[1], level.shape[2]
+    d = patch_frames * 49 * c
+    if level.dim() != 5 or level.shape[3] != h or level.shape[4] != 4 or out.numel() != n * patches * d:
+        raise McgError("swd_gather: level %s / out %s do not fit" % (tuple(level.shape), tuple(out.shape)))
+    _check(load().mcg_swd_gather(n, c, t, h, _p(_dense(level)), first_clip, patches, patch_frames, seed, stream_id, _p(_dense(out)), _stream()),
+           "mcg_swd_gather")
+    return out
+
+
+def swd_channel_sums(desc, c, ws, sums=None):
+    """[sum | sum of squares] per channel of desc [n][D] as 2 * c doubles"""
+    n, d = desc.shape
+    sums = torch.empty(2 * c, dtype=torch.float64, device=desc.device) if sums is None else sums
+    if sums.numel() < 2 * c or not _ws_ok(ws, n, d, 1):
+        raise McgError("swd_channel_sums: sums or workspace too small")
+    _check(load().mcg_swd_channel_sums(n, d, c, _p(_dense(desc)), _p(sums, torch.float64), _p(ws, torch.float64), _stream()), "mcg_swd_channel_sums")
+    return sums
+
+
+def swd_normalize(desc, c, sums):
+    """desc <- (desc - mean_c) / std_c in place (a constant channel -> zeros)"""
+    n, d = desc.shape
+    _check(load().mcg_swd_normalize(n, d, c, _p(_dense(desc)), _p(sums, torch.float64), _stream()), "mcg_swd_normalize")
+    return desc
+
+
+def swd_unit_columns(dirs):
+    """every column of dirs [D][K] to unit L2 norm, in place"""
+    d, k = dirs.shape
+    _check(load().mcg_swd_unit_columns(d, k, _p(_dense(dirs)), _stream()), "mcg_swd_unit_columns")
+    return dirs
+
+
+def swd_project(desc, dirs, out):
+    """out [K][n_stride] (direction-major) = (desc [n][D] @ dirs [D][K])^T"""
+    n, d = desc.shape
+    k = dirs.shape[1]
+    if dirs.shape[0] != d or out.dim() != 2 or out.shape[0] != k or out.shape[1] < n:
+        raise McgError("swd_project: desc %s, dirs %s, out %s do not fit" % (tuple(desc.shape), tuple(dirs.shape), tuple(out.shape)))
+    _check(load().mcg_swd_project(n, d, k, _p(_dense(desc)), _p(_dense(dirs)), _p(_dense(out)), out.shape[1], _stream()), "mcg_swd_project")
+    return out
+
+
+def sort_rows(data, n=None, ws=None):
+    """sorts the first n (default: all) elements of every row of data [rows][row_stride] ascending, in place"""
+    rows, stride = data.shape
+    n = stride if n is None else n
+    if n > sort_local_span() and (ws is None or not _ws_ok(ws, n, 1, rows)):
+        raise McgError("sort_rows: rows of %d elements need a workspace (swd_workspace)" % n)
+    _check(load().mcg_sort_rows(rows, n, _p(_dense(data)), stride, None if ws is None else _p(ws, torch.float64), _stream()), "mcg_sort_rows")
+    return data
+
+
+def swd_distance(a, b, n, ws, out):
+    """out (one double) = mean |a - b| over the first n elements of every row of two sorted [K][stride] sets"""
+    if a.shape[0] != b.shape[0] or not _ws_ok(ws, n, 1, 1):
+        raise McgError("swd_distance: direction counts differ or workspace too small")
+    _check(load().mcg_swd_distance(a.shape[0], n, n, _p(_dense(a)), a.shape[1], _p(_dense(b)), b.shape[1], _p(out, torch.float64),
+                                   _p(ws, torch.float64), _stream()), "mcg_swd_distance")
+    return out
