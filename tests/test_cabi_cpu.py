@@ -76,6 +76,52 @@ def test_argument_validation_happens_on_the_host(hl):
     assert int(lib.mcg_bn_workspace_bytes(0, 512)) == (512 * 2 * 512 + 3 * 512) * 4
 
 
+def test_generator_head_entry_points_refuse_on_the_host(hl):
+    """The GRU, the full-window layers and the losses pick their kernels from sizes the user sets (--dim_zm, the label count): what
+    no kernel covers is refused before anything is launched.  `one` is a non-null pointer that is never dereferenced; no call
+    below passes an acceptable argument set."""
+    lib = hl.load()
+    one = ctypes.c_void_p(16)
+    BAD, UNSUPPORTED = -1, -2
+
+    def gru(N, T, dz, dl, dc, labels=one, hole=None):
+        ptr = lambda name: None if name == hole else one
+        fwd = lib.mcg_gru_seq_fwd(N, T, dz, dl, dc, ptr('params'), ptr('h0'), ptr('e'), labels, ptr('zc'), ptr('z'), ptr('saved'), None)
+        bwd = lib.mcg_gru_seq_bwd(N, T, dz, dl, dc, ptr('params'), ptr('e'), labels, ptr('saved'), ptr('gz'), ptr('dparams'), None)
+        return fwd, bwd
+
+    for dz, dl, dc in ((0, 0, 50), (65, 0, 50), (64, 65, 50), (10, 119, 50), (1, 128, 50), (10, -1, 50), (10, 6, -1), (-3, 6, 50)):
+        assert gru(4, 16, dz, dl, dc) == (UNSUPPORTED, UNSUPPORTED), (dz, dl, dc)
+    assert gru(4, 16, 10, 6, 50, labels=None) == (BAD, BAD)                 # a one-hot without labels
+    assert gru(4, 16, 12, 6, 50, labels=None) == (BAD, BAD)
+    assert gru(4, 16, 64, 64, 50, labels=None) == (BAD, BAD)
+    for N, T in ((0, 16), (4, 0), (-1, 16), (4, -1)):
+        assert gru(N, T, 10, 0, 50) == (BAD, BAD), (N, T)
+    for hole in ('params', 'e', 'saved'):                                   # pointers BOTH entry points take (any other would leave one call acceptable)
+        assert gru(4, 16, 10, 0, 50, hole=hole) == (BAD, BAD), hole
+
+    fc = (lambda M, K, Co: lib.mcg_fc_fprop(M, K, Co, one, one, one, one, None),
+          lambda M, K, Co: lib.mcg_fc_dgrad(M, K, Co, one, one, one, 4, one, None),
+          lambda M, K, Co: lib.mcg_fc_dgrad(M, K, Co, one, one, None, 0, one, None),
+          lambda M, K, Co: lib.mcg_fc_wgrad(M, K, Co, one, one, one, one, None),
+          lambda M, K, Co: lib.mcg_fc_wgrad(M, K, Co, one, one, one, None, None))
+    for M, K, Co in ((64, 30, 60), (64, 1022, 62), (4, 2, 1), (0, 1024, 60), (64, 0, 60), (64, 1024, 0), (-8, 1024, 60), (64, -4, 60)):
+        for f in fc:
+            assert f(M, K, Co) == BAD, (M, K, Co)
+    for period in (0, -64, 6, 62, 48, 2048):                                # zero, negative, no multiple of 4 (twice), no divisor of K (twice)
+        assert lib.mcg_fc_dgrad(64, 1024, 62, one, one, one, period, one, None) == BAD, period
+
+    for N, C in ((0, 1), (19, 0), (0, 7), (-1, 7)):
+        for ce in (0, 1):
+            assert lib.mcg_loss_dis(N, C, one, one, one, one, ce, one, one, one, None) == BAD, (N, C, ce)
+            assert lib.mcg_loss_gen(N, C, one, one, one, ce, one, one, one, None) == BAD, (N, C, ce)
+    assert lib.mcg_loss_dis(19, 1, one, one, one, one, 1, one, one, one, None) == BAD         # no class columns beside the GAN logit
+    assert lib.mcg_loss_gen(19, 1, one, one, one, 1, one, one, one, None) == BAD
+    assert lib.mcg_loss_dis(19, 7, one, one, None, one, 1, one, one, one, None) == BAD        # classes without labels
+    assert lib.mcg_loss_dis(19, 7, one, one, one, None, 1, one, one, one, None) == BAD
+    assert lib.mcg_loss_gen(19, 7, one, one, None, 1, one, one, one, None) == BAD
+
+
 def test_product_path_refuses_host_tensors(hl):
     g = hl.make_geom(1, 4, 16, 16, 4, 64, 4)
     x = torch.zeros(16)

@@ -335,24 +335,44 @@ def test_conv_rejects_bad_geometry(hl):
 @pytest.mark.parametrize("M,K,Co", [(4, 512, 1), (3, 2048, 7), (32, 1024, 60),
                                     (512, 8192, 60), (100, 1024, 60), (77, 2048, 20),     # M >= 64, Co >= 16: the MFMA GEMM path
                                     (64, 32768, 7), (64, 8192, 7), (64, 32768, 1),        # D_V / D_I dc5 at the batch-32 step's 2n rows (infogan: 7)
-                                    (512, 32768, 1), (5, 64, 3)])                         # ... at the batch-256 step's; fewer rows than slices
+                                    (512, 32768, 1), (5, 64, 3),                          # ... at the batch-256 step's; fewer rows than slices
+                                    # G's dc1 at n_hidden = 50 + dim_zm off the default 60, and the thresholds of the three dispatches.
+                                    # fprop: GEMM | dot product per block; dgrad: eight rows | one row per block; wgrad (no db): GEMM | row slices
+                                    (64, 1024, 62),      # GEMM with Co % 4 != 0 | eight rows, Co % 4 != 0 (its loop is unrolled by 4) | row slices: Co % 4 != 0 at M >= 64
+                                    (80, 1024, 66),      # GEMM, a second column tile, a ragged second row tile | eight rows | row slices
+                                    (64, 1024, 114),     # GEMM, two column tiles, Co % 4 != 0 | eight rows | row slices
+                                    (72, 1024, 68),      # GEMM, Co > 64 | eight rows (M % 8 == 0, M % 64 != 0) | GEMM with Co > 64, M no multiple of its K-step
+                                    (64, 96, 20),        # dot products after the GEMM refuses K % 64 != 0 | eight rows | GEMM, two ragged tiles of K
+                                    (64, 1024, 8),       # dot products (Co < 16) | eight rows at their smallest Co | row slices
+                                    (63, 1024, 16),      # one row short of every M threshold: dot products | one row per block | row slices
+                                    (64, 1024, 16)])     # exactly on every threshold: GEMM | eight rows | GEMM
 def test_fc_ops(hl, M, K, Co):
     rng = np.random.RandomState(M * 7 + Co)
     x, w, b, gy = rng.randn(M, K), rng.randn(Co, K) * 0.05, rng.randn(Co), rng.randn(M, Co)
     xd, wd, bd, gyd = dev(x), dev(w), dev(b), dev(gy)
     yd = torch.empty((M, Co), device="cuda")
     hl.fc_fprop(M, K, Co, xd, wd, bd, yd)
-    assert rel_l2(yd, x @ w.T + b) < FWD_TOL
-    bias_k = rng.randn(64)
+    errs = {'fprop': rel_l2(yd, x @ w.T + b)}
+    yd = torch.full((M, Co), float('nan'), device="cuda")
+    hl.fc_fprop(M, K, Co, xd, wd, None, yd)
+    errs['fprop, no bias'] = rel_l2(yd, x @ w.T)
+    period = 64 if K % 64 == 0 else 32                           # (the period divides K: K = 96)
+    bias_k = rng.randn(period)
     gxd = torch.empty((M, K), device="cuda")
-    hl.fc_dgrad(M, K, Co, gyd, wd, dev(bias_k), 64, gxd)
-    assert rel_l2(gxd, gy @ w + np.tile(bias_k, K // 64)) < FWD_TOL
+    hl.fc_dgrad(M, K, Co, gyd, wd, dev(bias_k), period, gxd)
+    errs['dgrad'] = rel_l2(gxd, gy @ w + np.tile(bias_k, K // period))
+    gxd = torch.full((M, K), float('nan'), device="cuda")
+    hl.fc_dgrad(M, K, Co, gyd, wd, None, 0, gxd)                # the discriminators' last layer: no bias plane behind it
+    errs['dgrad, no bias'] = rel_l2(gxd, gy @ w)
     dwd = torch.ones((Co, K), device="cuda")
     hl.fc_wgrad(M, K, Co, xd, gyd, dwd)
-    assert rel_l2(dwd, gy.T @ x + 1) < BWD_TOL
+    errs['wgrad'] = rel_l2(dwd, gy.T @ x + 1)
     dwd, dbd = torch.ones((Co, K), device="cuda"), torch.ones(Co, device="cuda")      # with the bias gradient (the row-sliced kernel)
     hl.fc_wgrad(M, K, Co, xd, gyd, dwd, dbd)
-    assert rel_l2(dwd, gy.T @ x + 1) < BWD_TOL and rel_l2(dbd, gy.sum(0) + 1) < BWD_TOL
+    errs['wgrad with db'], errs['db'] = rel_l2(dwd, gy.T @ x + 1), rel_l2(dbd, gy.sum(0) + 1)
+    print("fc M=%d K=%d Co=%d:" % (M, K, Co), " ".join("%s %.2e" % kv for kv in errs.items()))
+    for k, v in errs.items():                                       # (measured first, then held: a failure leaves every figure behind)
+        assert v < (BWD_TOL if k in ('wgrad', 'wgrad with db', 'db') else FWD_TOL), (k, v)
 
 
 @pytest.mark.parametrize("C,M,act", [(64, 5000, 2), (128, 777, 1), (512, 64, 2), (256, 4096, 1)])
@@ -652,15 +672,54 @@ def test_pack_clip_u8_equals_the_reference_normalisation(hl, C, Cp):
         hl.pack_clip_u8(N, C, Cp, T, H * H, xf, out)                # a float tensor is not the loader's form
 
 
-@pytest.mark.parametrize("N,dim_zl,dz", [(5, 0, 10), (37, 6, 10), (7, 0, 24), (9, 6, 40), (3, 64, 64)])
-def test_gru_sequence(hl, N, dim_zl, dz):
-    """mcg_gru_seq_fwd / _bwd against the oracle's StatelessGRU steps: the register-resident kernels (dim_zm <= 16, the reference's
-    default 10 with and without labels) and the wide-state pair (weights in memory: --dim_zm up to 64, model/net.py:38-41)."""
-    rng = np.random.RandomState(N)
-    T, dc = 16, 50
+def gru_branch(dz, dl):
+    """Which kernel pair mcg_gru_seq_fwd / _bwd launch, restated from the words of include/mocogan_hip.h (dim_zm <= 16 and
+    dim_zm + dim_zl <= 32: a thread's weight rows in registers; beyond, up to 64 / 128, the weights are read from memory) and of
+    the host dispatch in csrc/small_ops.hip (the register kernels pad the input row, one-hot label + noise, to 16 or to 32)."""
+    if dz <= 16 and dz + dl <= 16:
+        return '<16>'
+    if dz <= 16 and dz + dl <= 32:
+        return '<32>'
+    return 'wide'
+
+
+GRU_BASE_CASES = [(5, 0, 10), (37, 6, 10), (7, 0, 24), (9, 6, 40), (3, 64, 64)]        # test_gru_sequence's rows: (N, dim_zl, dim_zm), T = 16
+
+# (N, dim_zm, dim_zl, T) beside the branch the row is there for
+GRU_BRANCH_CASES = [
+    ('<16>', (17, 16, 0, 16)),        # every unit lane live; a second block with one sample
+    ('<16>', (3, 1, 0, 2)),           # one unit
+    ('<16>', (4, 10, 6, 1)),          # one step: nothing to prefetch
+    ('<16>', (16, 10, 0, 24)),        # the sampler's other length; exactly one full block
+    ('<32>', (17, 10, 7, 16)),        # the smallest input count past 16
+    ('<32>', (5, 12, 6, 16)),         # --dim_zm 12 on the six MUG labels
+    ('<32>', (33, 16, 16, 16)),       # every unit lane and every input column live; three blocks
+    ('<32>', (6, 10, 22, 16)),        # the one-hot fill takes a second trip; in = 32
+    ('<32>', (3, 16, 1, 16)),         # in = 17
+    ('wide', (5, 17, 0, 16)),         # the smallest wide state
+    ('wide', (5, 16, 17, 16)),        # wide by the input count alone (in = 33)
+    ('wide', (6, 64, 0, 16)),         # the largest state, no labels
+    ('wide', (5, 2, 126, 16)),        # the largest input count; the one-hot fill takes a second trip of 64
+]
+
+
+@pytest.fixture(scope="module")
+def gru_arena():
+    from guard import Arena
+    return Arena(16 << 20)
+
+
+def _gru_fwd_bwd(hl, arena, N, dz, dim_zl, T, seed):
+    """mcg_gru_seq_fwd / _bwd inside guard bands against the oracle's StatelessGRU steps in float64: the state columns of z, the
+    four saved vectors and every link's gradient each to a bound of their own; the zc columns bit for bit; dparams += (a second
+    call doubles the first)."""
+    rng = np.random.RandomState(seed)
+    dc = 50
     p = onet.init_generator(rng, dim_zl=dim_zl, dim_zm=dz, n_filters=2, dtype=np.float64)
     gp = {k: (v + 0.1 * rng.randn(*v.shape)) for k, v in p.items() if k.startswith('g0/')}
-    draw = onet.gen_draw(rng, N, dim_zl=dim_zl, dim_zm=dz, dtype=np.float64)
+    draw = onet.gen_draw(rng, N, dim_zl=dim_zl, dim_zm=dz, video_len=T, dtype=np.float64)
+    if dim_zl and N >= 2:
+        draw['labels'][0], draw['labels'][1] = 0, dim_zl - 1        # the first and the last column of the one-hot always occur
     # oracle: run the recurrence alone
     gpo = {k[3:]: v for k, v in gp.items()}
     zl = np.eye(dim_zl)[draw['labels']] if dim_zl else None
@@ -671,23 +730,62 @@ def test_gru_sequence(hl, N, dim_zl, dz):
         hs.append(h), caches.append(c)
     z_ref = np.concatenate((np.tile(draw['zc'], (T, 1, 1)), np.stack(hs)), 2).reshape(T * N, dc + dz)
     lay = L()
-    flat = lay.gru_to_dev({k: dev(v) for k, v in gp.items()})
-    labels = dev(draw['labels'], torch.int32) if dim_zl else None
-    z = torch.empty((T * N, dc + dz), device="cuda")
-    saved = torch.empty((T, N, 4 * dz), device="cuda")
-    hl.gru_seq_fwd(N, T, dz, dim_zl, dc, flat, dev(draw['h0']), dev(draw['e']), labels, dev(draw['zc']), z, saved)
-    assert rel_l2(z, z_ref) < FWD_TOL
+    arena.reset()
+    flat = arena.put(lay.gru_to_dev({k: dev(v) for k, v in gp.items()}))
+    labels = arena.put(dev(draw['labels'], torch.int32)) if dim_zl else None
+    h0, e, zc = arena.put(dev(draw['h0'])), arena.put(dev(draw['e'])), arena.put(dev(draw['zc']))
+    z = arena.empty((T * N, dc + dz))                              # (poison: every element must be written)
+    saved = arena.empty((T, N, 4 * dz))
+    hl.gru_seq_fwd(N, T, dz, dim_zl, dc, flat, h0, e, labels, zc, z, saved)
+    arena.check()
+    tag = "gru N=%d dz=%d dl=%d T=%d %s:" % (N, dz, dim_zl, T, gru_branch(dz, dim_zl))
+    errs = {'z': rel_l2(z, z_ref), 'state': rel_l2(z[:, dc:], np.stack(hs).reshape(T * N, dz))}
+    for i, name in enumerate(('r', 'z', 'h_bar', 'h')):            # saved: [T][N][r | z | h_bar | h_prev]
+        errs['saved ' + name] = rel_l2(saved[:, :, i * dz:(i + 1) * dz], np.stack([c[name] for c in caches]))
+    print(tag, "fwd", " ".join("%s %.2e" % kv for kv in errs.items()))
+    assert torch.equal(z[:, :dc], zc.repeat(T, 1))
+    for k, v in errs.items():
+        assert v < FWD_TOL, (k, v)
     gz = rng.randn(T * N, dc + dz)
     grads = {k: np.zeros_like(v) for k, v in gpo.items()}
     gh = np.zeros((N, dz))
     for t in reversed(range(T)):
         gh = gh + gz.reshape(T, N, -1)[t][:, dc:]
         gh, _ = F.gru_step_bwd(gpo, caches[t], gh, grads)
-    dflat = torch.zeros_like(flat)
-    hl.gru_seq_bwd(N, T, dz, dim_zl, dc, flat, dev(draw['e']), labels, saved, dev(gz), dflat)
-    got = lay.gru_from_dev(dflat, dz, dim_zl, prefix='')
-    for k in grads:
-        assert rel_l2(got[k], grads[k]) < BWD_TOL, k
+    gzd = arena.put(dev(gz))
+    dflat = arena.zeros(tuple(flat.shape))
+    for call in (1, 2):                                             # dparams +=: the second call adds the same gradient again
+        hl.gru_seq_bwd(N, T, dz, dim_zl, dc, flat, e, labels, saved, gzd, dflat)
+        arena.check()
+        got = lay.gru_from_dev(dflat, dz, dim_zl, prefix='')
+        errs = {k: rel_l2(got[k], call * grads[k]) for k in grads}
+        print(tag, "bwd call %d" % call, " ".join("%s %.2e" % kv for kv in errs.items()))
+        for k, v in errs.items():
+            assert v < BWD_TOL, (call, k, v)
+
+
+@pytest.mark.parametrize("N,dim_zl,dz", GRU_BASE_CASES)
+def test_gru_sequence(hl, gru_arena, N, dim_zl, dz):
+    """mcg_gru_seq_fwd / _bwd against the oracle's StatelessGRU steps: the register-resident kernels (dim_zm <= 16, the reference's
+    default 10 with and without labels) and the wide-state pair (weights in memory: --dim_zm up to 64, model/net.py:38-41)."""
+    _gru_fwd_bwd(hl, gru_arena, N, dz, dim_zl, 16, seed=N)
+
+
+def test_gru_sequence_tables_reach_every_dispatch_branch():
+    """the two tables the GRU tests are parametrised with, as they stand: a later edit of either cannot silently drop a branch"""
+    from collections import Counter
+    hit = Counter(gru_branch(dz, dl) for _, dl, dz in GRU_BASE_CASES) + Counter(gru_branch(dz, dl) for _, (_, dz, dl, _) in GRU_BRANCH_CASES)
+    assert all(hit[b] >= 2 for b in ('<16>', '<32>', 'wide')), hit
+    assert all(gru_branch(dz, dl) == b for b, (_, dz, dl, _) in GRU_BRANCH_CASES)
+
+
+@pytest.mark.parametrize("branch,case", GRU_BRANCH_CASES, ids=["%s-N%d-zm%d-zl%d-T%d" % ((b,) + c) for b, c in GRU_BRANCH_CASES])
+def test_gru_sequence_dispatch_branches(hl, gru_arena, branch, case):
+    """Every kernel pair of the GRU dispatch at its boundaries (dim_zm 1, 16, 17, 64; 16, 17, 32, 33 and 128 inputs; one step and
+    24).  Measured on an MI355X (worst over the rows, bounds 1e-5 / 1e-5 / 1e-4): profiles/generator_head_parity.md."""
+    N, dz, dl, T = case
+    assert gru_branch(dz, dl) == branch
+    _gru_fwd_bwd(hl, gru_arena, N, dz, dl, T, seed=N + 100 * dz + 10000 * dl + 1000000 * T)
 
 
 @pytest.mark.parametrize("C,with_ce", [(1, False), (7, False), (7, True)])
@@ -711,6 +809,43 @@ def test_losses(hl, C, with_ce):
     hl.loss_gen(N, C, dev(yi.reshape(N, C)), dev(yf.reshape(N, C)), dev(tf, torch.int32), C == 7, loss, gi, gv)
     assert abs(float(loss) - l_ref) < 1e-5
     assert rel_l2(gi, gi_ref.reshape(N, C)) < 1e-5 and rel_l2(gv, gv_ref.reshape(N, C)) < 1e-5
+
+
+SATURATED = np.array([-100, -20, -1e-3, 0, 1e-3, 20, 100], np.float32).astype(np.float64)     # (as the device holds them)
+
+
+@pytest.mark.parametrize("N", [19, 300])
+@pytest.mark.parametrize("C,with_ce", [(1, False), (7, False), (7, True)])
+def test_losses_at_saturated_logits(hl, C, with_ce, N):
+    """Logits where softplus and sigmoid leave their comfortable range: +-100 (exp overflows fp32 one way, the term vanishes the
+    other), +-20 (1 + exp(-20) rounds to 1), +-1e-3 and 0.  Sample 0, the only one whose GAN term mcg_loss_dis evaluates, holds
+    the extremes.  The loss is held to 1e-5 relative to max(1, |loss|) (it reaches the hundreds), every gradient element to
+    1e-5 / N absolutely (an element is at most 2 / N; half of the reference underflows to zero, so a relative norm says nothing).
+    Measured on an MI355X: profiles/generator_head_parity.md."""
+    rng = np.random.RandomState(1000 * N + 10 * C + with_ce)
+    model = 'infogan' if C == 7 else 'normal'
+    yr, yf, yi = (SATURATED[rng.randint(0, 7, (N, C))] for _ in range(3))
+    first = SATURATED if C == 7 else SATURATED[6:]
+    yr[0], yf[0], yi[0] = first, first[::-1], first
+    tr, tf = rng.randint(0, 6, N), rng.randint(0, 6, N)
+    loss = torch.empty(1, device="cuda")
+    ga, gb = torch.empty((N, C), device="cuda"), torch.empty((N, C), device="cuda")
+
+    def check(what, refs):
+        l_ref, ga_ref, gb_ref = refs
+        l, da, db = float(loss), np.abs(ga.cpu().double().numpy() - ga_ref.reshape(N, C)).max(), np.abs(gb.cpu().double().numpy() - gb_ref.reshape(N, C)).max()
+        print("%s C=%d ce=%d N=%d: loss %.9g ref %.9g, |d| / max(1, |ref|) %.2e; max |dg| * N %.2e %.2e" % (
+            what, C, with_ce, N, l, l_ref, abs(l - l_ref) / max(1.0, abs(l_ref)), da * N, db * N))
+        assert np.isfinite(l) and bool(torch.isfinite(ga).all()) and bool(torch.isfinite(gb).all())
+        assert abs(l - l_ref) <= 1e-5 * max(1.0, abs(l_ref))
+        assert da <= 1e-5 / N and db <= 1e-5 / N
+
+    hl.loss_dis(N, C, dev(yr), dev(yf), dev(tr, torch.int32), dev(tf, torch.int32), with_ce, loss, ga, gb)
+    check("loss_dis", oupd.loss_dis(model, with_ce, yr.reshape(N, C, 1, 1, 1), yf.reshape(N, C, 1, 1, 1), tr, tf))
+    if C == 7 and not with_ce:
+        return
+    hl.loss_gen(N, C, dev(yi), dev(yf), dev(tf, torch.int32), C == 7, loss, ga, gb)
+    check("loss_gen", oupd.loss_gen(model, yi.reshape(N, C, 1, 1), yf.reshape(N, C, 1, 1, 1), tf))
 
 
 def test_adam_weight_decay(hl):

@@ -134,11 +134,15 @@ def test_discriminator_forward_backward(pkg, ndim, out, nf):
         assert rel_l2(st['bn%d/avg_var' % l], p_run['bn%d/avg_var' % l]) < 1e-5
 
 
-@pytest.mark.parametrize("dim_zl,nf,dim_zm", [(0, 8, 10), (6, 16, 10), (6, 8, 40)])        # (40: the wide-state GRU kernels, --dim_zm > 16)
-def test_generator_forward_backward(pkg, dim_zl, nf, dim_zm):
+@pytest.mark.parametrize("dim_zl,nf,dim_zm,n", [
+    pytest.param(0, 8, 10, 3, id="0-8-10"), pytest.param(6, 16, 10, 3, id="6-16-10"),
+    pytest.param(6, 8, 40, 3, id="6-8-40"),              # (40: the wide-state GRU kernels, --dim_zm > 16)
+    # 64 frames: dc1 on the GEMM (forward, weight gradient) and the eight-row input gradient, at n_hidden = 50 + dim_zm off 60
+    pytest.param(6, 8, 12, 4, id="6-8-12-n4"),           # 18 GRU inputs: the register kernels padded to 32; n_hidden = 62 (no multiple of 4)
+    pytest.param(0, 8, 16, 4, id="0-8-16-n4")])          # every unit lane of the register kernels live; n_hidden = 66 (a second column tile)
+def test_generator_forward_backward(pkg, dim_zl, nf, dim_zm, n):
     hl, lay, nets, _ = pkg
     rng = np.random.RandomState(200 + dim_zl)
-    n = 3
     p = _perturb(_f64(onet.init_generator(rng, dim_zl=dim_zl, dim_zm=dim_zm, n_filters=nf)), rng)
     draw = onet.gen_draw(rng, n, dim_zl=dim_zl, dim_zm=dim_zm, dtype=F64)
     x_ref, _, cache = onet.gen_forward(copy.deepcopy(p), draw)
