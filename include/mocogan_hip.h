@@ -311,7 +311,9 @@ int mcg_bn_act_bwd_from_sums(int64_t M, int64_t M_total, int C, const float* g_o
  *   mcg_bn_stats_from_partials   == mcg_bn_stats' finalize      (M = rows of the group)
  *   mcg_bn_act_bwd_from_partials == mcg_bn_act_bwd without its reduction pass over g_out and y
  *   mcg_colsum_from_partials     == mcg_colsum_acc without its pass over g
- * workspace: mcg_bn_workspace_bytes(M, C) (large slot counts are first folded into it, in a fixed order). */
+ * workspace: mcg_bn_workspace_bytes(M, C) (large slot counts are first folded into it, in a fixed order).
+ * Any n_slots >= 1, any slot_stride >= 2*C (columns outside the group's 2*C are never read) and any C % 4 == 0: these three have no
+ * pass over rows, so the C = 4 * 2^k limit of the column reductions above does not apply to them. */
 int mcg_bn_stats_from_partials(int64_t M, int C, const float* part, int n_slots, int slot_stride, const float* gamma,
                                const float* beta, float* stats, float* avg_mean, float* avg_var, float eps, float decay,
                                void* workspace, void* stream);
@@ -328,7 +330,8 @@ int mcg_colsum_acc(int64_t M, int C, const float* g, float* db, void* workspace,
 /* out[N][T][H][W][Cp] = x[N][C][T][H][W] (+ noise as above); padded channels = 0.  Turns the
  * reference-layout real clip batch (model/updater.py:89-90) into D's first conv input.
  * Element (n,c,t,hw) of x is at x + n*x_stride_n + c*x_stride_c + t*HW + hw, so a single frame
- * x[:, :, t] of a clip batch is expressed with T = 1 and the clip's strides. */
+ * x[:, :, t] of a clip batch is expressed with T = 1 and the clip's strides.  MCG_ERR_BAD_ARG (here and in mcg_pack_clip_u8):
+ * a null x / out, a non-positive extent, Cp < C, Cp % 4, a negative stride. */
 int mcg_pack_clip(int N, int C, int Cp, int T, int HW, const float* x, int64_t x_stride_n,
                   int64_t x_stride_c, const float* addend,
                   float sigma, uint64_t seed, uint64_t stream_id, float* out, void* stream);

@@ -1635,7 +1635,7 @@ extern "C" int mcg_colsum_acc(int64_t M, int C, const float* g, float* db, void*
 
 extern "C" int mcg_pack_clip(int N, int C, int Cp, int T, int HW, const float* x, int64_t x_stride_n, int64_t x_stride_c,
                              const float* addend, float sigma, uint64_t seed, uint64_t stream_id, float* out, void* stream) {
-    if (!x || !out || N <= 0 || C <= 0 || Cp < C || (Cp & 3) || T <= 0 || HW <= 0) return MCG_ERR_BAD_ARG;
+    if (!x || !out || N <= 0 || C <= 0 || Cp < C || (Cp & 3) || T <= 0 || HW <= 0 || x_stride_n < 0 || x_stride_c < 0) return MCG_ERR_BAD_ARG;
     long long npix = (long long)N * T * HW;
     hipLaunchKernelGGL(pack_clip_kernel, dim3(ew_grid(npix)), dim3(NT), 0, (hipStream_t)stream, N, C, Cp, T, HW, x,
                        (long long)x_stride_n, (long long)x_stride_c, addend, sigma, seed, stream_id, out);

@@ -122,6 +122,111 @@ def test_generator_head_entry_points_refuse_on_the_host(hl):
     assert lib.mcg_loss_gen(19, 7, one, one, None, 1, one, one, one, None) == BAD
 
 
+def test_layout_and_partial_sum_entry_points_refuse_on_the_host(hl):
+    """The layout kernels and the consumers of per-tile partial sums index with whatever extents and strides they are given: what
+    they cannot take is refused before anything is launched.  `one` is a non-null pointer that is never dereferenced, the outputs
+    are small host buffers that must come back untouched; no call below passes an acceptable argument set."""
+    lib = hl.load()
+    one = ctypes.c_void_p(16)
+    BAD, UNSUPPORTED = -1, -2
+    bufs = [(ctypes.c_float * 16)(*([3.0] * 16)) for _ in range(5)]
+    o1, o2, o3, o4, o5 = (ctypes.cast(b, ctypes.c_void_p) for b in bufs)
+    calls = []
+
+    def refused(code, rc, *what):
+        calls.append(what)
+        assert rc == code, (what, rc)
+        assert all(list(b) == [3.0] * 16 for b in bufs), what
+
+    pack = lambda N, C, Cp, T, HW, sn=1, sc=1, x=one, out=o1: lib.mcg_pack_clip(N, C, Cp, T, HW, x, sn, sc, None, 0.0, 0, 0, out, None)
+    pack8 = lambda N, C, Cp, T, HW, sn=1, st=1, x=one, out=o1: lib.mcg_pack_clip_u8(N, C, Cp, T, HW, x, sn, st, None, 0.0, 0, 0, out, None)
+    for name, f in (("mcg_pack_clip", pack), ("mcg_pack_clip_u8", pack8)):
+        refused(BAD, f(2, 5, 4, 3, 8), name, "Cp < C")
+        refused(BAD, f(2, 3, 6, 3, 8), name, "Cp % 4")
+        refused(BAD, f(2, 3, 0, 3, 8), name, "Cp = 0")
+        for ext in ((0, 3, 4, 3, 8), (2, 0, 4, 3, 8), (2, 3, 4, 0, 8), (2, 3, 4, 3, 0), (-2, 3, 4, 3, 8), (2, 3, 4, -3, 8), (2, 3, 4, 3, -8)):
+            refused(BAD, f(*ext), name, ext)
+        refused(BAD, f(2, 3, 4, 3, 8, sn=-72), name, "negative item stride")
+        refused(BAD, f(2, 3, 4, 3, 8, 72, -24), name, "negative channel / frame stride")
+        refused(BAD, f(2, 3, 4, 3, 8, x=None), name, "no x")
+        refused(BAD, f(2, 3, 4, 3, 8, out=None), name, "no out")
+
+    unpack = lambda N, C, Cp, T, HW, inp=one, x=o1: lib.mcg_unpack_clip(N, C, Cp, T, HW, inp, x, None)
+    refused(BAD, unpack(2, 5, 4, 3, 8), "mcg_unpack_clip", "Cp < C")
+    for ext in ((0, 3, 4, 3, 8), (2, 0, 4, 3, 8), (2, 3, 4, 0, 8), (2, 3, 4, 3, 0), (2, 3, 4, 3, -8)):
+        refused(BAD, unpack(*ext), "mcg_unpack_clip", ext)
+    refused(BAD, unpack(2, 3, 4, 3, 8, inp=None), "mcg_unpack_clip", "no in")
+    refused(BAD, unpack(2, 3, 4, 3, 8, x=None), "mcg_unpack_clip", "no x")
+
+    tanh = lambda N, T, fe, g=one, x=one, out=o1: lib.mcg_tanh_bwd_to_frames(N, T, fe, g, x, out, None)
+    for fe in (1, 2, 3, 6, 257, 0, -4):
+        refused(BAD, tanh(3, 5, fe), "mcg_tanh_bwd_to_frames", "frame_elems", fe)
+    refused(BAD, tanh(0, 5, 256), "mcg_tanh_bwd_to_frames", "N = 0")
+    refused(BAD, tanh(3, 0, 256), "mcg_tanh_bwd_to_frames", "T = 0")
+    for hole in range(3):
+        ptrs = [None if k == hole else p for k, p in enumerate((one, one, o1))]
+        refused(BAD, tanh(3, 5, 256, *ptrs), "mcg_tanh_bwd_to_frames", "null pointer", hole)
+
+    concat = lambda N, P, C, Cp, dl, Cq, x=one, labels=one, out=o1: lib.mcg_concat_label_planes(N, P, C, Cp, dl, Cq, x, labels, out, None)
+    refused(BAD, concat(3, 64, 3, 4, 6, 8), "mcg_concat_label_planes", "Cq < C + dl")
+    refused(BAD, concat(3, 64, 3, 4, 0, 0), "mcg_concat_label_planes", "Cq < C")
+    refused(BAD, concat(3, 64, 3, 4, 6, 10), "mcg_concat_label_planes", "Cq % 4")
+    refused(BAD, concat(3, 64, 3, 4, 6, 12, labels=None), "mcg_concat_label_planes", "label planes without labels")
+    refused(BAD, concat(3, 64, 5, 4, 6, 12), "mcg_concat_label_planes", "Cp < C")
+    refused(BAD, concat(3, 64, 3, 4, -1, 12), "mcg_concat_label_planes", "dl < 0")
+    refused(BAD, concat(0, 64, 3, 4, 6, 12), "mcg_concat_label_planes", "N = 0")
+    refused(BAD, concat(3, 0, 3, 4, 6, 12), "mcg_concat_label_planes", "P = 0")
+    refused(BAD, concat(3, 64, 0, 4, 6, 12), "mcg_concat_label_planes", "C = 0")
+    refused(BAD, concat(3, 64, 3, 4, 6, 12, x=None), "mcg_concat_label_planes", "no x")
+    refused(BAD, concat(3, 64, 3, 4, 6, 12, out=None), "mcg_concat_label_planes", "no out")
+
+    # the consumers of partial sums: stats (o1), running averages (o2, o3), gx (o1), dgamma / dbeta (o2, o3), db (o1), workspace (o4)
+    def stats(M, C, n, stride, part=one, am=o2, av=o3, ws=o4):
+        return lib.mcg_bn_stats_from_partials(M, C, part, n, stride, one, one, o1, am, av, 2e-5, 0.9, ws, None)
+
+    def bwd(M, C, n, stride, part=one, ws=o4, flags=0, gx=o1):
+        return lib.mcg_bn_act_bwd_from_partials(M, C, one, one, one, one, 2, part, n, stride, gx, flags, o2, o3, ws, None)
+
+    def colsum(M, C, n, stride, part=one, ws=o4):
+        return lib.mcg_colsum_from_partials(C, part, n, stride, o1, ws, None)
+
+    for name, f in (("mcg_bn_stats_from_partials", stats), ("mcg_bn_act_bwd_from_partials", bwd), ("mcg_colsum_from_partials", colsum)):
+        refused(BAD, f(64, 8, 0, 16), name, "n_slots = 0")
+        refused(BAD, f(64, 8, -3, 16), name, "n_slots < 0")
+        refused(BAD, f(64, 8, 5, 15), name, "slot_stride < 2 C")
+        refused(BAD, f(64, 8, 5, 8), name, "slot_stride = C")
+        refused(BAD, f(64, 8, 5, 0), name, "slot_stride = 0")
+        refused(BAD, f(64, 6, 5, 16), name, "C % 4")
+        refused(BAD, f(64, 0, 5, 16), name, "C = 0")
+        refused(BAD, f(64, 8, 5, 16, part=None), name, "no partials")
+    refused(BAD, stats(0, 8, 5, 16), "mcg_bn_stats_from_partials", "M = 0")
+    refused(BAD, bwd(0, 8, 5, 16), "mcg_bn_act_bwd_from_partials", "M = 0")
+    refused(BAD, stats(64, 8, 5, 16, av=None), "mcg_bn_stats_from_partials", "avg_mean without avg_var")
+    refused(BAD, stats(64, 8, 5, 16, am=None), "mcg_bn_stats_from_partials", "avg_var without avg_mean")
+    refused(BAD, bwd(64, 8, 5, 16, ws=None), "mcg_bn_act_bwd_from_partials", "no workspace")
+    refused(BAD, bwd(64, 8, 5, 16, gx=None), "mcg_bn_act_bwd_from_partials", "no gx")
+    refused(BAD, bwd(64, 8, 5, 16, flags=hl.IO_OUT_BF16, gx=one), "mcg_bn_act_bwd_from_partials", "in place across element types")
+    refused(UNSUPPORTED, bwd(64, 8, 5, 16, flags=hl.IO_OUT_SPLIT), "mcg_bn_act_bwd_from_partials", "split output of 8 channels")
+
+    acc = lambda M, C, g=one, db=o1, ws=o4: lib.mcg_colsum_acc(M, C, g, db, ws, None)
+    refused(BAD, acc(0, 8), "mcg_colsum_acc", "M = 0")
+    refused(BAD, acc(-5, 8), "mcg_colsum_acc", "M < 0")
+    refused(BAD, acc(64, 6), "mcg_colsum_acc", "C % 4")
+    refused(BAD, acc(64, 0), "mcg_colsum_acc", "C = 0")
+    refused(UNSUPPORTED, acc(64, 24), "mcg_colsum_acc", "6 channel quads do not divide a block")
+    refused(UNSUPPORTED, acc(64, 2048), "mcg_colsum_acc", "more channel quads than threads")
+    refused(BAD, acc(64, 8, g=None), "mcg_colsum_acc", "no g")
+    refused(BAD, acc(64, 8, db=None), "mcg_colsum_acc", "no db")
+    refused(BAD, acc(64, 8, ws=None), "mcg_colsum_acc", "no workspace")
+
+    quad = lambda M, C, out=o1: lib.mcg_randn_rowquad(M, C, 0.2, 1, 2, out, None)
+    for M in (1, 2, 3, 5, 6, 1023, 0, -4):
+        refused(BAD, quad(M, 64), "mcg_randn_rowquad", "M", M)
+    refused(BAD, quad(64, 0), "mcg_randn_rowquad", "C = 0")
+    refused(BAD, quad(64, 64, out=None), "mcg_randn_rowquad", "no out")
+    assert len(calls) > 100
+
+
 def test_product_path_refuses_host_tensors(hl):
     g = hl.make_geom(1, 4, 16, 16, 4, 64, 4)
     x = torch.zeros(16)
