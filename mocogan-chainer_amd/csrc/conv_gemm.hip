@@ -151,13 +151,47 @@ __device__ __forceinline__ constexpr int dense_src(int d) { return dense_group(d
 template <bool DN> struct DenseOff { static constexpr int akd[3] = {0, 0, 0}; };
 template <> struct DenseOff<true> { int akd[3]; };
 
+// Position-major rows of a forward GEMM (policy parameter LV of FpropP; tile codes 27 / 40 / 37).  Row m is (pos, q) = (m / (N To),
+// m % (N To)): pos = (ho, wo), q = (n, to).  A tile's rows then share their spatial position (or a few neighbouring ones), and a
+// filter tap that reads zero padding for EVERY row of the tile -- kh = 0 at ho = 0, kh = 3 at ho = Ho - 1, the same along w -- is
+// left out of the K loop: (1 - 1 / (2 Ho))^2 of the K-steps are live on average.  The output tensor keeps its layout.
+// live_taps: the 16 spatial taps that read inside the image at output position pos (what FpropP::init computes per row)
+__host__ __device__ inline u32 live_taps(int Ho, int Wo, int lgWo, int pos) {
+    const int ho = pos >> lgWo, wo = pos & (Wo - 1);
+    const u32 wbits = (wo > 0 ? 1u : 0u) | 6u | (wo < Wo - 1 ? 8u : 0u);
+    return (ho > 0 ? wbits : 0u) | wbits << 4 | wbits << 8 | (ho < Ho - 1 ? wbits << 12 : 0u);
+}
+// ... OR-ed over the positions p0 .. p1 of a row tile
+__host__ __device__ inline u32 live_taps_of_tile(int Ho, int Wo, int lgWo, int p0, int p1) {
+    u32 mk = 0;
+    for (int p = p0; p <= p1 && mk != 0xffffu; ++p) mk |= live_taps(Ho, Wo, lgWo, p);
+    return mk;
+}
+// Blocks cut by live K-steps (tile codes 1027 / 1040, 2027 / 2040): a row tile runs as `parts` blocks, each an equal share (to
+// within one) of the tile's LIVE steps; the partial tiles of a cut tile are added onto the cleared y (as split K), a tile left
+// whole is stored.  blk[c], block c along x: row tile | part << 8 | (parts - 1) << 12, part-major -- neighbouring blocks (one XCD,
+// one L2) are the same part of neighbouring tiles, i.e. they read the same filter taps at about the same time.
+constexpr int LIVE_MAX_TILES = 256, LIVE_MAX_PARTS = 16, LIVE_MAX_BLOCKS = 1024;
+template <bool ON> struct LiveRows {};
+template <> struct LiveRows<true> {
+    int nto; u32 magic_nto;            // N * To rows per position; m / nto == umulhi(m, magic_nto) (the launcher checks the range)
+    int chunked;                       // the launch cuts its tiles by live steps
+    u32 live;                          // block-uniform: the taps some row of this block's tile reads inside the image
+    int part, parts;                   // this block is part `part` of the `parts` blocks of its tile
+    int o_first, o_count;              // ... and runs the tile's live steps o_first .. o_first + o_count - 1
+    unsigned short blk[LIVE_MAX_BLOCKS];
+};
+
 // ---------------- fprop ----------------
 // NT: threads per block (the slot convention with NT threads); SW: the K-contiguous 16-byte slot a thread LOADS is XOR-swizzled
 // by its tile row, ((row >> 1) & 7) -- the source-side half of the LDS-DMA kernels' bank-conflict-free tile image (the
 // destination of an LDS-DMA load is lane-linear, so the permutation goes on the source address; gemm_bf16_v2_kernel).
-template <int BM, int BN, int BK, int E_ = 4, bool ST = false, int NT = NTHREADS, bool SW = false, bool DN = false>
-struct FpropP : DenseOff<DN> {
+// LV: 0 = rows in memory order; 1 = position-major rows, all-padding taps skipped (see live_taps); 2 = position-major, nothing
+// skipped (tile code 37: what code 27 must equal bit for bit)
+template <int BM, int BN, int BK, int E_ = 4, bool ST = false, int NT = NTHREADS, bool SW = false, bool DN = false, int LV = 0>
+struct FpropP : DenseOff<DN>, LiveRows<LV != 0> {
     using DenseOff<DN>::akd;
+    static constexpr int KADV = DN ? 4 * BK : BK;   // k of one pass of the kernel's loop body
     static constexpr bool A_KC = true, B_KC = true;
     static constexpr int ORDER = 0;
     static constexpr int E = E_, ESZ = 16 / E_, EA = E_, EB = E_;
@@ -189,7 +223,14 @@ struct FpropP : DenseOff<DN> {
         zz = z;
         ak = SW ? ((tid % KC4) ^ ((tid / (2 * KC4)) & (KC4 - 1))) * E : (tid % KC4) * E;
         krot = 0;
-        if (g.kt == 4) {
+        if constexpr (LV != 0) {
+            const int last = (m0 + BM < M ? m0 + BM : M) - 1;
+            this->live = LV == 2 ? 0xffffu : live_taps_of_tile(g.Ho, g.Wo, g.lgWo, (int)__umulhi((u32)m0, this->magic_nto), (int)__umulhi((u32)last, this->magic_nto));
+            const int cnt = live_steps();
+            this->o_first = (int)((long long)this->part * cnt / this->parts);
+            this->o_count = (int)((long long)(this->part + 1) * cnt / this->parts) - this->o_first;
+            if (this->parts > 1) { kchunk = 0; zz = this->o_first; }   // partial tile: added onto the cleared y, the first part carries the bias
+        } else if (g.kt == 4) {
             const int q0 = m0 >> (g.lgWo + g.lgHo);
             const int to0 = q0 - div_To(g, q0) * g.To;
             krot = ((4 - (to0 & 3)) & 3) * 16 * g.Ci;
@@ -204,6 +245,10 @@ struct FpropP : DenseOff<DN> {
             bool ok = m < M;
             int mm = ok ? m : 0;
             int wo = mm & (g.Wo - 1), ho = (mm >> g.lgWo) & (g.Ho - 1), q = mm >> (g.lgWo + g.lgHo);
+            if constexpr (LV != 0) {
+                const int pos = (int)__umulhi((u32)mm, this->magic_nto);
+                q = mm - pos * this->nto; wo = pos & (g.Wo - 1); ho = pos >> g.lgWo;
+            }
             int n = div_To(g, q), to = q - n * g.To;
             int hi0 = 2 * ho - 1, wi0 = 2 * wo - 1;
             abase[j] = ((int)x_batch_off(g, n) + ((to * g.Hi + hi0) * g.Wi + wi0) * g.Ci) * ESZ;
@@ -227,9 +272,54 @@ struct FpropP : DenseOff<DN> {
             for (int j = 0; j < NB; ++j) bbase[j] = OOB;
         }
     }
-    __device__ int k_begin(int z) const { return z * kchunk; }
-    __device__ int k_end(int z) const { int e = (z + 1) * kchunk; return e < K ? e : K; }
-    __device__ int next_valid(int k0) const { return k0; }
+    __device__ int k_begin(int z) const { if constexpr (LV != 0) return live_k(this->o_first); else return z * kchunk; }
+    __device__ int k_end(int z) const {
+        if constexpr (LV != 0) return live_k(this->o_first + this->o_count - 1) + KADV;
+        else { int e = (z + 1) * kchunk; return e < K ? e : K; }
+    }
+    // LV: the first K-step >= k0 whose tap some row of the tile reads inside the image (a K-step lies inside one tap: v2_ok, dense_ok)
+    __device__ int next_valid(int k0) const {
+        if constexpr (LV != 0) {
+            while (k0 < K) {
+                const int tap = k0 >> g.lgCi;
+                if ((this->live >> (tap & 15)) & 1u) break;
+                k0 = (tap + 1) << g.lgCi;
+            }
+        }
+        return k0;
+    }
+    // LV: the tile's live K-steps, and the k of live step o (temporal tap by temporal tap, the set bits of `live` in order)
+    __device__ int live_steps() const { return (__builtin_popcount(this->live) * g.kt * g.Ci) / KADV; }
+    __device__ int live_k(int o) const {
+        const int per_tap = g.Ci / KADV;                        // (a power of two)
+        int j = o / per_tap;
+        const int r = o - j * per_tap, pc = __builtin_popcount(this->live);
+        int a = 0;
+        while (j >= pc) { j -= pc; ++a; }
+        u32 mk = this->live;
+        for (int i = 0; i < j; ++i) mk &= mk - 1;
+        return (((a << 4) + __builtin_ctz(mk)) << g.lgCi) + r * KADV;
+    }
+    // the kernel's block index along x -> row tile (chunked launches: through blk, block-uniform)
+    template <int L_ = LV, class = typename std::enable_if<L_ != 0>::type> __device__ int locate(int c) {     // (position-major policies only: block_tile)
+        this->part = 0; this->parts = 1;
+        if (!this->chunked) return c;
+        // The table is indexed with a run-time value: read through the kernel's copy of the policy it would put the whole policy
+        // into scratch, so it is read where it lies, in the kernel-argument segment (the policy is the kernel's only argument).
+        typedef __attribute__((address_space(4))) const unsigned char* karg_t;
+        const long at = reinterpret_cast<const unsigned char*>(&this->blk[0]) - reinterpret_cast<const unsigned char*>(this);
+        const int e = *reinterpret_cast<__attribute__((address_space(4))) const unsigned short*>((karg_t)__builtin_amdgcn_kernarg_segment_ptr() + at + 2 * c);
+        this->part = (e >> 8) & 15; this->parts = (e >> 12) + 1;
+        return e & 255;
+    }
+    // output row (pixel index of the tensor in memory) of GEMM row m, and its batch item
+    __device__ int out_row(int m, int& n) const {
+        if constexpr (LV != 0) {
+            const int pos = (int)__umulhi((u32)m, this->magic_nto), q = m - pos * this->nto;
+            n = div_To(g, q);
+            return (q << (g.lgWo + g.lgHo)) + pos;
+        } else { n = 0; return m; }
+    }
     __device__ int rotated(int k0) const { int k = k0 + krot; return k >= K ? k - K : k; }     // whole K-steps stay inside one tap
     __device__ void load_a(int k0, f32x4 (&r)[NA]) const {
         static_assert(!DN, "register-staged loaders: each_a / each_b would give a dense policy its step-0 offsets");
@@ -270,7 +360,10 @@ struct FpropP : DenseOff<DN> {
     }
     // plain epilogue: the row part of an output address is computed once per accumulator row (row_off), not per element
     static constexpr bool HAS_ROW_OFF = true;
-    __device__ long long row_off(int m) const { return m < M ? (long long)m * g.Co : -1; }
+    __device__ long long row_off(int m) const {
+        if constexpr (LV != 0) { int n; return m < M ? (long long)out_row(m, n) * g.Co : -1; }
+        else return m < M ? (long long)m * g.Co : -1;
+    }
     __device__ void store_at(long long ro, int n, float v) const {
         if (ro < 0 || n >= g.Co) return;
         if (e.out16) reinterpret_cast<__bf16*>(y)[ro + n] = (__bf16)(v + (bias ? bias[n] : 0.f));
@@ -302,6 +395,12 @@ struct FpropP : DenseOff<DN> {
     __device__ int slot(int bx, int /*bz*/) const { return bx; }
     __device__ RowInfo row_info(int m) const {
         RowInfo r;
+        if constexpr (LV != 0) {
+            int n;
+            r.ok = m < M; r.pix = out_row(r.ok ? m : 0, n); r.base = (long long)r.pix * g.Co;
+            r.grp = (e.groups == 2 && n >= e.half_n) ? 1 : 0;
+            return r;
+        }
         r.ok = m < M; r.base = (long long)m * g.Co; r.pix = m;
         r.grp = (e.groups == 2 && (long long)m >= e.grp_rows) ? 1 : 0;
         return r;
@@ -550,8 +649,20 @@ struct DgradP : DenseOff<DN> {
 // EA_ (MCG_PREC_BF16_Y16, register-staged kernels): elements per 16-byte slot of the A operand (y) when it differs from the B
 // operand's (x): 8 = y bf16 in memory beside an fp32 x.
 // DN (with SPL): the dense form -- the k rows of a triple of K-steps are 12 blocks of 16 rows, 3 planes x 4 groups of 16 pixels.
-template <int BM, int BN, int BK, int E_ = 4, int NT = NTHREADS, bool SW = false, bool SPL = false, int EA_ = E_, bool DN = false>
-struct WgradP {
+// PJ (with SPL; tile codes 27 / 28): the pixel axis is visited position-major -- pixel p of the sum is (pos, q) = (p / (N To),
+// p % (N To)), as FpropP's LV rows.  N To is a multiple of the K advance (16 pixels; dense: 64), so an advance lies inside ONE
+// output position and its decode is block-uniform; an advance whose position reads zero padding for every filter tap of the
+// block's column tile is left out (next_valid), and the pixel splits are cut in the column tile's LIVE advances.
+template <bool ON> struct LivePix {};
+template <> struct LivePix<true> {
+    int nto; u32 magic_nto;            // N * To pixels per position; p / nto == umulhi(p, magic_nto) (the launcher checks the range)
+    u32 tmask;                         // block-uniform: the spatial taps (bit kh * 4 + kw) of this block's column tile
+    int o_first, o_count;              // this block's live advances of its column tile
+};
+template <int BM, int BN, int BK, int E_ = 4, int NT = NTHREADS, bool SW = false, bool SPL = false, int EA_ = E_, bool DN = false, bool PJ = false>
+struct WgradP : LivePix<PJ> {
+    static_assert(!PJ || SPL, "position-major pixels: split operands");
+    static constexpr int ADV = DN ? 64 : 16;       // (SPL) pixels of one pass of the kernel's loop body
     static constexpr bool HAS_EPI = false;
     static constexpr bool HAS_ROW_OFF = false;
     static constexpr bool A_KC = false, B_KC = false;
@@ -566,9 +677,17 @@ struct WgradP {
     u32 aoff; int akrow[NA];      // A: byte offset of this thread's 4 output channels (OOB beyond Co)
     bool bok; int bt, bkh, bkw, bci; int bkrow[NB];
 
-    __device__ void init(int m0, int n0, int tid, int /*z*/) {
+    __device__ void init(int m0, int n0, int tid, int z) {
         constexpr int AC4 = BM / EA, BC4 = BN / E;
         xr = make_srd(x, g.x_bytes); yr = make_srd(y, g.y_bytes);
+        if constexpr (PJ) {
+            const int kf1 = (n0 + BN < Kf ? n0 + BN : Kf) - 1;
+            this->tmask = 0;
+            for (int t = n0 >> g.lgCi; t <= kf1 >> g.lgCi; ++t) this->tmask |= 1u << (t & 15);
+            const int cnt = live_positions() * (this->nto / ADV), nz = (int)gridDim.z;
+            this->o_first = (int)((long long)z * cnt / nz);
+            this->o_count = (int)((long long)(z + 1) * cnt / nz) - this->o_first;
+        }
         int aco = m0 + (SW && EA == 8 ? ((tid % AC4) ^ sw_cols(tid / AC4, AC4)) : tid % AC4) * EA;
         aoff = aco < g.Co ? (SPL ? (u32)((aco >> 4) * 64 + (aco & 8)) * 2u : (u32)aco * (u32)ESZA) : OOB;
 #pragma unroll
@@ -590,11 +709,11 @@ struct WgradP {
         for (int j = 0; j < NA; ++j) {
             if constexpr (SPL && DN) {
                 const int d = 4 * s + (akrow[j] >> 4), grp = dense_group(d), plane = d - 3 * grp;
-                const int pix = (k0 >> 2) + 16 * grp + (akrow[j] & 15);
-                f(j, pix < Mpix ? aoff + (u32)(pix * 4 * g.Co + plane * 16) * 2u : OOB, 0u);
+                const int p = (k0 >> 2) + 16 * grp + (akrow[j] & 15), pix = mem_pixel(p);
+                f(j, p < Mpix ? aoff + (u32)(pix * 4 * g.Co + plane * 16) * 2u : OOB, 0u);
             } else if constexpr (SPL) {
-                const int plane = akrow[j] >> 4, pix = (k0 >> 2) + (akrow[j] & 15);
-                f(j, plane < 3 ? aoff + (u32)(pix * 4 * g.Co + plane * 16) * 2u : OOB, 0u);       // (pixels beyond Mpix: beyond the buffer)
+                const int plane = akrow[j] >> 4, p = (k0 >> 2) + (akrow[j] & 15), pix = mem_pixel(p);
+                f(j, plane < 3 ? aoff + (u32)(pix * 4 * g.Co + plane * 16) * 2u : OOB, 0u);       // (pixels beyond Mpix: beyond the buffer; PJ: there are none)
             } else f(j, aoff + (u32)((k0 + akrow[j]) * g.Co) * (u32)ESZA, 0u);
         }
     }
@@ -606,7 +725,11 @@ struct WgradP {
             bool ok = bok && pix < Mpix;
             if constexpr (SPL) {
                 const int plane = DN ? dq - 3 * dgrp : bkrow[j] >> 4;
-                const int wo = pix & (g.Wo - 1), ho = (pix >> g.lgWo) & (g.Ho - 1), q = pix >> (g.lgWo + g.lgHo);
+                int wo = pix & (g.Wo - 1), ho = (pix >> g.lgWo) & (g.Ho - 1), q = pix >> (g.lgWo + g.lgHo);
+                if constexpr (PJ) {
+                    const int pos = (int)__umulhi((u32)pix, this->magic_nto);
+                    q = pix - pos * this->nto; wo = pos & (g.Wo - 1); ho = pos >> g.lgWo;
+                }
                 const int n = div_To(g, q), to = q - n * g.To;
                 const int hi = 2 * ho - 1 + bkh, wi = 2 * wo - 1 + bkw;
                 ok = ok && plane < 3 && (unsigned)hi < (unsigned)g.Hi && (unsigned)wi < (unsigned)g.Wi;
@@ -624,9 +747,44 @@ struct WgradP {
             f(j, ok ? vo : OOB, 0u);
         }
     }
-    __device__ int k_begin(int z) const { return z * chunk * (SPL ? 4 : 1); }
-    __device__ int k_end(int z) const { int e = (z + 1) * chunk; return (e < Mpix ? e : Mpix) * (SPL ? 4 : 1); }
-    __device__ int next_valid(int k0) const { return k0; }
+    __device__ int k_begin(int z) const { if constexpr (PJ) return this->o_count > 0 ? live_k(this->o_first) : 0; else return z * chunk * (SPL ? 4 : 1); }
+    __device__ int k_end(int z) const {
+        if constexpr (PJ) return this->o_count > 0 ? live_k(this->o_first + this->o_count - 1) + 4 * ADV : 0;
+        else { int e = (z + 1) * chunk; return (e < Mpix ? e : Mpix) * (SPL ? 4 : 1); }
+    }
+    // PJ: the first advance >= k0 at a position where some tap of the column tile reads inside the image
+    __device__ int next_valid(int k0) const {
+        if constexpr (PJ) {
+            while (k0 < 4 * Mpix) {
+                const int pos = (int)__umulhi((u32)(k0 >> 2), this->magic_nto);
+                if (live_taps(g.Ho, g.Wo, g.lgWo, pos) & this->tmask) break;
+                k0 = 4 * (pos + 1) * this->nto;
+            }
+        }
+        return k0;
+    }
+    // PJ: pixel p of the sum -> pixel of y in memory (its batch item and frame q, its position pos)
+    __device__ int mem_pixel(int p) const {
+        if constexpr (PJ) {
+            const int pos = (int)__umulhi((u32)p, this->magic_nto);
+            return ((p - pos * this->nto) << (g.lgWo + g.lgHo)) + pos;
+        } else return p;
+    }
+    // PJ: positions with a live tap of the column tile; k (quarter pixels) of the tile's live advance o
+    __device__ int live_positions() const {
+        int c = 0;
+        for (int pos = 0; pos < g.Ho * g.Wo; ++pos) c += (live_taps(g.Ho, g.Wo, g.lgWo, pos) & this->tmask) ? 1 : 0;
+        return c;
+    }
+    __device__ int live_k(int o) const {
+        const int per_pos = this->nto / ADV;
+        int j = o / per_pos, pos = 0;
+        const int r = o - j * per_pos;
+        for (;; ++pos) {
+            if (live_taps(g.Ho, g.Wo, g.lgWo, pos) & this->tmask) { if (j == 0) break; --j; }
+        }
+        return 4 * (pos * this->nto + r * ADV);
+    }
     __device__ void load_a(int k0, f32x4 (&r)[NA]) const {
         // rows beyond Mpix fall outside the buffer: the range check returns zeros
 #pragma unroll
@@ -895,6 +1053,9 @@ template <class P> __device__ __forceinline__ bool dgrad_block(const P& p, int L
     return true;
 }
 
+// p.locate(block index along x) -> row tile where the policy has one (FpropP with position-major rows), else the index itself
+template <class P> __device__ __forceinline__ auto block_tile(P& p, int bx, int) -> decltype(p.locate(bx)) { return p.locate(bx); }
+template <class P> __device__ __forceinline__ int block_tile(P&, int bx, long) { return bx; }
 // p.idle(first live K-step, end of the block's K range) where the policy has one (DgradP), else false
 template <class P> __device__ __forceinline__ auto block_idle(const P& p, int k, int kend, int) -> decltype(p.idle(k, kend)) { return p.idle(k, kend); }
 template <class P> __device__ __forceinline__ bool block_idle(const P&, int, int, long) { return false; }
@@ -1471,6 +1632,10 @@ __device__ __forceinline__ void frag_wait(bf16x8 (&d)[T], s16x4 (&lo)[NL], s16x4
 // for bit the padded form's.  Three quarters of the LDS-DMA instructions, K-steps and barriers for the same MFMAs.
 template <class P, int BM, int BN, int STAGES, int EPI = 0, int SPLIT = 0>
 __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
+    // The policy is this kernel's ONLY argument, at offset 0 of the kernel-argument segment: FpropP::locate reads its block list
+    // there (a run-time index into the kernel's own copy would put the whole policy into scratch).  A second argument, or
+    // anything in front of `p`, breaks that read: change locate() with it.
+    static_assert(sizeof(P) <= 4096, "the policy is the whole kernel-argument segment");
     // P::E == 8: bf16 operands, BK = 64, v_mfma_f32_32x32x16_bf16.  P::E == 4: fp32 operands, BK = 32, v_mfma_f32_32x32x2_f32 --
     // the same tile bytes, the same LDS images (a K-contiguous row is 128 bytes either way), the same ring; tiles in global
     // orientation are read column-wise with ds_read_b32 (conflict-free as they are: no swizzle, no transposing read for 4-byte data).
@@ -1503,6 +1668,7 @@ __global__ __launch_bounds__(NT2) void gemm_bf16_v2_kernel(P p) {
             if (!dgrad_block(p, blockIdx.x, bx, by, bz)) return;
         } else { bx = t % gx; by = (t / gx) % gy; bz = t / (gx * gy); }
     }
+    bx = block_tile(p, bx, 0);
     const int m0 = bx * BM, n0 = by * BN;
     const int z = bz;
     p.init(m0, n0, tid, z);
@@ -3038,6 +3204,11 @@ bool fits(long long elems, int esz) { return elems * esz < (1ll << 31); }
 // Tile codes of the dense LDS form of split operands: 17 / 20 = tile 7 / 10.  (No 18: with the fragments of a 256x256 tile's
 // carried planes gemm_bf16_v2_kernel<.., SPLIT = 2> needs 40-92 bytes of scratch at two waves per SIMD; that tile keeps the padded form.)
 bool dense_code(int t) { return t == 17 || t == 20; }
+// ... and of the dense form with position-major rows (forward only; FpropP's LV): 27 / 40 = 17 / 20 with the all-padding taps
+// skipped, 37 = 27 with nothing skipped (the bit-for-bit reference of 27).  + 1000 / + 2000: the tiles cut by live K-steps into
+// about one / two blocks per resident slot (plan_fprop_live); without it one block per tile, which can carry an epilogue.
+// 28 (weight gradient only): the padded 256x256/2 tile with a position-major pixel axis (WgradP's PJ); 27 there: 128x256/3 dense.
+int live_code(int t) { return t == 27 || t == 40 || t == 28 ? 1 : t == 37 ? 2 : 0; }
 
 int make_geom(const mcg_conv_geom* c, Geom& g) {
     if (!c) return MCG_ERR_BAD_ARG;
@@ -3052,10 +3223,14 @@ int make_geom(const mcg_conv_geom* c, Geom& g) {
     if (c->ci_valid < 0 || c->ci_valid > c->Ci) return MCG_ERR_BAD_ARG;
     g.cv = c->ci_valid ? c->ci_valid : c->Ci;
     if (g.prec != MCG_PREC_F32 && g.prec != MCG_PREC_BF16 && g.prec != MCG_PREC_BF16_STORE && g.prec != MCG_PREC_SPLIT) return MCG_ERR_BAD_ARG;
-    if (c->tile < 0 || (c->tile % 100 > 10 && !dense_code(c->tile % 100)) || (c->tile / 100) % 10 > 2 || c->tile / 1000 > 2) return MCG_ERR_BAD_ARG;
-    g.dense = dense_code(c->tile % 100) ? 1 : 0;                 // 17 / 20: tile 7 / 10 with the dense LDS form of split operands
+    const int lv = live_code(c->tile % 100);
+    if (c->tile < 0 || (c->tile % 100 > 10 && !dense_code(c->tile % 100) && !lv) || (c->tile / 100) % 10 > 2 || c->tile / 1000 > 2) return MCG_ERR_BAD_ARG;
+    // 17 / 20: tile 7 / 10 with the dense LDS form of split operands; host side only: + 2 * LV for the position-major codes
+    // (28: 2 -- position-major, padded LDS form)
+    g.dense = dense_code(c->tile % 100) ? 1 : c->tile % 100 == 28 ? 2 : lv ? 1 + 2 * lv : 0;
     if (g.dense && g.prec != MCG_PREC_SPLIT) return MCG_ERR_UNSUPPORTED;
-    g.tile = c->tile % 100 - 10 * g.dense; g.bk = ((c->tile / 100) % 10) * 32; g.ksplit = 1 << (c->tile / 1000);
+    g.tile = lv ? (c->tile % 100 == 40 ? 10 : c->tile % 100 == 28 ? 8 : 7) : c->tile % 100 - 10 * g.dense;
+    g.bk = ((c->tile / 100) % 10) * 32; g.ksplit = 1 << (c->tile / 1000);
     g.lgHo = ilog2_exact(g.Ho); g.lgWo = ilog2_exact(g.Wo);
     g.lgCi = ilog2_exact(g.Ci); g.lgCo = ilog2_exact(g.Co);
     if (g.N <= 0 || g.Ci <= 0 || g.Co <= 0) return MCG_ERR_BAD_ARG;
@@ -3276,6 +3451,56 @@ int launch_fprop_v2(const Geom& g, const float* x, const float* w, const float* 
     });
     }
 }
+// The dense split forward with position-major rows (FpropP's LV; g: the split geometry).  g.ksplit == 1: one block per tile.
+// Otherwise every row tile is cut into blocks of at most L of ITS live K-steps (the tap mask of its positions: live_taps_of_tile,
+// the function the kernel uses), L the smallest length (>= 4 triples, as split K) at which the launch has no more than
+// (g.ksplit / 2) x CUs x blocks-per-CU blocks -- one round (+ 1000) or two rounds (+ 2000) of blocks whose longest member runs L
+// steps, instead of one round that lasts as long as an interior tile's whole K range.  The table is a function of the geometry alone
+// and travels in the kernel argument (LIVE_MAX_TILES row tiles; more: MCG_ERR_UNSUPPORTED, such launches have whole rounds anyway),
+// part-major (LiveRows).  A tile left whole stores its result; y is cleared for the others.
+constexpr int LIVE_CUS = 256;
+template <int BM, int BN, int STAGES, int LV>
+int launch_fprop_live(const Geom& g, const float* x, const float* w, const float* bias, float* y, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
+    using Pol = FpropP<BM, BN, 64, 8, true, NT2, true, true, LV>;
+    const long long M = (long long)g.N * g.To * g.Ho * g.Wo;
+    const int nto = g.N * g.To;
+    if (nto < 2 || M * nto >= (1ll << 32)) return MCG_ERR_UNSUPPORTED;       // (the range of the kernel's division by N * To)
+    return with_epi<LV == 2 ? 1 : 2>(e, [&](auto epi) -> int {
+        Pol p; dim3 grid;
+        p.g = g; p.e = e; p.x = x; p.w = w; p.bias = bias; p.y = y;
+        p.M = (int)M; p.K = g.taps * g.Ci; p.kchunk = p.K;
+        p.nto = nto; p.magic_nto = (u32)((1ull << 32) / (unsigned)nto) + 1u;
+        p.chunked = fprop_ksplit(g, e) > 1;
+        const int tiles = (p.M + BM - 1) / BM, gy = (g.Co + BN - 1) / BN;
+        int blocks = tiles;
+        if (p.chunked) {
+            if (tiles > LIVE_MAX_TILES) return MCG_ERR_UNSUPPORTED;
+            int cnt[LIVE_MAX_TILES], longest = 0;
+            for (int t = 0; t < tiles; ++t) {
+                const int last = ((t + 1) * BM < p.M ? (t + 1) * BM : p.M) - 1;
+                const u32 live = LV == 2 ? 0xffffu : live_taps_of_tile(g.Ho, g.Wo, g.lgWo, t * BM / nto, last / nto);
+                cnt[t] = __builtin_popcount(live) * g.kt * g.Ci / Pol::KADV;
+                longest = cnt[t] > longest ? cnt[t] : longest;
+            }
+            int target = (g.ksplit / 2) * LIVE_CUS * (v2_lds(BM, BN, STAGES) <= 80 * 1024 ? 2 : 1) / gy;      // blocks along x
+            target = target > LIVE_MAX_BLOCKS ? LIVE_MAX_BLOCKS : target;
+            auto blocks_at = [&](int L) { int b = 0; for (int t = 0; t < tiles; ++t) b += (cnt[t] + L - 1) / L; return b; };
+            int L = (longest + LIVE_MAX_PARTS - 1) / LIVE_MAX_PARTS;
+            L = L < 4 ? 4 : L;
+            while (L < longest && blocks_at(L) > target) ++L;
+            blocks = 0;
+            for (int j = 0; j < LIVE_MAX_PARTS; ++j)
+                for (int t = 0; t < tiles; ++t) {
+                    const int parts = (cnt[t] + L - 1) / L;
+                    if (j < parts) p.blk[blocks++] = (unsigned short)(t | j << 8 | (parts - 1) << 12);
+                }
+            if (clear_output(y, M * g.Co, s) != MCG_OK) return MCG_ERR_LAUNCH;
+        }
+        if (ep) { ep->n_slots = tiles; ep->slot_stride = e.slot_stride; }
+        grid = dim3(blocks, gy, 1);
+        return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, epi, 2>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
+    });
+}
 template <int BM, int BN, int STAGES, int PM, int SPLIT = 0>
 int launch_dgrad_v2(const Geom& g, const float* y, const float* w, const float* bias, float* x, int act, int acc, const Epi& e, mcg_conv_epilogue* ep, hipStream_t s) {
     // not instantiated: 256x256 on split operands (three planes of fragments spill); 256x64 with two buffers on fp32 ones
@@ -3302,6 +3527,33 @@ int launch_wgrad_v2(const Geom& g, const float* x, const float* y, float* dw, hi
     plan_wgrad<BM, BN>(p, grid, g, x, y, dw, BK, 512, SPLIT == 2 ? 8 : SPLIT ? 32 : 8);
     return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
     }
+}
+
+// The split weight gradient with a position-major pixel axis (WgradP's PJ).  Refused unless N To is a multiple of the K advance in
+// pixels (16 padded, 64 dense).  The number of pixel splits is plan_wgrad's, at most the live advances of the column tile that
+// has fewest; every block takes an equal share (to within one) of ITS column tile's live advances (WgradP::init).
+template <int BM, int BN, int STAGES, int SPLIT>
+int launch_wgrad_live(const Geom& g, const float* x, const float* y, float* dw, hipStream_t s) {
+    using Pol = WgradP<BM, BN, 64, 8, NT2, true, true, 8, SPLIT == 2, true>;
+    const int nto = g.N * g.To;
+    const long long M = (long long)nto * g.Ho * g.Wo;
+    if (nto % Pol::ADV || M * nto >= (1ll << 32)) return MCG_ERR_UNSUPPORTED;
+    Pol p; dim3 grid;
+    plan_wgrad<BM, BN>(p, grid, g, x, y, dw, Pol::ADV, 512, SPLIT == 2 ? 8 : 32);
+    p.nto = nto; p.magic_nto = (u32)((1ull << 32) / (unsigned)nto) + 1u;
+    int fewest = 1 << 30;
+    for (int by = 0; by < (int)grid.y; ++by) {
+        const int kf1 = ((by + 1) * BN < p.Kf ? (by + 1) * BN : p.Kf) - 1;
+        u32 tmask = 0;
+        for (int t = by * BN / g.Ci; t <= kf1 / g.Ci; ++t) tmask |= 1u << (t & 15);
+        int c = 0;
+        for (int pos = 0; pos < g.Ho * g.Wo; ++pos) c += (live_taps(g.Ho, g.Wo, g.lgWo, pos) & tmask) ? 1 : 0;
+        c *= nto / Pol::ADV;
+        fewest = c < fewest ? c : fewest;
+    }
+    if (fewest < 1) return MCG_ERR_UNSUPPORTED;
+    if ((int)grid.z > fewest) grid.z = fewest;
+    return launch<gemm_bf16_v2_kernel<Pol, BM, BN, STAGES, 0, SPLIT>>(grid, dim3(NT2), v2_lds(BM, BN, STAGES), s, p);
 }
 
 // operand form of an LDS-DMA launch -> (PM, SPLIT) of the launcher `fn`
@@ -3461,6 +3713,10 @@ int make_epi(const mcg_conv_epilogue* ep, const Geom& g, int pass, Epi& e) {
 //   9      -                              dgrad_patch_kernel                         -
 //   10     LDS-DMA 128x128/2              128x128/2 (Ci = 64: 256x64/2, not fp32)    128x128/2
 //   17, 20 split operands only: as 7, 10 with the dense LDS form (SPLIT = 2; 64 | Ci)     (64 | Co)                  (any split wgrad)
+//   27, 40 split operands only: as 17, 20 with position-major rows, padding taps skipped   -                          27: as 17, position-major pixels
+//   37     as 27, nothing skipped (+ 1000 / + 2000 on 27 / 40: tiles cut by live K-steps)  -                          -
+//   28     -                                                                               -                          split: padded 256x256/2, position-major pixels
+//          (weight gradient, 27 / 28: N To a multiple of 64 / 16 pixels; + 1000 / + 2000 as for 7 / 8)
 // dgrad, t = 0, Ci = 4 outside dgrad_c4_mfma_kernel's reach: dgrad_c4_kernel (VALU).  The LDS-DMA kernels take fp32,
 // bf16-stored or split operands (one dispatch on the form, MCG_V2_FORMS), tile 9 bf16-stored or split ones.
 
@@ -3482,7 +3738,7 @@ int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, cons
     int t = g.tile;
     if (split) {
         if ((t != 0 && t != 7 && t != 8 && t != 10) || !split_ok(g, SPLIT_CI) || e.out16) return MCG_ERR_UNSUPPORTED;
-        if (g.dense && !dense_ok(g, SPLIT_CI)) return MCG_ERR_UNSUPPORTED;
+        if (g.dense && (g.dense == 2 || !dense_ok(g, SPLIT_CI))) return MCG_ERR_UNSUPPORTED;       // (28: the weight gradient's code)
         if (!t) t = 7;
     } else if ((t == 0 || t == 6) && c4_fprop_ok(g, e)) {          // the 3-channel clip padded to 4: weight-stationary kernel
         if (ep) { ep->n_slots = 0; ep->slot_stride = e.slot_stride; }
@@ -3494,6 +3750,11 @@ int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, cons
         if (!split && !v2_ok(g, g.Ci)) return MCG_ERR_UNSUPPORTED;
         const Geom h = split ? split_geom(g, SPLIT_CI) : g;
         const int form = v2_form(g);
+        if (g.dense > 1) {                                         // position-major rows (27 / 40; 37: tile 7 only)
+            if (g.dense == 5) return t == 7 ? launch_fprop_live<256, 128, 3, 2>(h, x, w, bias, y, e, ep, s) : MCG_ERR_UNSUPPORTED;
+            if (t == 10) return launch_fprop_live<128, 128, 2, 1>(h, x, w, bias, y, e, ep, s);
+            return launch_fprop_live<256, 128, 3, 1>(h, x, w, bias, y, e, ep, s);
+        }
         if (t == 10) return MCG_V2_FORMS(launch_fprop_v2, 128, 128, 2, form, h, x, w, bias, y, e, ep, s);     // two blocks per CU
         if (t == 8 && (!split || g.Co >= 256)) return MCG_V2_FORMS(launch_fprop_v2, 256, 256, 2, form, h, x, w, bias, y, e, ep, s);
         return MCG_V2_FORMS(launch_fprop_v2, 256, 128, 3, form, h, x, w, bias, y, e, ep, s);
@@ -3579,7 +3840,7 @@ int conv_dgrad_impl(const mcg_conv_geom* c, const float* y, const float* w, cons
     int t = g.tile;
     if (split) {
         if ((t != 0 && t != 7 && t != 8 && t != 9 && t != 10) || !split_ok(g, SPLIT_CO) || e.out16) return MCG_ERR_UNSUPPORTED;
-        if (g.dense && !dense_ok(g, SPLIT_CO)) return MCG_ERR_UNSUPPORTED;
+        if (g.dense && (g.dense > 1 || !dense_ok(g, SPLIT_CO))) return MCG_ERR_UNSUPPORTED;       // (position-major rows: forward only)
         if (!t) t = 7;
     } else {
         if ((t == 0 || t == 6) && g.prec != MCG_PREC_BF16_STORE && c4_dgrad_mfma_ok(g, e, bias, act, accumulate)) {
@@ -3647,6 +3908,13 @@ extern "C" int mcg_conv_wgrad(const mcg_conv_geom* c, const float* x, const floa
     int t = g.tile;
     if (split) {
         if ((t != 0 && t != 7 && t != 8 && t != 10) || !split_ok(g, SPLIT_PIX)) return MCG_ERR_UNSUPPORTED;
+        if (g.dense > 1) {                                       // position-major pixel axis: 27 = 128x256/3 dense, 28 = 256x256/2 padded
+            if (g.Co < 128 || (g.Co & 63) || g.Ci < 64 || (g.Ci & (g.Ci - 1))) return MCG_ERR_UNSUPPORTED;
+            const Geom h = split_geom(g, SPLIT_PIX);
+            if (g.dense == 2) return g.Co >= 256 ? launch_wgrad_live<256, 256, 2, 1>(h, x, y, dw, s) : MCG_ERR_UNSUPPORTED;
+            if (g.dense == 3 && t == 7) return launch_wgrad_live<128, 256, 3, 2>(h, x, y, dw, s);
+            return MCG_ERR_UNSUPPORTED;                          // (40, 37: forward only)
+        }
         if (!t) t = 7;
     } else {
         // the 3-channel clip padded to 4: patch-in-LDS kernel.  Only on request (tile code 6): measured on the MI355X it equals the

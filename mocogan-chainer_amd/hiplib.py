@@ -319,6 +319,10 @@ WGRAD_SPLIT_CANDIDATES = (2007, 2008, 2010, 1010)      # LDS-DMA weight gradient
 V2_CANDIDATES = (7, 8, 10)                              # gemm_bf16_v2_kernel (bf16-stored / split / fp32 operands): 256x128 / 256x256 (wgrad 128x256 / 256x256) one block per CU; 10 = 128x128, two blocks per CU
 DENSE_CANDIDATES = (17, 20)                             # MCG_PREC_SPLIT only: tiles 7 / 10 with the dense LDS form (no padding-plane slots; the library
                                                         # refuses it where a triple of K-steps would straddle a tap: channels along the sum not a multiple of 64)
+LIVE_CANDIDATES = (27, 40, 1027, 2027, 1040, 2040)       # MCG_PREC_SPLIT forward only: 17 / 20 with position-major rows -- K-steps of filter taps that read zero padding for every row
+                                                        # of a tile are skipped; + 1000 / + 2000: the tiles cut into blocks of equal LIVE work, one / two per resident slot (no epilogue)
+LIVE_WGRAD_CANDIDATES = (27, 28, 1027, 2027, 1028, 2028)     # MCG_PREC_SPLIT weight gradient: 128x256/3 dense / 256x256/2 padded with a position-major pixel axis -- advances whose position
+                                                        # reads only padding for the column tile's taps are skipped; needs N * To a multiple of 64 / 16 (the library refuses otherwise)
 _autotune = False
 _tile_cache = {}
 
@@ -329,6 +333,10 @@ _PRETUNED = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_tile
 # spread (tools/ab_dense_split.py, profiles/dense_split_notes.md).  A list of its own, applied by set_autotune(True): the main
 # table and use_pretuned_table() stay the padded reference that the production-batch parity test pins against float64.
 _PRETUNED_DENSE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'dense_tiles_mi355x.json')
+# ... and the forward launches among them which take position-major rows and live K-steps (LIVE_CANDIDATES), measured the same way
+# (tools/ab_live_steps.py, profiles/live_steps_notes.md); applied on top of the dense list where a training step is built with the
+# tuner on (step.TrainStep -> use_live_list): set_autotune()'s table stays the shipped one with the dense entries
+_PRETUNED_LIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'live_tiles_mi355x.json')
 
 
 def set_autotune(on, use_pretuned=True):
@@ -379,6 +387,37 @@ def use_dense_list():
         for k, v in json.load(f):
             if _tile_cache.get(tuple(k), -1) == shipped.get(tuple(k)):
                 _tile_cache[tuple(k)] = int(v)
+
+
+def _read_list(path):
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return {tuple(k): int(v) for k, v in json.load(f)}
+
+
+def live_list(path=None):
+    """{key: code} of live_tiles_mi355x.json (or of `path`), checked: forward / weight-gradient launches of the split form, codes of LIVE_CANDIDATES / LIVE_WGRAD_CANDIDATES"""
+    entries = _read_list(path or _PRETUNED_LIVE)
+    for k, v in entries.items():
+        if k[9] != PREC_SPLIT or not ((k[0] == 'fprop' and v in LIVE_CANDIDATES) or (k[0] == 'wgrad' and v in LIVE_WGRAD_CANDIDATES)):
+            raise ValueError("not a live-steps entry: %r -> %r" % (k, v))
+    return entries
+
+
+def use_live_list(path=None):
+    """Move the launches of live_tiles_mi355x.json to their position-major codes -- where the table still holds the shipped code or
+    the dense list's code for them.  Called by step.TrainStep when the tuner is on (bench.py, train.py); set_autotune() does not;
+    MCG_LIVE_STEPS=0 leaves the table as it is (A/B timing).  Returns the number of launches moved."""
+    if not os.path.exists(_PRETUNED) or os.environ.get('MCG_LIVE_STEPS', '1') == '0':
+        return 0
+    shipped, dense = _read_list(_PRETUNED), _read_list(_PRETUNED_DENSE)
+    moved = 0
+    for k, v in live_list(path).items():
+        if k in shipped and _tile_cache.get(k, -1) in (shipped[k], dense.get(k, shipped[k])):
+            _tile_cache[k] = v
+            moved += 1
+    return moved
 
 
 def reset_tuning():
@@ -539,6 +578,10 @@ def _tuned(kind, g, extra, out_side, run_on):
             cands = V2_CANDIDATES + DENSE_CANDIDATES
             if kind in ("fprop", "dgrad") and out_elems <= (1 << 25):
                 cands = cands + (1007, 2007, 1010, 2010, 1017, 2017, 1020, 2020)
+            if kind == "fprop":
+                cands = cands + LIVE_CANDIDATES
+            if kind == "wgrad":
+                cands = cands + LIVE_WGRAD_CANDIDATES
             if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
                 # few (Co, tap x Ci) tiles -- the 2-D layers: many pixel splits then add onto the same small dw with float
                 # atomics; + 2000 halves / + 1000 doubles the number of splits (round 6)

@@ -171,6 +171,11 @@ class TrainStep:
             assert precision in ('f32', 'bf16', 'f32x3')
             for net in (gen, dis_i, dis_v):
                 net.set_precision(precision)
+        if hl.autotune_on():
+            # the training step's forward launches that take position-major rows / live K-steps (hiplib.use_live_list: only where the
+            # table still holds the shipped or the dense code; MCG_LIVE_STEPS=0 leaves it).  set_autotune() itself loads the shipped
+            # table and the dense list, nothing else.
+            hl.use_live_list()
         # ema_decay: None = off (nothing allocated, the launches of before); D in [0, 1): the generator keeps an exponential moving
         # average of its parameters and running statistics (gen.ema; ema_rate is the schedule), advanced by its Adam launch
         if ema_decay is not None:
