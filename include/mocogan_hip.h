@@ -130,7 +130,8 @@ typedef struct mcg_conv_geom {
  * 8 = the sampling path (mcg_bn_fold_deconv, mcg_clip_to_u8, MCG_ACT_RELU in mcg_conv_dgrad / mcg_conv_dgrad_ex; no argument list changed);
  *     still 8 with the averaged generator (mcg_adam_wd_ema, mcg_ema_multi added; no argument list changed)
  *     and with the differentiable augmentation (mcg_augment_* added; no argument list changed)
- *     and with the sliced Wasserstein distance (mcg_swd_*, mcg_sort_* added; no argument list changed). */
+ *     and with the sliced Wasserstein distance (mcg_swd_*, mcg_sort_* added; no argument list changed)
+ *     and with the gradient statistics (mcg_grad_stats*, mcg_adam_wd_ctl added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -446,6 +447,44 @@ int mcg_adam_wd_ema(int64_t n, float* p, const float* g, float* m, float* v, dou
  * MCG_ERR_BAD_ARG: a null pointer, nseg <= 0 or > 32, an n <= 0, ema_rate outside (0, 1]. */
 typedef struct mcg_ema_seg { const float* src; float* dst; int64_t n; } mcg_ema_seg;
 int mcg_ema_multi(int nseg, const mcg_ema_seg* segs, float ema_rate, void* stream);
+
+/* ---- gradient norms on the device: telemetry, norm clipping (chainer.optimizer.GradientClipping), non-finite skip ----------
+ * mcg_grad_stats reduces nseg <= 32 segments [offset, offset + n) (elements) of the flat gradient g and leaves
+ *   stats [(nseg + 1)][4] doubles, a row per segment: { sum of g^2, largest |g|, number of non-finite elements, 0 }.  Non-finite
+ *         elements are counted and kept out of the sum and the maximum (0 when no element is finite).  Row nseg is the total: the
+ *         sums added in segment order, the largest maximum, the counts added;
+ *   ctl   [8] floats, from   norm = grad_scale * sqrt(total sum),   rate = min(1, threshold / norm) (1 when norm == 0),
+ *         bad = (total count > 0), all three in double:
+ *         ctl[0] = (float)(grad_scale * rate), (float)grad_scale when bad     the gradient scale mcg_adam_wd_ctl applies
+ *         ctl[1] = bad ? 1 : 0                                                mcg_adam_wd_ctl then writes nothing
+ *         ctl[2] = (float)rate     ctl[3] = (float)norm
+ *         ctl[4] = max(ctl[4], ctl[3]) when !bad and ctl[3] is finite         a running peak: the reader zeroes it
+ *         ctl[5] += bad                                                       skipped updates, exact to 2^24; persists
+ *         ctl[6], ctl[7]: not touched.
+ * grad_scale is 1 / world under data parallelism (g holds the SUM over the ranks: the norm is the mean gradient's);
+ * threshold = +inf never clips and still skips.  `segs` is a HOST array.  g needs 4-byte alignment; a segment that starts on a
+ * 16-byte boundary is read with 16-byte loads throughout, any other after a scalar head.
+ * Two launches -- per-block partial sums into `workspace` (mcg_grad_stats_workspace_bytes(nseg) = 32 bytes for each of the at
+ * most MAX_PART = 512 blocks), then one block that adds them -- no float atomics, no hand-off between workgroups inside a launch.
+ * Squares are formed and added in double: per thread, over the block in a fixed tree, over a segment's blocks in block order.
+ * Two calls on the same input agree bit for bit.  Blocks: with S = mcg_grad_stats_span() (the elements a block covers per loop
+ * trip) and N the sum of all n, segment s gets  min(ceil(n_s / S), 1 + floor((512 - nseg) * n_s / N))  blocks, its trips
+ * dealt to them round-robin.
+ * MCG_ERR_BAD_ARG: a null pointer, nseg outside [1, 32], an n <= 0, an offset < 0, grad_scale not finite and positive,
+ * threshold NaN or <= 0. */
+typedef struct mcg_stat_seg { int64_t offset; int64_t n; } mcg_stat_seg;
+int64_t mcg_grad_stats_workspace_bytes(int nseg);
+int mcg_grad_stats_span(void);
+int mcg_grad_stats(int nseg, const mcg_stat_seg* segs, const float* g, double grad_scale, double threshold,
+                   double* stats, float* ctl, void* workspace, void* stream);
+/* mcg_adam_wd_ema with the gradient scale taken from DEVICE memory: grad_scale = ctl[0], read once per thread, and a launch that
+ * finds ctl[1] != 0 writes nothing -- p, m, v, p_bf16 and ema keep their bits (the host's step counter has advanced all the same:
+ * nothing here waits for the device).  ema may be NULL (ema_rate is then ignored): mcg_adam_wd.  Same arithmetic, same 16-byte /
+ * scalar forms by the same alignment rule: with ctl[1] == 0 the outputs are bit for bit those of mcg_adam_wd / mcg_adam_wd_ema
+ * called with grad_scale = ctl[0].  MCG_ERR_BAD_ARG: as mcg_adam_wd_ema (ema NULL allowed), a null ctl. */
+int mcg_adam_wd_ctl(int64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta1,
+                    double beta2, double eps, double wd, const float* ctl, uint16_t* p_bf16, float* ema,
+                    float ema_rate, void* stream);
 
 /* out[i] = sigma * N(0,1), the same Philox stream mcg_bn_act_fwd / mcg_pack_clip draw from. */
 int mcg_randn(int64_t n, float sigma, uint64_t seed, uint64_t stream_id, float* out, void* stream);

@@ -1133,10 +1133,16 @@ __device__ __forceinline__ float ema_elem(float e, float x, float r, bool take_x
 // EMA: the exponential moving average `ema` of the parameters follows in the same pass (the fresh parameter is in a register).
 // V = 4: 16-byte accesses, for pointers that are all 16-byte aligned (p16: 8-byte); the n % 4 last elements are done one by one
 // by the first threads of block 0.  V = 1: any 4-byte aligned pointers.
-template <bool EMA, int V>
+// CTL (mcg_adam_wd_ctl): the gradient scale is ctl[0] of device memory, read once per thread -- what mcg_grad_stats' finalize launch
+// left there (grad_scale x clipping rate) -- and a non-zero ctl[1] (a non-finite gradient) ends the launch before anything is written.
+template <bool EMA, int V, bool CTL = false>
 __global__ __launch_bounds__(NT) void adam_wd_kernel(long long n, float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ v, AdamK k, __bf16* __restrict__ p16,
-                                                     float* __restrict__ ema, float r) {
+                                                     float* __restrict__ ema, float r, const float* __restrict__ ctl = nullptr) {
+    if constexpr (CTL) {
+        if (ctl[1] != 0.0f) return;               // (uniform over the whole grid: p, m, v, p16 and ema keep their bits)
+        k.gscale = ctl[0];
+    }
     const bool take_x = r == 1.0f;
     const long long stride = (long long)gridDim.x * NT, first = (long long)blockIdx.x * NT + threadIdx.x;
     auto one = [&](long long i) {
@@ -1187,6 +1193,149 @@ __global__ __launch_bounds__(NT) void ema_multi_kernel(EmaSegs sg, float r) {
     const bool take_x = r == 1.0f;
     for (long long i = (long long)((int)blockIdx.x - b0) * NT + threadIdx.x; i < n; i += (long long)nb * NT)
         dst[i] = ema_elem(dst[i], src[i], r, take_x);
+}
+
+// ------------------------------------------------------------------------------------------
+// mcg_grad_stats: sum of squares, largest |g| and non-finite count of up to 32 segments of a flat gradient, and from the total the
+// control block the Adam launch reads (mcg_adam_wd_ctl).  Two launches, no atomics, no hand-off between workgroups inside a launch:
+// every sum has ONE order, so two calls on the same input agree bit for bit.
+//   partial: a block belongs to one segment (found in the prefix sums of the block counts, as split_planes_multi_kernel finds it) and walks it in trips of STAT_SPAN
+//            elements, its trips strided by the segment's block count.  A thread issues its STAT_LOADS 16-byte loads of a trip before it
+//            uses the first (the note at col_partial_kernel: with at most MAX_PART blocks on the chip one dependent load per
+//            iteration leaves HBM idle).  Squares are formed and added in double (the product of two fp32 values is exact there):
+//            per thread, then over the block through LDS in a fixed tree -> workspace[block][4].
+//   final:   one block; thread s adds segment s's partials in block order, thread 0 the segments in segment order -> stats, ctl.
+// A segment start that is not 16-byte aligned gets a scalar head (up to 3 elements), n % 4 leftovers a scalar tail: both in the
+// segment's first block.  Non-finite elements are counted and kept OUT of the sum and the maximum, so the norm stays that of the
+// finite part and says how large the rest of the gradient was.
+// ------------------------------------------------------------------------------------------
+constexpr int MAX_STAT_SEGS = 32, STAT_LOADS = 4, STAT_SPAN = NT * 4 * STAT_LOADS;
+struct StatSegs { long long off[MAX_STAT_SEGS]; long long n[MAX_STAT_SEGS]; int blk_end[MAX_STAT_SEGS]; int nseg; };
+
+struct StatAcc {
+    double ss; float mx; unsigned int bad;
+    __device__ __forceinline__ void add(float x) {
+        const bool fin = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
+        const double d = fin ? (double)x : 0.0;
+        ss += d * d;
+        mx = fmaxf(mx, fin ? fabsf(x) : 0.0f);
+        bad += fin ? 0u : 1u;
+    }
+};
+
+__global__ __launch_bounds__(NT) void grad_stats_partial_kernel(StatSegs sg, const float* __restrict__ g, double* __restrict__ part) {
+    int s = 0, hi = sg.nseg - 1;
+    while (s < hi) {                                                                    // (block-uniform; by halves: the small tensors come last)
+        const int mid = (s + hi) >> 1;
+        if ((int)blockIdx.x >= sg.blk_end[mid]) s = mid + 1; else hi = mid;
+    }
+    const int b0 = s ? sg.blk_end[s - 1] : 0, nb = sg.blk_end[s] - b0, b = (int)blockIdx.x - b0;
+    const float* __restrict__ x = g + sg.off[s];
+    const long long n = sg.n[s];
+    const int tid = threadIdx.x;
+    long long head = (long long)((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2;    // elements in front of the first 16-byte boundary
+    if (head > n) head = n;
+    const long long nq = (n - head) >> 2, tail0 = head + (nq << 2);
+    StatAcc a = {0.0, 0.0f, 0u};
+    if (b == 0) {
+        if (tid < head) a.add(x[tid]);
+        if (tid >= 4 && tail0 + (tid - 4) < n) a.add(x[tail0 + (tid - 4)]);             // (threads 4..6)
+    }
+    const f32x4* __restrict__ xq = reinterpret_cast<const f32x4*>(x + head);
+    constexpr long long TRIP = STAT_SPAN / 4;                                           // 16-byte pieces of a trip
+    for (long long q0 = (long long)b * TRIP; q0 < nq; q0 += (long long)nb * TRIP) {
+        f32x4 v[STAT_LOADS];
+#pragma unroll
+        for (int j = 0; j < STAT_LOADS; ++j) {
+            const long long q = q0 + j * NT + tid;
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            v[j] = q < nq ? xq[q] : zero;
+        }
+#pragma unroll
+        for (int j = 0; j < STAT_LOADS; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a.add(v[j][e]);
+    }
+    __shared__ double sh_ss[NT];
+    __shared__ float sh_mx[NT];
+    __shared__ unsigned int sh_bad[NT];
+    sh_ss[tid] = a.ss; sh_mx[tid] = a.mx; sh_bad[tid] = a.bad;
+    __syncthreads();
+    for (int w = NT / 2; w > 0; w >>= 1) {                                              // the fixed tree: t <- t + (t + w)
+        if (tid < w) {
+            sh_ss[tid] += sh_ss[tid + w];
+            sh_mx[tid] = fmaxf(sh_mx[tid], sh_mx[tid + w]);
+            sh_bad[tid] += sh_bad[tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double* o = part + 4LL * blockIdx.x;
+        o[0] = sh_ss[0]; o[1] = (double)sh_mx[0]; o[2] = (double)sh_bad[0]; o[3] = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(NT) void grad_stats_final_kernel(StatSegs sg, const double* __restrict__ part, double gscale, double threshold,
+                                                              double* __restrict__ stats, float* __restrict__ ctl) {
+    __shared__ double sh[3][MAX_PART];
+    __shared__ double row[MAX_STAT_SEGS][3];
+    const int tid = threadIdx.x, nblk = sg.blk_end[sg.nseg - 1];
+    for (int i = tid; i < nblk; i += NT) {
+        const double* q = part + 4LL * i;
+        sh[0][i] = q[0]; sh[1][i] = q[1]; sh[2][i] = q[2];
+    }
+    __syncthreads();
+    // the sums in block order by threads 0.. of the first wave, maxima and counts (any order gives the same) by the second wave beside
+    // them; eight LDS reads are in flight before the first is added (one read per dependent add: 20 us for G's 330 partials)
+    const int seg = tid & 63, role = tid >> 6;
+    if (seg < sg.nseg && role < 2) {
+        const int b0 = seg ? sg.blk_end[seg - 1] : 0, b1 = sg.blk_end[seg];
+        double* o = stats + 4LL * seg;
+        int b = b0;
+        if (role == 0) {
+            double ss = 0.0;
+            for (; b + 8 <= b1; b += 8) {
+                double t[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) t[j] = sh[0][b + j];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss += t[j];
+            }
+            for (; b < b1; ++b) ss += sh[0][b];
+            row[seg][0] = ss;
+            o[0] = ss; o[3] = 0.0;
+        } else {
+            double mx = 0.0, bad = 0.0;
+            for (; b + 4 <= b1; b += 4) {
+                double t[4], c[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { t[j] = sh[1][b + j]; c[j] = sh[2][b + j]; }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { mx = fmax(mx, t[j]); bad += c[j]; }
+            }
+            for (; b < b1; ++b) { mx = fmax(mx, sh[1][b]); bad += sh[2][b]; }
+            row[seg][1] = mx; row[seg][2] = bad;
+            o[1] = mx; o[2] = bad;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double ss = 0.0, mx = 0.0, cnt = 0.0;
+        for (int s = 0; s < sg.nseg; ++s) { ss += row[s][0]; mx = fmax(mx, row[s][1]); cnt += row[s][2]; }       // segment order
+        double* o = stats + 4LL * sg.nseg;
+        o[0] = ss; o[1] = mx; o[2] = cnt; o[3] = 0.0;
+        const bool bad = cnt > 0.0;
+        const double norm = gscale * sqrt(ss);
+        const double rate = norm == 0.0 ? 1.0 : fmin(1.0, threshold / norm);
+        const float fnorm = (float)norm;
+        ctl[0] = bad ? (float)gscale : (float)(gscale * rate);
+        ctl[1] = bad ? 1.0f : 0.0f;
+        ctl[2] = (float)rate;
+        ctl[3] = fnorm;
+        const bool fin = (__float_as_uint(fnorm) & 0x7f800000u) != 0x7f800000u;
+        if (!bad && fin) ctl[4] = fmaxf(ctl[4], fnorm);                                  // peak over the finite norms of clean calls
+        if (bad) ctl[5] += 1.0f;                                                        // skipped updates (exact to 2^24)
+    }
 }
 
 __global__ __launch_bounds__(NT) void randn_kernel(long long n, float sigma, uint64_t seed, uint64_t stream_id, float* __restrict__ out) {
@@ -1840,6 +1989,54 @@ extern "C" int mcg_ema_multi(int nseg, const mcg_ema_seg* segs, float ema_rate, 
     }
     sg.nseg = nseg;
     hipLaunchKernelGGL(ema_multi_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, sg, ema_rate);
+    return launch_status();
+}
+
+extern "C" int64_t mcg_grad_stats_workspace_bytes(int nseg) {
+    return nseg >= 1 && nseg <= MAX_STAT_SEGS ? (int64_t)MAX_PART * 4 * (int64_t)sizeof(double) : 0;
+}
+
+extern "C" int mcg_grad_stats_span(void) { return STAT_SPAN; }
+
+extern "C" int mcg_grad_stats(int nseg, const mcg_stat_seg* segs, const float* g, double grad_scale, double threshold, double* stats,
+                              float* ctl, void* workspace, void* stream) {
+    if (!segs || !g || !stats || !ctl || !workspace || nseg < 1 || nseg > MAX_STAT_SEGS) return MCG_ERR_BAD_ARG;
+    if (!(grad_scale > 0.0) || !__builtin_isfinite(grad_scale) || !(threshold > 0.0)) return MCG_ERR_BAD_ARG;      // (NaN fails both; threshold +inf: never clips)
+    StatSegs sg;
+    unsigned __int128 total = 0;
+    for (int s = 0; s < nseg; ++s) {
+        if (segs[s].n <= 0 || segs[s].offset < 0) return MCG_ERR_BAD_ARG;
+        total += (unsigned __int128)segs[s].n;
+    }
+    // the apportioning rule (include/mocogan_hip.h): one block per segment, the other MAX_PART - nseg by size, never more than trips
+    int blocks = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const long long trips = (long long)((segs[s].n + STAT_SPAN - 1) / STAT_SPAN);
+        long long nb = 1 + (long long)((unsigned __int128)(MAX_PART - nseg) * (unsigned __int128)segs[s].n / total);
+        if (nb > trips) nb = trips;
+        blocks += (int)nb;
+        sg.off[s] = segs[s].offset; sg.n[s] = segs[s].n; sg.blk_end[s] = blocks;
+    }
+    sg.nseg = nseg;
+    hipLaunchKernelGGL(grad_stats_partial_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, sg, g, (double*)workspace);
+    hipLaunchKernelGGL(grad_stats_final_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, sg, (const double*)workspace, grad_scale, threshold,
+                       stats, ctl);
+    return launch_status();
+}
+
+extern "C" int mcg_adam_wd_ctl(int64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta1, double beta2, double eps,
+                               double wd, const float* ctl, uint16_t* p_bf16, float* ema, float ema_rate, void* stream) {
+    if (!p || !g || !m || !v || !ctl || n <= 0) return MCG_ERR_BAD_ARG;
+    if (ema && (!ema_rate_ok(ema_rate) || overlaps(ema, p, n) || overlaps(ema, g, n) || overlaps(ema, m, n) || overlaps(ema, v, n))) return MCG_ERR_BAD_ARG;
+    const AdamK k = adam_consts(lr_t, beta1, beta2, eps, wd, 1.0);                        // (gscale: ctl[0], read by the kernel)
+    const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | ((uintptr_t)p_bf16 << 1);
+    const bool wide = (bits & 15) == 0 && n >= 4;                                        // mcg_adam_wd_ema's rule
+    const dim3 grid(ew_grid(wide ? n / 4 : n));
+    auto launch = [&](auto kern, float r) {
+        hipLaunchKernelGGL(kern, grid, dim3(NT), 0, (hipStream_t)stream, (long long)n, p, g, m, v, k, (__bf16*)p_bf16, ema, r, ctl);
+    };
+    if (ema) { if (wide) launch(adam_wd_kernel<true, 4, true>, ema_rate); else launch(adam_wd_kernel<true, 1, true>, ema_rate); }
+    else     { if (wide) launch(adam_wd_kernel<false, 4, true>, 0.0f);    else launch(adam_wd_kernel<false, 1, true>, 0.0f); }
     return launch_status();
 }
 

@@ -90,6 +90,10 @@ SIGNATURES = {
     "mcg_adam_wd": (_I, [_I64, _P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _P, _P]),
     "mcg_adam_wd_ema": (_I, [_I64, _P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _P, _P, _F, _P]),
     "mcg_ema_multi": (_I, [_I, _P, _F, _P]),
+    "mcg_grad_stats_workspace_bytes": (_I64, [_I]),
+    "mcg_grad_stats_span": (_I, []),
+    "mcg_grad_stats": (_I, [_I, _P, _P, _D, _D, _P, _P, _P, _P]),
+    "mcg_adam_wd_ctl": (_I, [_I64, _P, _P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _P, _F, _P]),
     "mcg_randn": (_I, [_I64, _F, _U64, _U64, _P, _P]),
     "mcg_randint": (_I, [_I64, _I, _U64, _U64, _P, _P]),
     "mcg_split_planes": (_I, [_I64, _I64, _P, _P, _P]),
@@ -1039,6 +1043,54 @@ def ema_multi(pairs, rate):
         _p(_dense(src)), _p(_dense(dst))                           # (device, dtype and density are checked here)
         q.src, q.dst, q.n = src.data_ptr(), dst.data_ptr(), src.numel()
     _check(load().mcg_ema_multi(len(pairs), C.cast(segs, C.c_void_p), rate, _stream()), "mcg_ema_multi")
+
+
+class StatSeg(C.Structure):                                        # mcg_stat_seg
+    _fields_ = [("offset", C.c_int64), ("n", C.c_int64)]
+
+
+STAT_COLS, CTL_FLOATS, MAX_STAT_SEGS = 4, 8, 32                    # a stats row; the control block; segments of one call
+
+
+def grad_stats_span():
+    """the elements of a segment one block of mcg_grad_stats covers per loop trip (tests sit on its edges)"""
+    return int(load().mcg_grad_stats_span())
+
+
+def stat_segs(items):
+    """[(offset, n), ...] in elements of the flat gradient -> the host array mcg_grad_stats reads (built once, reused every call)"""
+    segs = (StatSeg * len(items))()
+    for q, (off, n) in zip(segs, items):
+        q.offset, q.n = int(off), int(n)
+    return segs
+
+
+def grad_stats_workspace(nseg, device):
+    """the partial-sum workspace of grad_stats for up to nseg segments (float64)"""
+    return torch.empty(max(int(load().mcg_grad_stats_workspace_bytes(nseg)) // 8, 1), dtype=torch.float64, device=device)
+
+
+def grad_stats(segs, g, grad_scale, threshold, stats, ctl, ws):
+    """segs: stat_segs(...) over the flat fp32 gradient g.  stats (float64)[(len(segs) + 1) * 4]: per segment and, last, in total
+    {sum of squares, max |g|, non-finite count, 0}; ctl (float32)[8]: the control block adam_wd_ctl reads (include/mocogan_hip.h:
+    mcg_grad_stats).  threshold: the L2 norm to clip to, math.inf for none.  Two launches on the current stream, no host sync."""
+    nseg = len(segs)
+    if stats.numel() < (nseg + 1) * STAT_COLS or ctl.numel() < CTL_FLOATS or ws.numel() * 8 < int(load().mcg_grad_stats_workspace_bytes(nseg)):
+        raise McgError("grad_stats: stats, ctl or workspace too small for %d segments" % nseg)
+    _check(load().mcg_grad_stats(nseg, C.cast(segs, C.c_void_p), _p(_dense(g)), grad_scale, threshold, _p(_dense(stats), torch.float64),
+                                 _p(_dense(ctl)), _p(ws, torch.float64), _stream()), "mcg_grad_stats")
+
+
+def adam_wd_ctl(p, g, m, v, lr_t, beta1, beta2, eps, wd, ctl, ema=None, ema_rate=0.0, p16=None):
+    """adam_wd / adam_wd_ema (ema given) with the gradient scale read from ctl[0] on the device; nothing is written when
+    ctl[1] != 0 (grad_stats found a non-finite gradient)"""
+    for name, t in (('g', g), ('m', m), ('v', v), ('ema', ema), ('p16', p16)):
+        if t is not None and t.numel() != p.numel():
+            raise McgError("%s has %d elements, p has %d" % (name, t.numel(), p.numel()))
+    if ctl.numel() < CTL_FLOATS:
+        raise McgError("ctl holds %d floats, %d are needed" % (ctl.numel(), CTL_FLOATS))
+    _check(load().mcg_adam_wd_ctl(p.numel(), _p(_dense(p)), _p(_dense(g)), _p(_dense(m)), _p(_dense(v)), lr_t, beta1, beta2, eps, wd,
+                                  _p(_dense(ctl)), _p(_dense(p16), torch.bfloat16), _p(_dense(ema)), ema_rate, _stream()), "mcg_adam_wd_ctl")
 
 
 def randint(out, modulus, seed, stream_id):

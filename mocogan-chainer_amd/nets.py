@@ -117,6 +117,38 @@ class EmaParams(FlatParams):
         return super().param16(name)
 
 
+class GradStats:
+    """What hl.grad_stats needs and leaves for one network, allocated once: a segment per named parameter of the flat gradient
+    (16 / 19 for the reference's networks; one call takes 32), the statistics rows, the control block the Adam launch reads and
+    the partial-sum workspace.  Nothing here is touched by the host between reads."""
+
+    def __init__(self, fp):
+        if len(fp.names) > hl.MAX_STAT_SEGS:
+            raise hl.McgError('gradient statistics: %d named parameters, one call takes %d' % (len(fp.names), hl.MAX_STAT_SEGS))
+        self.names = list(fp.names)
+        items = [(fp.offsets[k], int(np.prod(fp.shapes[k]))) for k in fp.names]
+        dev = fp.g.device
+        self.segs = hl.stat_segs(items)
+        self.stats = torch.zeros((len(items) + 1) * hl.STAT_COLS, dtype=torch.float64, device=dev)
+        self.ctl = torch.zeros(hl.CTL_FLOATS, dtype=torch.float32, device=dev)
+        self.ws = hl.grad_stats_workspace(len(items), dev)
+
+        self.grad_scale = 1.0
+
+    def launch(self, fp, grad_scale, threshold):
+        self.grad_scale = float(grad_scale)
+        hl.grad_stats(self.segs, fp.g, grad_scale, math.inf if threshold is None else threshold, self.stats, self.ctl, self.ws)
+
+    def read(self):
+        """Host copies of the last call's results (a host sync); the peak norm is zeroed behind the read, in stream order."""
+        ctl = self.ctl.cpu().tolist()
+        self.ctl[4:5].zero_()
+        st = self.stats.cpu().view(-1, hl.STAT_COLS).tolist()
+        tot = st[-1]
+        return {'grad_norm': ctl[3], 'grad_norm_peak': ctl[4], 'grad_max': tot[1], 'nonfinite': int(tot[2]), 'clip_rate': ctl[2],
+                'skipped': int(ctl[5]), 'tensors': {k: self.grad_scale * math.sqrt(r[0]) for k, r in zip(self.names, st[:-1])}}
+
+
 def _np_to(t, device):
     return torch.as_tensor(np.asarray(t), dtype=torch.float32).to(device)
 
@@ -316,6 +348,14 @@ class _Net:
     wgrad_stream = None
     ema = None                     # GenNet.enable_ema: the averaged network (EmaGenNet)
     sync_bn = None                 # step.GradExchange when BatchNorm is synchronised over the data-parallel ranks
+    gstats = None                  # enable_grad_stats: the gradient statistics' buffers (GradStats); step.adam_update launches them
+
+    def enable_grad_stats(self):
+        """Allocate, once, what the gradient statistics of this network need (step.TrainStep(grad_stats=True), or a clipping
+        threshold on its optimizer).  Calling it again keeps the buffers and their counters."""
+        if self.gstats is None:
+            self.gstats = GradStats(self.fp)
+        return self.gstats
 
     # (round 4: queueing a layer's weight gradient behind its input-gradient GEMM was measured slower, profiles/NOTES.md)
     def _wgrad(self, geom, x, y, dw):
@@ -518,6 +558,8 @@ class _Net:
         self.ws = self.ws.to(device)
         self.device = device
         self._reset_derived()
+        if self.gstats is not None:                            # (fresh buffers on the new device: peak and skip count start again)
+            self.gstats = GradStats(self.fp) if device.type == 'cuda' else None
         if self.ema is not None:
             self.fp.e = self.fp.e.to(device)
             self.ema._moved(self)

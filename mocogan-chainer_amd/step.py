@@ -42,11 +42,25 @@ class AdamHyper:
     """train.py:93-101 -- Chainer Adam(alpha=2e-4, beta1=5e-5) (beta2 0.999 / eps 1e-8 defaults)
     plus the WeightDecay(1e-5) hook."""
 
-    def __init__(self, alpha=2e-4, beta1=5e-5, beta2=0.999, eps=1e-8, weight_decay=1e-5):
+    def __init__(self, alpha=2e-4, beta1=5e-5, beta2=0.999, eps=1e-8, weight_decay=1e-5, clip=None):
         self.alpha, self.beta1, self.beta2, self.eps, self.weight_decay = alpha, beta1, beta2, eps, weight_decay
+        # clip: None = off; T > 0 (math.inf allowed): chainer.optimizer.GradientClipping(T) -- the loss gradient of ALL of this
+        # optimizer's parameters is scaled by min(1, T / its L2 norm) before weight decay, and an update whose gradient holds a
+        # non-finite element is skipped (math.inf: that alone).  No reference counterpart (train.py:93-101 adds WeightDecay only).
+        self.clip = check_clip(clip)
 
     def lr(self, t):
         return self.alpha * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
+
+
+def check_clip(threshold):
+    """a clipping threshold as AdamHyper carries it: None, or a float > 0 that is finite or +inf"""
+    if threshold is None:
+        return None
+    t = float(threshold)
+    if not t > 0.0:                                               # (a NaN fails too)
+        raise ValueError('the gradient-clipping threshold must be > 0 (math.inf: skip non-finite steps only), got %r' % (threshold,))
+    return t
 
 
 def ema_rate(decay, k):
@@ -62,17 +76,33 @@ def adam_update(net, hyper, grad_scale=1.0):
     """optimizer.update() tail: hooks, t += 1, per-parameter Adam -- one launch over the flat buffers.
     grad_scale: 1 / world under data parallelism (the flat gradient then holds the SUM over the ranks).
     A net with an averaged twin (nets.GenNet.enable_ema): the same launch advances the average of the parameters (fp.e), one more
-    launch behind it on the same stream the average of the running statistics."""
+    launch behind it on the same stream the average of the running statistics.
+    A net with gradient statistics (nets._Net.enable_grad_stats): their two launches go first, on this stream, over the gradient as
+    it stands (after the exchange: with grad_scale the norm is the mean gradient's).  hyper.clip set: the update then reads its
+    gradient scale from the control block they left (hl.adam_wd_ctl) and writes nothing when the gradient held a non-finite
+    element.  The host never waits for a norm, so on a skipped update everything the host does here happens all the same: t, the
+    averaged twin's k and its running statistics advance, the split filters are refreshed (to what they were)."""
     net.t += 1
     fp = net.fp
     ema = net.ema
-    if ema is None:
+    gst = net.gstats
+    clip = getattr(hyper, 'clip', None)
+    if clip is not None and gst is None:
+        raise RuntimeError('a clipping threshold needs the gradient statistics of the network: net.enable_grad_stats() '
+                           '(TrainStep does it for every optimizer that carries one)')
+    if gst is not None:
+        gst.launch(fp, grad_scale, clip)
+    r = ema_rate(ema.decay, ema.k) if ema is not None else 0.0
+    if clip is not None:
+        hl.adam_wd_ctl(fp.p, fp.g, fp.m, fp.v, hyper.lr(net.t), hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay, gst.ctl,
+                       ema=fp.e if ema is not None else None, ema_rate=r, p16=fp.p16 if net.precision == 'bf16' else None)
+    elif ema is None:
         hl.adam_wd(fp.p, fp.g, fp.m, fp.v, hyper.lr(net.t), hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay, grad_scale,
                    p16=fp.p16 if net.precision == 'bf16' else None)
     else:
-        r = ema_rate(ema.decay, ema.k)
         hl.adam_wd_ema(fp.p, fp.g, fp.m, fp.v, hyper.lr(net.t), hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay, fp.e, r, grad_scale,
                        p16=fp.p16 if net.precision == 'bf16' else None)
+    if ema is not None:
         hl.ema_multi([(net.running[key], ema.running[key]) for key in sorted(net.running)], r)
         ema.k += 1
         ema.written(net)
@@ -164,7 +194,7 @@ class TrainStep:
     """Holds the three networks, their Adam hyper-parameters and runs update_core on device data."""
 
     def __init__(self, model, gen, dis_i, dis_v, hyper=None, exchange=None, seed=0, rank=0, precision=None, overlap=False, sync_bn=False,
-                 input_ready_early=False, ema_decay=None, augment=None):
+                 input_ready_early=False, ema_decay=None, augment=None, grad_stats=False):
         assert model in ('normal', 'cgan', 'infogan')
         self.model, self.gen, self.dis_i, self.dis_v = model, gen, dis_i, dis_v
         if precision is not None:                                 # 'f32' | 'bf16': MFMA operand type of every conv GEMM
@@ -186,6 +216,14 @@ class TrainStep:
         self.augment = hl.parse_augment(augment)
         self.hyper = hyper or {'image_gen': AdamHyper(), 'image_dis': AdamHyper(), 'video_dis': AdamHyper()}
         self.exchange = exchange
+        # grad_stats: False = off (nothing allocated, the launches of before).  True: every network's Adam update is preceded by the
+        # two launches of hl.grad_stats over its flat gradient -- norm, peak, largest element, non-finite count, per-tensor norms,
+        # read with grad_stats() -- and stays on the launch it had.  A clipping threshold on an optimizer (AdamHyper.clip) implies the
+        # statistics for that network, whose update then goes through hl.adam_wd_ctl (adam_update).
+        self._nets = {'image_gen': gen, 'image_dis': dis_i, 'video_dis': dis_v}
+        for name, net in self._nets.items():
+            if grad_stats or getattr(self.hyper[name], 'clip', None) is not None:
+                net.enable_grad_stats()
         # sync_bn (opt-in): BatchNorm statistics and their backward sums are all-reduced over the ranks, i.e.
         # taken over the GLOBAL batch; without it every rank normalises with the statistics of its own shard.
         for net in (gen, dis_i, dis_v):
@@ -509,6 +547,12 @@ class TrainStep:
         return {**res, 'x_fake': x_fake, 't_fake': t_fake, 't': t, 'gx_fake': gx, 'saved_gen': s_gen, 'saved_fake_i': s_fake_i, 'saved_fake_v': s_fake_v,
                 'saved_i': s_i, 'saved_v': s_v,
                 'y_real_i': y_real_i, 'y_real_v': y_real_v, 'y_fake_i': y_fake_i, 'y_fake_v': y_fake_v}
+
+    def grad_stats(self):
+        """{network: {'grad_norm', 'grad_norm_peak' (since the last read; zeroed behind it), 'grad_max', 'nonfinite', 'clip_rate',
+        'skipped' (updates so far), 'tensors': {parameter: norm}}} of the last iteration, for every network that keeps the
+        statistics -- forces a host sync, like losses().  Norms are those of the gradient the update saw (the mean over the ranks)."""
+        return {name: net.gstats.read() for name, net in self._nets.items() if net.gstats is not None}
 
     def losses(self):
         """(loss_dis_i, loss_dis_v, loss_gen) of the last iteration -- forces a host sync."""

@@ -19,6 +19,17 @@ class WeightDecay:
         self.rate = rate
 
 
+class GradientClipping:
+    """chainer.optimizer.GradientClipping(threshold): the gradient of all of the optimizer's parameters is scaled by
+    threshold / ||g||_2 when that is below 1.  Here the norm is taken on the device in front of the Adam launch (step.adam_update),
+    the scale acts on the loss gradient before weight decay whatever the order of the add_hook calls, and an update whose gradient
+    holds a non-finite element is skipped; threshold math.inf keeps that skip alone."""
+    name = 'GradientClipping'
+
+    def __init__(self, threshold):
+        self.threshold = threshold
+
+
 class Adam:
     """chainer.optimizers.Adam hyper-parameters; the update itself is the fused kernel (step.adam_update)."""
 
@@ -40,7 +51,11 @@ class Adam:
 
     def hyper(self):
         wd = sum(h.rate for h in self._hooks.values() if isinstance(h, WeightDecay))
-        return _step.AdamHyper(self.alpha, self.beta1, self.beta2, self.eps, wd)
+        clips = [h.threshold for h in self._hooks.values() if isinstance(h, GradientClipping)]
+        if len(clips) > 1:
+            raise ValueError('more than one GradientClipping hook on one optimizer')
+        # (the threshold is validated by AdamHyper: > 0, finite or +inf)
+        return _step.AdamHyper(self.alpha, self.beta1, self.beta2, self.eps, wd, clip=clips[0] if clips else None)
 
 
 # ---- iterator (train.py:66) -----------------------------------------------------------------------

@@ -37,6 +37,9 @@ class Updater:
         ema_decay = kwargs.pop('ema_decay', None)
         # None: off; 'color,translation,cutout' (any subset) or a mask: differentiable augmentation in front of both discriminators
         augment = kwargs.pop('augment', None)
+        # False: off; True: per-network gradient norms from the device, reported with the losses at every new epoch (a
+        # GradientClipping hook on an optimizer switches them on for its network either way; they are reported only with this)
+        self._grad_stats = bool(kwargs.pop('grad_stats', False))
         if kwargs:
             raise TypeError('unexpected arguments: %s' % sorted(kwargs))
         self.iteration = 0
@@ -44,7 +47,8 @@ class Updater:
         hyper = {k: self._optimizers[k].hyper() for k in ('image_gen', 'image_dis', 'video_dis')}
         self._step = _step.TrainStep(self.model, self.image_gen.impl, self.image_dis.impl, self.video_dis.impl,
                                      hyper=hyper, exchange=exchange, seed=seed, rank=rank, overlap=overlap,
-                                     precision=precision, sync_bn=sync_bn, ema_decay=ema_decay, augment=augment)
+                                     precision=precision, sync_bn=sync_bn, ema_decay=ema_decay, augment=augment,
+                                     grad_stats=self._grad_stats)
 
     # ---- StandardUpdater surface -------------------------------------------------------------------
     def get_optimizer(self, name):
@@ -172,3 +176,8 @@ class Updater:
             self.observation = dict(l)
             for name, link in self.links().items():
                 self.tf_writer.add_scalar('loss:{}'.format(link.name), l['%s/loss' % name], self.epoch)
+            if self._grad_stats:
+                for name, st in self._step.grad_stats().items():
+                    for key in ('grad_norm', 'grad_norm_peak', 'clip_rate', 'skipped'):
+                        self.observation['%s/%s' % (name, key)] = float(st[key])
+                        self.tf_writer.add_scalar('{}:{}'.format(key, self.links()[name].name), float(st[key]), self.epoch)

@@ -62,8 +62,13 @@ def main():
                                                                   "keeps the averaged generator as well")
     ap.add_argument('--augment', default='', help="train.py's flag: '' = off, a subset of color,translation,cutout = differentiable "
                                                   "augmentation in front of both discriminators")
+    ap.add_argument('--grad_clip', type=float, default=0.0, help="train.py's flag: 0 = off, T > 0 (or inf) = a GradientClipping(T) hook on all "
+                                                                  "three optimizers (norm on the device, non-finite updates skipped)")
+    ap.add_argument('--grad_stats', type=int, default=0, choices=[0, 1], help="train.py's flag: 1 = gradient norms reported with the losses")
     ap.add_argument('--out', default=os.path.join(ROOT, 'bench_train.json'))
     args = ap.parse_args()
+    if not args.grad_clip >= 0.0:
+        ap.error('--grad_clip must be 0 (off), a positive threshold or inf')
 
     import torch
     from model.net import ImageGenerator, ImageDiscriminator, VideoDiscriminator
@@ -103,11 +108,14 @@ def main():
         o = T.Adam(alpha=2e-4, beta1=5e-5)
         o.setup(model)
         o.add_hook(T.WeightDecay(1e-5), 'hook_dec')
+        if args.grad_clip > 0:
+            o.add_hook(T.GradientClipping(args.grad_clip), 'hook_clip')
         return o
     updater = Updater(model=args.model, models=(gen, di, dv), video_length=T_, img_size=64, channel=channel, dim_zl=num_labels,
                       iterator=it, tensorboard_writer=T.NullWriter(), optimizer={'image_gen': opt(gen), 'image_dis': opt(di), 'video_dis': opt(dv)},
                       device=0, seed=0, overlap=bool(args.overlap), precision=args.mfma,
-                      **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}), **(dict(augment=args.augment) if args.augment else {}))
+                      **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}), **(dict(augment=args.augment) if args.augment else {}),
+                      **(dict(grad_stats=True) if args.grad_stats else {}))
     out_dir = '/tmp/mcg_bench_train'
 
     def run_to(n):
@@ -124,7 +132,7 @@ def main():
     dt = time.perf_counter() - t0
     rec = {"path": "train.py object graph: Trainer + Updater.update_core + %s" % type(it).__name__, "data": args.data,
            "loader_workers": args.loader_workers, "dtype": args.mfma, "model": args.model, "batch": args.batchsize, "iters": args.iters,
-           "ema_decay": args.ema_decay, "augment": args.augment, "side_streams": bool(args.overlap), "two_chain_iterations": mstep.chain_iterations - chains0,
+           "ema_decay": args.ema_decay, "augment": args.augment, "grad_clip": args.grad_clip, "grad_stats": args.grad_stats, "side_streams": bool(args.overlap), "two_chain_iterations": mstep.chain_iterations - chains0,
            "clips_per_s": round(args.batchsize * args.iters / dt, 1), "ms_per_iteration": round(dt / args.iters * 1e3, 3),
            "epochs_seen": updater.epoch, "dataset_clips": args.size}
     print(json.dumps(rec), flush=True)

@@ -79,9 +79,18 @@ def parse_args(argv=None):
                    help="'' (default): off.  A comma-separated subset of color,translation,cutout: differentiable augmentation (Zhao et "
                         "al. 2020) of the real and the generated clips in front of both discriminators, one random parameter set per "
                         "clip; the generator's gradient is carried back through it")
+    p.add_argument('--grad_clip', type=float, default=0.0,
+                   help="0 (default): off.  T > 0: a GradientClipping(T) hook on all three optimizers -- each network's gradient is "
+                        "scaled to an L2 norm of at most T (taken on the device, no host sync), and an update whose gradient holds "
+                        "a non-finite element is skipped; inf: that skip alone")
+    p.add_argument('--grad_stats', type=int, default=0, choices=[0, 1],
+                   help="1: per-network gradient norm, peak norm, clipping rate and skipped updates in the log and TensorBoard at "
+                        "every new epoch (two short launches per network and iteration)")
     args = p.parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0:
         p.error('--ema_decay must lie in [0, 1)')
+    if not args.grad_clip >= 0.0:                                # (a NaN fails too)
+        p.error('--grad_clip must be 0 (off), a positive threshold or inf')
     try:
         from mocogan_chainer_amd.hiplib import parse_augment
         parse_augment(args.augment)
@@ -161,6 +170,8 @@ def main(argv=None):
         optimizer = T.Adam(alpha=alpha, beta1=beta1)              # beta2 is not forwarded (train.py:94)
         optimizer.setup(model)
         optimizer.add_hook(T.WeightDecay(1e-5), 'hook_dec')
+        if args.grad_clip > 0:
+            optimizer.add_hook(T.GradientClipping(args.grad_clip), 'hook_clip')
         return optimizer
 
     opts = {'image_gen': make_optimizer(image_gen, 2e-4, 5e-5, 0.999),
@@ -171,7 +182,8 @@ def main(argv=None):
                       img_size=size, channel=channel, dim_zl=num_labels, iterator=train_iter,
                       tensorboard_writer=writer, optimizer=opts, device=args.gpu, seed=args.seed, exchange=exchange, rank=rank,
                       overlap=bool(args.overlap), precision=args.mfma, sync_bn=bool(args.sync_bn),
-                      ema_decay=args.ema_decay if args.ema_decay > 0 else None, augment=args.augment or None)
+                      ema_decay=args.ema_decay if args.ema_decay > 0 else None, augment=args.augment or None,
+                      grad_stats=bool(args.grad_stats))
 
     save_path = Path('result') / args.save_name
     trainer = T.Trainer(updater, (args.max_epoch, 'epoch'), out=save_path)
