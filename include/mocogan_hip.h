@@ -537,9 +537,11 @@ int mcg_randint(int64_t n, int modulus, uint64_t seed, uint64_t stream_id, int32
  *   contiguous row for the sort), on v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation; any D (the tail is zero-filled).
  * mcg_sort_rows: sorts `rows` independent rows data[r * row_stride .. + n) ascending, in place, keys only, any n >= 1; elements
  *   n .. row_stride of a row are not touched.  Bitonic: steps inside mcg_sort_local_span() elements run in LDS, every wider step is
- *   a launch of its own over the rows padded to a power of two with +inf in `workspace` (not needed, may be NULL, for
- *   n <= mcg_sort_local_span()).  No kernel waits on another workgroup.  Values finite or +-inf; with NaN the order is
- *   unspecified but every access stays inside the row (indices do not depend on values).  rows <= 65535.
+ *   a launch of its own over the rows padded to a power of two in `workspace` (not needed, may be NULL, for
+ *   n <= mcg_sort_local_span()).  No kernel waits on another workgroup.  The order is the total order of the bit patterns that
+ *   agrees with < on finite and infinite values: -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN, NaNs by payload.  So the result is
+ *   a permutation of the row's bit patterns whatever it holds, and equal to a comparison sort's wherever the values are no NaN
+ *   (-0 before +0).  Every access stays inside the row (indices do not depend on values).  rows <= 65535.
  * mcg_swd_distance: out[0] = mean over k < K, i < n of |a[k][i] - b[k][i]| for two sorted sets (differences and sums in double, fixed
  *   order: out(a, b) == out(b, a) bit for bit and out(a, a) == 0).  n_a != n_b is MCG_ERR_BAD_ARG.
  * MCG_ERR_BAD_ARG: a null pointer, a non-positive extent, C outside 1..3, pt > T, a stride below its extent. */

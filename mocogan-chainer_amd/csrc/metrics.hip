@@ -12,7 +12,7 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int NT = 256;
 constexpr int RED_BLOCKS = 1024;     // max partial-sum blocks of the statistics and distance passes (workspace sizing)
@@ -278,26 +278,41 @@ __global__ __launch_bounds__(NT) void swd_project_kernel(long long n, int D, int
 }
 
 // ------------------------------------------------------------------------------------------
-// Bitonic sort of independent rows.  The row is seen padded to a power of two n2 with +inf.  Steps with a partner distance below
-// SORT_L run on a span of SORT_L elements in LDS (one launch for all of them); the steps with a larger distance are launches of
+// Bitonic sort of independent rows.  Values are compared as keys: the bit pattern with the magnitude bits of negative values
+// inverted, a signed integer that orders like the value for everything finite or infinite and is a TOTAL order of all bit
+// patterns (-NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN).  The row is seen padded to a power of two n2 with the largest key
+// (0x7fffffff), so the first n elements of the sorted padded row are the row's own bit patterns whatever they hold (a float
+// comparison is false both ways for a NaN: next to +inf padding it put padding into the first n places and elements out of them).
+// Steps with a partner distance below SORT_L run on a span of SORT_L elements in LDS (one launch for all of them); the steps with a larger distance are launches of
 // their own over the padded rows in the workspace, two steps to a launch where both are that wide.  Element i's partner in step j is i ^ j, its direction in stage k is ascending where
 // (i & k) == 0: indices depend on nothing but (i, j, k), so no value (NaN included) can move an access.
 // ------------------------------------------------------------------------------------------
 constexpr int SORT_L = 8192;
 
-__device__ __forceinline__ void cmpx(float& a, float& b, bool asc) {
-    if ((a > b) == asc) { const float t = a; a = b; b = t; }
+constexpr int SORT_PAD = 0x7fffffff;  // the largest key
+
+// a value's bit pattern -> its key, and back: the map is its own inverse.  The kernels see the rows as ints: no float is formed.
+__device__ __forceinline__ int sort_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+
+__device__ __forceinline__ void cmpx(int& a, int& b, bool asc) {
+    if ((a > b) == asc) { const int t = a; a = b; b = t; }
 }
 
 // full != 0: sorts each span (stages 2 .. span; span `b` ascending where (b * span & span) == 0 -- the next stage's input);
-// full == 0: the steps j = span / 2 .. 1 of stage `stage`.  Reads elements below n_src of src (others +inf), writes those below n_dst.
-__global__ __launch_bounds__(NT) void sort_local_kernel(const float* src, long long src_stride, int n_src, float* dst,
-                                                        long long dst_stride, int n_dst, int span, int stage, int full) {
-    __shared__ float s[SORT_L];
+// full == 0: the steps j = span / 2 .. 1 of stage `stage`.  Reads elements below n_src of src (others the pad key), writes those
+// below n_dst.  LDS and the workspace hold keys, the caller's rows values: src_values / dst_values say which of the two src and
+// dst are (so a value is converted once on its way in and once on its way out, whatever the number of launches).
+__global__ __launch_bounds__(NT) void sort_local_kernel(const int* src, long long src_stride, int n_src, int src_values, int* dst,
+                                                        long long dst_stride, int n_dst, int dst_values, int span, int stage, int full) {
+    __shared__ int s[SORT_L];
     const int base = blockIdx.x * span;
-    const float* in = src + (long long)blockIdx.y * src_stride;
-    float* o = dst + (long long)blockIdx.y * dst_stride;
-    for (int i = threadIdx.x; i < span; i += NT) s[i] = base + i < n_src ? in[base + i] : INFINITY;
+    const int* in = src + (long long)blockIdx.y * src_stride;
+    int* o = dst + (long long)blockIdx.y * dst_stride;
+    for (int i = threadIdx.x; i < span; i += NT) {
+        int k = SORT_PAD;
+        if (base + i < n_src) { k = in[base + i]; if (src_values) k = sort_key(k); }
+        s[i] = k;
+    }
     __syncthreads();
     auto step = [&](int k, int j) {
         for (int p = threadIdx.x; p < (span >> 1); p += NT) {
@@ -312,48 +327,48 @@ __global__ __launch_bounds__(NT) void sort_local_kernel(const float* src, long l
     } else {
         for (int j = span >> 1; j > 0; j >>= 1) step(stage, j);
     }
-    for (int i = threadIdx.x; i < span; i += NT) if (base + i < n_dst) o[base + i] = s[i];
+    for (int i = threadIdx.x; i < span; i += NT) if (base + i < n_dst) o[base + i] = dst_values ? sort_key(s[i]) : s[i];
 }
 
-// one step with partner distance j >= SORT_L of stage k over the padded rows ws [rows][n2]; a thread owns 4 consecutive pairs
-__global__ __launch_bounds__(NT) void sort_global_kernel(float* __restrict__ ws, int n2, int k, int j) {
+// one step with partner distance j >= SORT_L of stage k over the padded rows' keys ws [rows][n2]; a thread owns 4 consecutive pairs
+__global__ __launch_bounds__(NT) void sort_global_kernel(int* __restrict__ ws, int n2, int k, int j) {
     const int p = 4 * (blockIdx.x * NT + threadIdx.x);
     if (p >= (n2 >> 1)) return;
     const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-    float* row = ws + (long long)blockIdx.y * n2;
-    f32x4 a = *reinterpret_cast<const f32x4*>(row + i), b = *reinterpret_cast<const f32x4*>(row + i + j);
+    int* row = ws + (long long)blockIdx.y * n2;
+    i32x4 a = *reinterpret_cast<const i32x4*>(row + i), b = *reinterpret_cast<const i32x4*>(row + i + j);
     const bool asc = (i & k) == 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        float x = a[e], y = b[e];
+        int x = a[e], y = b[e];
         cmpx(x, y, asc);
         a[e] = x; b[e] = y;
     }
-    *reinterpret_cast<f32x4*>(row + i) = a;
-    *reinterpret_cast<f32x4*>(row + i + j) = b;
+    *reinterpret_cast<i32x4*>(row + i) = a;
+    *reinterpret_cast<i32x4*>(row + i + j) = b;
 }
 
 // the two steps j and j / 2 (both >= SORT_L) of stage k in one pass: the four elements i, i + j/2, i + j, i + 3j/2 (i with zero
 // bits at j and j / 2) exchange among themselves only; a thread owns 4 consecutive such quadruples
-__global__ __launch_bounds__(NT) void sort_global2_kernel(float* __restrict__ ws, int n2, int k, int j) {
+__global__ __launch_bounds__(NT) void sort_global2_kernel(int* __restrict__ ws, int n2, int k, int j) {
     const int p = 4 * (blockIdx.x * NT + threadIdx.x), h = j >> 1;
     if (p >= (n2 >> 2)) return;
     const int i = ((p & ~(h - 1)) << 2) | (p & (h - 1));
-    float* row = ws + (long long)blockIdx.y * n2;
-    f32x4 v0 = *reinterpret_cast<const f32x4*>(row + i), v1 = *reinterpret_cast<const f32x4*>(row + i + h);
-    f32x4 v2 = *reinterpret_cast<const f32x4*>(row + i + j), v3 = *reinterpret_cast<const f32x4*>(row + i + j + h);
+    int* row = ws + (long long)blockIdx.y * n2;
+    i32x4 v0 = *reinterpret_cast<const i32x4*>(row + i), v1 = *reinterpret_cast<const i32x4*>(row + i + h);
+    i32x4 v2 = *reinterpret_cast<const i32x4*>(row + i + j), v3 = *reinterpret_cast<const i32x4*>(row + i + j + h);
     const bool asc = (i & k) == 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        float a = v0[e], b = v1[e], c = v2[e], d = v3[e];
+        int a = v0[e], b = v1[e], c = v2[e], d = v3[e];
         cmpx(a, c, asc); cmpx(b, d, asc);         // step j
         cmpx(a, b, asc); cmpx(c, d, asc);         // step j / 2
         v0[e] = a; v1[e] = b; v2[e] = c; v3[e] = d;
     }
-    *reinterpret_cast<f32x4*>(row + i) = v0;
-    *reinterpret_cast<f32x4*>(row + i + h) = v1;
-    *reinterpret_cast<f32x4*>(row + i + j) = v2;
-    *reinterpret_cast<f32x4*>(row + i + j + h) = v3;
+    *reinterpret_cast<i32x4*>(row + i) = v0;
+    *reinterpret_cast<i32x4*>(row + i + h) = v1;
+    *reinterpret_cast<i32x4*>(row + i + j) = v2;
+    *reinterpret_cast<i32x4*>(row + i + j + h) = v3;
 }
 
 int pow2_at_least(long long n) {
@@ -471,15 +486,17 @@ extern "C" int mcg_sort_rows(int rows, int64_t n, float* data, int64_t row_strid
     if (n == 1) return MCG_OK;
     const int n2 = pow2_at_least(n);
     hipStream_t st = (hipStream_t)stream;
+    int* rows_bits = reinterpret_cast<int*>(data);
     if (n2 <= SORT_L) {
-        hipLaunchKernelGGL(sort_local_kernel, dim3(1, rows), dim3(NT), 0, st, data, (long long)row_stride, (int)n, data, (long long)row_stride,
-                           (int)n, n2, 0, 1);
+        hipLaunchKernelGGL(sort_local_kernel, dim3(1, rows), dim3(NT), 0, st, rows_bits, (long long)row_stride, (int)n, 1, rows_bits,
+                           (long long)row_stride, (int)n, 1, n2, 0, 1);
         return launch_status();
     }
     if (!workspace || ((uintptr_t)workspace & 15)) return MCG_ERR_BAD_ARG;
-    float* ws = (float*)workspace;
+    int* ws = (int*)workspace;                                  // the padded rows' keys
     const dim3 lgrid(n2 / SORT_L, rows), ggrid(n2 / 8 / NT, rows), g2grid(n2 / 16 / NT, rows);
-    hipLaunchKernelGGL(sort_local_kernel, lgrid, dim3(NT), 0, st, data, (long long)row_stride, (int)n, ws, (long long)n2, n2, SORT_L, 0, 1);
+    hipLaunchKernelGGL(sort_local_kernel, lgrid, dim3(NT), 0, st, rows_bits, (long long)row_stride, (int)n, 1, ws, (long long)n2, n2, 0,
+                       SORT_L, 0, 1);
     for (long long k = 2LL * SORT_L; k <= n2; k <<= 1) {
         for (int j = (int)(k >> 1); j >= SORT_L;) {
             if ((j >> 1) >= SORT_L) {
@@ -491,8 +508,8 @@ extern "C" int mcg_sort_rows(int rows, int64_t n, float* data, int64_t row_strid
             }
         }
         const bool last = k == n2;
-        hipLaunchKernelGGL(sort_local_kernel, lgrid, dim3(NT), 0, st, ws, (long long)n2, n2, last ? data : ws,
-                           last ? (long long)row_stride : (long long)n2, last ? (int)n : n2, SORT_L, (int)k, 0);
+        hipLaunchKernelGGL(sort_local_kernel, lgrid, dim3(NT), 0, st, ws, (long long)n2, n2, 0, last ? rows_bits : ws,
+                           last ? (long long)row_stride : (long long)n2, last ? (int)n : n2, last ? 1 : 0, SORT_L, (int)k, 0);
     }
     return launch_status();
 }

@@ -122,6 +122,77 @@ def projection_bound(desc, dirs, extra=0):
     return (desc.shape[1] + extra) * 2.0 ** -24 * (np.abs(desc) @ np.abs(dirs))
 
 
+# ---- 6. the reductions' launch geometry and error bound -----------------------------------------------------------------------
+RED_THREADS, RED_BLOCKS, NORM_BLOCKS = 256, 1024, 8192    # metrics.hip: NT, RED_BLOCKS, the grid cap of mcg_swd_normalize
+
+
+def reduction_blocks(total, cap=RED_BLOCKS):
+    """blocks of the statistics / distance partial pass over `total` elements (`cap` blocks of 256 threads at most)"""
+    return min(cap, -(-total // RED_THREADS))
+
+
+def reduction_trips(total, cap=RED_BLOCKS):
+    """the most elements one thread of that pass adds: ceil(total / (blocks * 256)); above one the grid-stride loop repeats"""
+    return -(-total // (reduction_blocks(total, cap) * RED_THREADS))
+
+
+def double_sum_bound(total, abs_sum):
+    """|device sum - math.fsum| <= (trips + 24) 2^-53 fsum(|terms|) for the two-pass double sums of metrics.hip over `total` terms.
+    A term passes through at most `trips` additions in its thread, 8 levels of the block's tree, ceil(blocks / 256) <= 4 additions
+    of the fold kernel's thread and 8 more tree levels: depth d <= trips + 20, and a sum whose every term passes through at most d
+    roundings of 2^-53 errs by at most ((1 + 2^-53)^d - 1) sum |terms| = d 2^-53 sum |terms| (1 + 1e-14).  The terms themselves are
+    exact (an fp32 value, the square of one, the difference of two of like magnitude are doubles).  One of the four spare units is
+    the rounding of math.fsum's own result; the others are slack, not measured."""
+    return (reduction_trips(total) + 24) * 2.0 ** -53 * abs_sum
+
+
+# ---- 7. the launch schedule of mcg_sort_rows, emulated -------------------------------------------------------------------------
+def sort_rows_emulation(x, L):
+    """one row through the launch schedule of mcg_sort_rows with a local span of L: (the sorted row, the launches as
+    ('local_full',), ('global', k, j), ('global2', k, j), ('local', k)).  Element i meets i ^ j in step j and sorts ascending in
+    stage k where (i & k) == 0; a 'global2' launch is the steps j and j / 2, a 'local' launch the steps L / 2 .. 1 of its stage."""
+    x = np.asarray(x)
+    n2 = 2
+    while n2 < len(x):
+        n2 <<= 1
+    v = np.full(n2, np.inf, x.dtype)
+    v[:len(x)] = x
+    idx = np.arange(n2)
+
+    def step(k, j):
+        lo = idx[(idx & j) == 0]
+        a, b = v[lo], v[lo | j]
+        swap = (a > b) == ((lo & k) == 0)
+        v[lo], v[lo | j] = np.where(swap, b, a), np.where(swap, a, b)
+
+    launches = [('local_full',)]
+    k = 2
+    while k <= min(L, n2):
+        j = k >> 1
+        while j > 0:
+            step(k, j)
+            j >>= 1
+        k <<= 1
+    while k <= n2:
+        j = k >> 1
+        while j >= L:
+            if (j >> 1) >= L:
+                launches.append(('global2', k, j))
+                step(k, j)
+                step(k, j >> 1)
+                j >>= 2
+            else:
+                launches.append(('global', k, j))
+                step(k, j)
+                j >>= 1
+        launches.append(('local', k))
+        while j > 0:
+            step(k, j)
+            j >>= 1
+        k <<= 1
+    return v[:len(x)], launches
+
+
 # ---- the fixed test sets ------------------------------------------------------------------------------------------------------
 def blob_clips(N, T, C, seed, contrast=1.0, smooth=6):
     """smooth random blobs as uint8 clips (N,T,64,64,C): white noise, `smooth` passes of a [1,2,1]/4 blur per axis (wrapping), scaled

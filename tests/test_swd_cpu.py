@@ -237,3 +237,44 @@ def test_fixed_sets_have_no_constant_channel_and_a_distance_far_above_the_gpu_to
             tol = max(tol, sr.projection_bound(da[s], dirs, 8).max() + sr.projection_bound(db[s], dirs, 8).max())
         assert res[str(s)] * 1e-3 >= 100 * tol, (s, res[str(s)] * 1e-3, tol)
     assert res['avg'] == pytest.approx(np.mean([res[str(s)] for s in sr.LEVELS]))
+
+
+def test_edge_chain_shape_has_a_distance_far_above_the_gpu_tolerance():
+    """the same margin for the chain of tests/test_gpu_swd_edges.py: P = 10923 patches of each of 3 clips (n = 32769 = 4 L + 1 at
+    L = 8192), D = 147, K = 136 directions (two tiles), one repeat, on the reference's own levels"""
+    C, P_, K_ = 3, 10923, 136
+    real, fake = sr.fixed_sets(C)
+    da, db = sr.descriptors(sr.pyramid(real), C, P_, 1, SEED), sr.descriptors(sr.pyramid(fake), C, P_, 1, SEED)
+    res = sr.distance(da, db, 1, K_, SEED)
+    for li, s in enumerate(sr.LEVELS):
+        assert da[s].shape == (32769, 147)
+        dirs = sr.unit_columns(sr.raw_directions(li, 0, 147, K_, SEED))
+        tol = sr.projection_bound(da[s], dirs, 8).max() + sr.projection_bound(db[s], dirs, 8).max()
+        print("edge chain level %d: ref %.6f, tol %.3e, ref / tol %.0f" % (s, res[str(s)] * 1e-3, tol, res[str(s)] * 1e-3 / tol))
+        assert res[str(s)] * 1e-3 >= 100 * tol, (s, res[str(s)] * 1e-3, tol)
+
+
+# ---- the sort's launch schedule, scaled down -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("length", ['L', '2L+3', '4L+1', '8L+5', '16L+1', '64L'])
+def test_emulated_sort_schedule_sorts_and_has_the_launch_patterns_the_gpu_tests_name(length):
+    """the host loop of mcg_sort_rows, restated in swd_ref.sort_rows_emulation and run with a local span of 16: it sorts at the
+    lengths the GPU tests use (so a failure there is the kernels', not the schedule's), and a 'global2' launch is followed by a
+    'global' one in a stage first at n2 = 8 L, by a second 'global2' first at n2 = 16 L"""
+    L = 16
+    m, r = length.split('L')
+    n = (int(m) if m else 1) * L + (int(r) if r else 0)
+    rng = np.random.RandomState(n)
+    for x in (rng.randn(n).astype(np.float32), rng.randint(-3, 4, n).astype(np.float32), np.sort(rng.randn(n).astype(np.float32))[::-1]):
+        got, launches = sr.sort_rows_emulation(x, L)
+        assert np.array_equal(got, np.sort(x))
+    stages = {}
+    for la in launches[1:]:
+        stages.setdefault(la[1], []).append(la[0])
+    n2 = 1 << (n - 1).bit_length()
+    assert sorted(stages) == [L << s for s in range(1, (n2 // L).bit_length())]
+    kinds = set(tuple(v) for v in stages.values())
+    assert all(v[-1] == 'local' for v in kinds)
+    assert (('global2', 'global', 'local') in kinds) == (n2 >= 8 * L)
+    assert (('global2', 'global2', 'local') in kinds) == (n2 >= 16 * L)
+    # the descending half of a 'global2' launch: some element of it has (i & k) != 0 exactly when k < n2
+    assert any(la[0] == 'global2' and la[1] < n2 for la in launches) == (n2 >= 8 * L)
