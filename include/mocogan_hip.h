@@ -199,11 +199,15 @@ typedef struct mcg_conv_epilogue {
                                  * counter per (row quad, channel) of the group's output -- element (m, c) is normal
                                  * m & 3 of counter (m >> 2) * C + c (mcg_randn_rowquad draws the same stream) */
     uint64_t seed, stream_id[2];
-    uint32_t* mask_out;         /* [rows][(C+31)/32] words, bit c & 31 of word c >> 5 set <=> pre-activation >= 0; or NULL */
+    uint32_t* mask_out;         /* [rows][(C+31)/32] words, bit c & 31 of word c >> 5 set <=> pre-activation >= 0; or NULL.  When C is
+                                 * not a multiple of 32 the bits of a row's last word that belong to columns >= C are unspecified
+                                 * (every word is written whole); mask_in never looks at them */
     int32_t out_bf16;           /* the OUTPUT tensor (y of fprop, x of dgrad) is bf16 (uint16_t, round-to-nearest-even) --
                                  * what the next layer's GEMMs (with act) or the element-wise passes (without) of a bf16
                                  * network read.  With the plain store or any epilogue (MCG_SUMS_BN_BWD: LDS-DMA kernels only); never with a
-                                 * split-K tile code, an accumulating dgrad or the Ci = 4 layers (MCG_ERR_UNSUPPORTED).  The
+                                 * split-K tile code, an accumulating dgrad, the input gradient of the Ci = 4 layers or MCG_PREC_SPLIT
+                                 * operands, and on the LDS-DMA kernels (tile 7 / 8 / 10, which store runs of 8 channels) only when the
+                                 * output's channel count is a multiple of 8 (MCG_ERR_UNSUPPORTED).  The
                                  * sums of an epilogue are those of the STORED (rounded) values: BatchNorm then normalises the
                                  * tensor it reads with that tensor's own mean and variance.
                                  * MCG_IO_OUT_SPLIT (ABI 7; mcg_conv_fprop_ex with act, Co a multiple of 16): y is written in the
@@ -218,7 +222,10 @@ typedef struct mcg_conv_epilogue {
      * together with out_bf16): bn_y is bf16 (uint16_t) instead of fp32; the sums are those of the STORED output values */
     int32_t bn_y_bf16;
 } mcg_conv_epilogue;
-/* upper bound of the bytes `part` needs for this geometry (any tile choice); pass = 0 fprop, 1 dgrad */
+/* upper bound of the bytes `part` needs for this geometry (any tile choice); pass = 0 fprop, 1 dgrad.  It is the need of the
+ * smallest block tile (64 rows; dgrad: per output-parity class, four classes): a launch writes n_slots * slot_stride floats,
+ * slot_stride == groups * 2 * C, at most that many and fewer with a taller tile; nothing behind them is touched, every float of
+ * them is written (MCG_SUMS_COL: the second of each pair holds no defined value).  A refused launch writes nothing at all. */
 int64_t mcg_conv_epilogue_part_bytes(const mcg_conv_geom* g, int pass, int groups);
 int mcg_conv_fprop_ex(const mcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y,
                       mcg_conv_epilogue* ep, void* stream);

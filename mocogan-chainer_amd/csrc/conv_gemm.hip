@@ -3748,6 +3748,9 @@ int conv_fprop_impl(const mcg_conv_geom* c, const float* x, const float* w, cons
     if (t == 6 || t == 9) return MCG_ERR_UNSUPPORTED;
     if (t == 7 || t == 8 || t == 10) {                             // the LDS-DMA kernels (wide layers)
         if (!split && !v2_ok(g, g.Ci)) return MCG_ERR_UNSUPPORTED;
+        // the row-wise bf16 store (store_vec8_bf16) writes whole runs of 8 channels: with Co = 8 k + 4 (fp32 operands only; bf16-stored
+        // ones need 8 | Co anyway) the last run of a row would reach 4 elements into the next row, and past y behind the last one
+        if (e.out16 && (g.Co & 7)) return MCG_ERR_UNSUPPORTED;
         const Geom h = split ? split_geom(g, SPLIT_CI) : g;
         const int form = v2_form(g);
         if (g.dense > 1) {                                         // position-major rows (27 / 40; 37: tile 7 only)
