@@ -131,7 +131,8 @@ typedef struct mcg_conv_geom {
  *     still 8 with the averaged generator (mcg_adam_wd_ema, mcg_ema_multi added; no argument list changed)
  *     and with the differentiable augmentation (mcg_augment_* added; no argument list changed)
  *     and with the sliced Wasserstein distance (mcg_swd_*, mcg_sort_* added; no argument list changed)
- *     and with the gradient statistics (mcg_grad_stats*, mcg_adam_wd_ctl added; no argument list changed). */
+ *     and with the gradient statistics (mcg_grad_stats*, mcg_adam_wd_ctl added; no argument list changed)
+ *     and with the adaptive augmentation (mcg_augment_draw_gated, mcg_ada_update added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -402,6 +403,36 @@ int mcg_augment_bwd(int N, int C, int Cp, int T, int H, int W, const float* g_ou
  * rectangle 0, 0, 0, 0) but its words are consumed, so switching one component never changes another's draw.
  * geo [N][8] int32, col [N][4] float as above. */
 int mcg_augment_draw(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, int32_t* geo, float* col, void* stream);
+
+/* ---- adaptive augmentation: the draw gated by a probability that the discriminators' overfitting sets -------------------------
+ * Karras et al. 2020, "Training Generative Adversarial Networks with Limited Data", sections 2.2 and 3 (no reference counterpart).
+ * The state is a block of eight doubles in device memory that the caller allocates and initialises; mcg_ada_update writes it,
+ * mcg_augment_draw_gated reads it, the host never waits for it:
+ *   ada[0] = p, the probability with which each component of the policy is applied to a clip
+ *   ada[1], ada[2] = sum of sign over the VideoDiscriminator's / the ImageDiscriminator's real logits since the last adjustment
+ *   ada[3] = logits counted per discriminator, ada[4] = calls since the last adjustment
+ *   ada[5], ada[6] = r_t = E[sign(D(real))] of the VideoDiscriminator / the ImageDiscriminator at the last adjustment
+ *   ada[7] = adjustments so far
+ *
+ * mcg_augment_draw_gated: the parameters mcg_augment_draw(N, H, W, policy, seed, stream_id) writes, each component kept with
+ * probability p = ada[0].  Clip i also takes Philox counter i of (seed, gate_stream_id), words g0..g3, and with the draw's own u:
+ * colour is kept iff (double)u(g0) < p, translation iff (double)u(g1) < p, cutout iff (double)u(g2) < p; g3 is not used.  A
+ * component that fails its gate gets its identity values (as if the policy left it out).  geo[6] holds the MCG_AUG_* flags of the
+ * components that are in the policy and passed, geo[7] = 0 (mcg_augment_fwd / mcg_augment_bwd read geo[0..5] only).  So p = 0
+ * gives identity parameters for every clip, p >= 1 mcg_augment_draw's bits everywhere except geo[6].  One launch; ada is not written.
+ * MCG_ERR_BAD_ARG: what mcg_augment_draw refuses, a null ada, gate_stream_id == stream_id. */
+int mcg_augment_draw_gated(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, uint64_t gate_stream_id,
+                           const double* ada, int32_t* geo, float* col, void* stream);
+/* One step of the controller on the real clips' logits y_video, y_image [N][C] (column 0 is read: y[n * C]).  With
+ * s(y) = +1 for y > 0, -1 for y < 0, 0 for +-0 and NaN:  ada[1] += sum s(y_video), ada[2] += sum s(y_image), ada[3] += N,
+ * ada[4] += 1 (the sign sums are formed as integers: exact, no order enters).  When ada[4] >= interval the adjustment runs:
+ *   r_v = ada[1] / ada[3], r_i = ada[2] / ada[3], r = max(r_v, r_i)   (both discriminators see the same augmented clips: the one
+ *   that overfits more sets the strength);   d = (r > target) - (r < target);   ada[0] = min(1, max(0, ada[0] + d step));
+ *   ada[5] = r_v, ada[6] = r_i, ada[7] += 1, ada[1..4] = 0
+ * all in double.  One launch of one workgroup, any N >= 1.  MCG_ERR_BAD_ARG: a null pointer, N or C or interval <= 0, step
+ * negative or NaN, target NaN or outside (-1, 1). */
+int mcg_ada_update(int N, int C, const float* y_video, const float* y_image, double target, double step, int interval, double* ada,
+                   void* stream);
 
 /* ---- GRU motion-code recurrence (L.StatelessGRU, model/net.py:39-41,61-81) ------------------ */
 /* params: the six Linear links packed as [W_r|U_r|W_z|U_z|W|U], each (weights row-major

@@ -1586,34 +1586,99 @@ __global__ __launch_bounds__(NT) void augment_bwd_apply_kernel(int C, int P, int
 
 // clip i: Philox counters 2i, 2i + 1 of the stream -> words w0..w7 (w7 unused); a component the policy leaves out gets its
 // identity values, its words are consumed all the same
+struct AugDraw { float b, s, c; int dx, dy, x0, x1, y0, y1; };
+__device__ __forceinline__ void aug_philox(uint64_t ctr, uint64_t seed, uint64_t stream_id, uint32_t (&r)[4]) {
+    mcg::philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32), (uint32_t)seed,
+                       (uint32_t)(seed >> 32), r);
+}
+__device__ __forceinline__ float aug_unit(uint32_t v) { return (float)(v >> 9) * 1.1920928955078125e-07f; }       // 23 bits x 2^-23: exact in fp32
+__device__ __forceinline__ AugDraw aug_draw_clip(int i, int H, int W, int policy, uint64_t seed, uint64_t stream_id) {
+    uint32_t w[8], r[4];
+    for (int h = 0; h < 2; ++h) {
+        aug_philox(2ull * (uint64_t)i + h, seed, stream_id, r);
+        for (int k = 0; k < 4; ++k) w[4 * h + k] = r[k];
+    }
+    AugDraw a = {0.f, 1.f, 1.f, 0, 0, 0, 0, 0, 0};
+    if (policy & MCG_AUG_COLOR) { a.b = aug_unit(w[0]) - 0.5f; a.s = 2.f * aug_unit(w[1]); a.c = aug_unit(w[2]) + 0.5f; }
+    if (policy & MCG_AUG_TRANSLATION) {
+        a.dx = (int)(w[3] % (uint32_t)(2 * (W / 8) + 1)) - W / 8;
+        a.dy = (int)(w[4] % (uint32_t)(2 * (H / 8) + 1)) - H / 8;
+    }
+    if (policy & MCG_AUG_CUTOUT) {
+        const int cx = (int)(w[5] % (uint32_t)(W + 1)), cy = (int)(w[6] % (uint32_t)(H + 1));
+        int x0 = cx - W / 4, x1 = x0 + W / 2, y0 = cy - H / 4, y1 = y0 + H / 2;
+        a.x0 = x0 < 0 ? 0 : x0; a.x1 = x1 > W ? W : x1; a.y0 = y0 < 0 ? 0 : y0; a.y1 = y1 > H ? H : y1;
+    }
+    return a;
+}
+// (word 6 of geo: the components that were applied -- 0 from the plain draw, the flags that passed from the gated one)
+__device__ __forceinline__ void aug_store(const AugDraw& a, int applied, int i, int32_t* __restrict__ geo, float* __restrict__ col) {
+    int32_t* q = geo + 8 * (long long)i;
+    q[0] = a.dx; q[1] = a.dy; q[2] = a.x0; q[3] = a.x1; q[4] = a.y0; q[5] = a.y1; q[6] = applied; q[7] = 0;
+    float* f = col + 4 * (long long)i;
+    f[0] = a.b; f[1] = a.s; f[2] = a.c; f[3] = 0.f;
+}
+
 __global__ __launch_bounds__(NT) void augment_draw_kernel(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id,
                                                           int32_t* __restrict__ geo, float* __restrict__ col) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= N) return;
-    uint32_t w[8], r[4];
-    for (int h = 0; h < 2; ++h) {
-        const uint64_t ctr = 2ull * (uint64_t)i + h;
-        mcg::philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32), (uint32_t)seed,
-                           (uint32_t)(seed >> 32), r);
-        for (int k = 0; k < 4; ++k) w[4 * h + k] = r[k];
+    aug_store(aug_draw_clip(i, H, W, policy, seed, stream_id), 0, i, geo, col);
+}
+
+// The gated draw (Karras et al. 2020, section 2.2: an augmentation applied with probability p < 1 does not leak into the generated
+// clips).  Clip i also takes counter i of the gate stream, words g0..g3: colour passes iff u(g0) < p, translation iff u(g1) < p,
+// cutout iff u(g2) < p, p = ada[0] read from device memory (mcg_ada_update writes it; the host never sees it).  A component that
+// fails is drawn as if the policy left it out.
+__global__ __launch_bounds__(NT) void augment_draw_gated_kernel(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id,
+                                                                uint64_t gate_stream_id, const double* __restrict__ ada,
+                                                                int32_t* __restrict__ geo, float* __restrict__ col) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= N) return;
+    const double p = ada[0];
+    uint32_t g[4];
+    aug_philox((uint64_t)i, seed, gate_stream_id, g);
+    int pass = 0;
+    if ((double)aug_unit(g[0]) < p) pass |= MCG_AUG_COLOR;
+    if ((double)aug_unit(g[1]) < p) pass |= MCG_AUG_TRANSLATION;
+    if ((double)aug_unit(g[2]) < p) pass |= MCG_AUG_CUTOUT;
+    const int applied = policy & pass;
+    aug_store(aug_draw_clip(i, H, W, applied, seed, stream_id), applied, i, geo, col);
+}
+
+// The controller of the gate's probability (Karras et al. 2020, section 3: r_t = E[sign(D(real))] as the overfitting signal).
+// ada[8] = p, sign sum of D_V, of D_I, logits counted, calls counted, r_t of D_V, of D_I at the last adjustment, adjustments.
+// One workgroup: the signs are summed as integers -- per thread, then over the block in a fixed tree -- so the sums are exact and
+// no order enters; thread 0 does the rest in double.
+__device__ __forceinline__ int ada_sign(float y) { return (y > 0.f) - (y < 0.f); }                   // (NaN and +-0: 0)
+__global__ __launch_bounds__(NT) void ada_update_kernel(int N, int C, const float* __restrict__ y_video, const float* __restrict__ y_image,
+                                                        double target, double step, int interval, double* __restrict__ ada) {
+    __shared__ int sh_v[NT], sh_i[NT];
+    const int tid = threadIdx.x;
+    int sv = 0, si = 0;
+    for (int n = tid; n < N; n += NT) {
+        sv += ada_sign(y_video[(long long)n * C]);
+        si += ada_sign(y_image[(long long)n * C]);
     }
-    auto u = [](uint32_t v) { return (float)(v >> 9) * 1.1920928955078125e-07f; };       // 23 bits x 2^-23: exact in fp32
-    float b = 0.f, s = 1.f, c = 1.f;
-    int dx = 0, dy = 0, x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-    if (policy & MCG_AUG_COLOR) { b = u(w[0]) - 0.5f; s = 2.f * u(w[1]); c = u(w[2]) + 0.5f; }
-    if (policy & MCG_AUG_TRANSLATION) {
-        dx = (int)(w[3] % (uint32_t)(2 * (W / 8) + 1)) - W / 8;
-        dy = (int)(w[4] % (uint32_t)(2 * (H / 8) + 1)) - H / 8;
+    sh_v[tid] = sv; sh_i[tid] = si;
+    __syncthreads();
+    for (int w = NT / 2; w > 0; w >>= 1) {
+        if (tid < w) { sh_v[tid] += sh_v[tid + w]; sh_i[tid] += sh_i[tid + w]; }
+        __syncthreads();
     }
-    if (policy & MCG_AUG_CUTOUT) {
-        const int cx = (int)(w[5] % (uint32_t)(W + 1)), cy = (int)(w[6] % (uint32_t)(H + 1));
-        x0 = cx - W / 4; x1 = x0 + W / 2; y0 = cy - H / 4; y1 = y0 + H / 2;
-        x0 = x0 < 0 ? 0 : x0; x1 = x1 > W ? W : x1; y0 = y0 < 0 ? 0 : y0; y1 = y1 > H ? H : y1;
+    if (tid == 0) {
+        const double sum_v = ada[1] + (double)sh_v[0], sum_i = ada[2] + (double)sh_i[0];
+        const double count = ada[3] + (double)N, calls = ada[4] + 1.0;
+        if (calls >= (double)interval) {
+            const double r_v = sum_v / count, r_i = sum_i / count, r = fmax(r_v, r_i);
+            const double d = (double)((r > target) - (r < target));
+            ada[0] = fmin(1.0, fmax(0.0, ada[0] + d * step));
+            ada[1] = 0.0; ada[2] = 0.0; ada[3] = 0.0; ada[4] = 0.0;
+            ada[5] = r_v; ada[6] = r_i; ada[7] += 1.0;
+        } else {
+            ada[1] = sum_v; ada[2] = sum_i; ada[3] = count; ada[4] = calls;
+        }
     }
-    int32_t* q = geo + 8 * (long long)i;
-    q[0] = dx; q[1] = dy; q[2] = x0; q[3] = x1; q[4] = y0; q[5] = y1; q[6] = 0; q[7] = 0;
-    float* f = col + 4 * (long long)i;
-    f[0] = b; f[1] = s; f[2] = c; f[3] = 0.f;
 }
 
 int check_augment(int N, int C, int Cp, int T, int H, int W, const void* in, const void* geo, const void* col, const void* ws, const void* out) {
@@ -2086,6 +2151,22 @@ extern "C" int64_t mcg_augment_workspace_bytes(int N) { return N > 0 ? (int64_t)
 extern "C" int mcg_augment_draw(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, int32_t* geo, float* col, void* stream) {
     if (!geo || !col || N <= 0 || H <= 0 || W <= 0 || policy < 0 || policy > 7) return MCG_ERR_BAD_ARG;
     hipLaunchKernelGGL(augment_draw_kernel, dim3((N + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, N, H, W, policy, seed, stream_id, geo, col);
+    return launch_status();
+}
+
+extern "C" int mcg_augment_draw_gated(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, uint64_t gate_stream_id,
+                                      const double* ada, int32_t* geo, float* col, void* stream) {
+    if (!geo || !col || !ada || N <= 0 || H <= 0 || W <= 0 || policy < 0 || policy > 7 || gate_stream_id == stream_id) return MCG_ERR_BAD_ARG;
+    hipLaunchKernelGGL(augment_draw_gated_kernel, dim3((N + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, N, H, W, policy, seed, stream_id,
+                       gate_stream_id, ada, geo, col);
+    return launch_status();
+}
+
+extern "C" int mcg_ada_update(int N, int C, const float* y_video, const float* y_image, double target, double step, int interval, double* ada,
+                              void* stream) {
+    if (!y_video || !y_image || !ada || N <= 0 || C <= 0 || interval <= 0) return MCG_ERR_BAD_ARG;
+    if (!(step >= 0.0) || !(target > -1.0 && target < 1.0)) return MCG_ERR_BAD_ARG;          // (a NaN fails either test)
+    hipLaunchKernelGGL(ada_update_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, N, C, y_video, y_image, target, step, interval, ada);
     return launch_status();
 }
 

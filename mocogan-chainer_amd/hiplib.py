@@ -100,6 +100,8 @@ SIGNATURES = {
     "mcg_split_planes_multi": (_I, [_I, _P, _P]),
     "mcg_augment_workspace_bytes": (_I64, [_I]),
     "mcg_augment_draw": (_I, [_I, _I, _I, _I, _U64, _U64, _P, _P, _P]),
+    "mcg_augment_draw_gated": (_I, [_I, _I, _I, _I, _U64, _U64, _U64, _P, _P, _P, _P]),
+    "mcg_ada_update": (_I, [_I, _I, _P, _P, _D, _D, _I, _P, _P]),
     "mcg_augment_fwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcg_augment_bwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcg_swd_workspace_bytes": (_I64, [_I64, _I, _I]),
@@ -1179,6 +1181,47 @@ def augment_draw(n, H, W, policy, seed, stream_id, geo=None, col=None, device=No
     _check(load().mcg_augment_draw(n, H, W, policy, seed, stream_id, _p(_dense(geo), torch.int32), _p(_dense(col)), _stream()),
            "mcg_augment_draw")
     return geo, col
+
+
+ADA_DOUBLES = 8                                                    # the state block of the adaptive augmentation (mcg_ada_update)
+ADA_P, ADA_SUM_V, ADA_SUM_I, ADA_COUNT, ADA_CALLS, ADA_RT_V, ADA_RT_I, ADA_ADJUSTMENTS = range(8)
+
+
+def ada_state(p, device):
+    """a fresh state block: probability p, every counter zero"""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('the augmentation probability lies in [0, 1], got %r' % (p,))
+    return torch.tensor([p] + [0.0] * (ADA_DOUBLES - 1), dtype=torch.float64, device=device)
+
+
+def _ada_block(ada, name):
+    if ada.dtype != torch.float64 or ada.numel() < ADA_DOUBLES:
+        raise McgError("%s: the state block is %d doubles" % (name, ADA_DOUBLES))
+    return _p(_dense(ada), torch.float64)
+
+
+def augment_draw_gated(n, H, W, policy, seed, stream_id, gate_stream_id, ada, geo=None, col=None, device=None):
+    """augment_draw with every component of the policy kept with probability ada[0] (device memory; gates from Philox stream
+    (seed, gate_stream_id)); geo[:, 6] holds the flags that were applied"""
+    if geo is None:
+        geo = torch.empty((n, 8), dtype=torch.int32, device=device)
+        col = torch.empty((n, 4), dtype=torch.float32, device=device)
+    if geo.numel() < 8 * n or col.numel() < 4 * n:
+        raise McgError("augment_draw_gated: a parameter tensor is smaller than the clip count")
+    _check(load().mcg_augment_draw_gated(n, H, W, policy, seed, stream_id, gate_stream_id, _ada_block(ada, "augment_draw_gated"),
+                                         _p(_dense(geo), torch.int32), _p(_dense(col)), _stream()), "mcg_augment_draw_gated")
+    return geo, col
+
+
+def ada_update(y_video, y_image, target, step, interval, ada):
+    """one step of the controller on the real clips' logits [n][c] (column 0 is read); one launch on the current stream"""
+    n, c = y_video.shape
+    if tuple(y_image.shape) != (n, c):
+        raise McgError("ada_update: the two discriminators' logits differ in shape")
+    _check(load().mcg_ada_update(n, c, _p(_dense(y_video)), _p(_dense(y_image)), target, step, interval, _ada_block(ada, "ada_update"),
+                                 _stream()), "mcg_ada_update")
+    return ada
 
 
 def _augment(fn, name, x, c, geo, col, ws, out):

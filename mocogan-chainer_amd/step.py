@@ -63,6 +63,48 @@ def check_clip(threshold):
     return t
 
 
+ADA_DEFAULTS = {'target': 0.6, 'interval': 4, 'kimg': 500}        # Karras et al. 2020, section 3 and appendix D
+
+
+def check_ada(ada):
+    """the `ada` option of TrainStep as a dict of target / interval / kimg, or None (off): True = the paper's values, a dict
+    overrides any of them"""
+    if ada is None or ada is False:
+        return None
+    if ada is True:
+        ada = {}
+    if not isinstance(ada, dict):
+        raise ValueError("ada is True or a dict with any of 'target', 'interval', 'kimg', got %r" % (ada,))
+    unknown = sorted(set(ada) - set(ADA_DEFAULTS))
+    if unknown:
+        raise ValueError('unknown ada settings %s (known: %s)' % (unknown, ', '.join(sorted(ADA_DEFAULTS))))
+    cfg = dict(ADA_DEFAULTS, **ada)
+    target, interval, kimg = float(cfg['target']), cfg['interval'], float(cfg['kimg'])
+    if not -1.0 < target < 1.0:                                   # (a NaN fails too)
+        raise ValueError('the ada target is a mean of signs: it lies in (-1, 1), got %r' % (cfg['target'],))
+    if isinstance(interval, bool) or int(interval) != interval or interval < 1:
+        raise ValueError('the ada interval is a whole number of iterations >= 1, got %r' % (interval,))
+    if not 0.0 < kimg < math.inf:
+        raise ValueError('ada kimg (thousands of real clips in which p may cross [0, 1]) must be > 0 and finite, got %r' % (cfg['kimg'],))
+    return {'target': target, 'interval': int(interval), 'kimg': kimg}
+
+
+def check_augment_gate(augment, augment_p, ada, exchange=None):
+    """TrainStep's augment_p / ada options -> (the starting probability, or None when both are off; check_ada's dict or None)"""
+    cfg = check_ada(ada)
+    if augment_p is None and cfg is None:
+        return None, None
+    if not hl.parse_augment(augment):
+        raise ValueError('augment_p / ada set how often the augmentation is applied: they need a non-empty augment policy')
+    if exchange is not None and exchange.active:
+        raise ValueError('augment_p / ada with a gradient exchange: the ranks would need an all-reduce of the sign sums to keep '
+                         'p equal (not implemented)')
+    p0 = 0.0 if augment_p is None else float(augment_p)
+    if not 0.0 <= p0 <= 1.0:                                      # (a NaN fails too)
+        raise ValueError('augment_p lies in [0, 1], got %r' % (augment_p,))
+    return p0, cfg
+
+
 def ema_rate(decay, k):
     """r_k = 1 - d_k of the averaged generator's k-th update (k = 0, 1, ...: updates already done): d_k = min(decay, (1 + k) / (10 + k)),
     a warm-up that lets the average forget its starting point (rates 0.9, 0.82, 0.75, ... until the decay takes over).  In double,
@@ -194,8 +236,9 @@ class TrainStep:
     """Holds the three networks, their Adam hyper-parameters and runs update_core on device data."""
 
     def __init__(self, model, gen, dis_i, dis_v, hyper=None, exchange=None, seed=0, rank=0, precision=None, overlap=False, sync_bn=False,
-                 input_ready_early=False, ema_decay=None, augment=None, grad_stats=False):
+                 input_ready_early=False, ema_decay=None, augment=None, grad_stats=False, augment_p=None, ada=None):
         assert model in ('normal', 'cgan', 'infogan')
+        p0, ada_cfg = check_augment_gate(augment, augment_p, ada, exchange)      # (refused before anything is touched)
         self.model, self.gen, self.dis_i, self.dis_v = model, gen, dis_i, dis_v
         if precision is not None:                                 # 'f32' | 'bf16': MFMA operand type of every conv GEMM
             assert precision in ('f32', 'bf16', 'f32x3')
@@ -214,6 +257,16 @@ class TrainStep:
         # hl.AUG_* flags: differentiable augmentation (Zhao et al. 2020) of the real and the generated clips in front of BOTH
         # discriminators, one parameter set per clip; the generator's gradient goes back through its adjoint.  No reference counterpart.
         self.augment = hl.parse_augment(augment)
+        # augment_p, ada: both None = the draws of before (no launch, allocation, stream id or event more).  augment_p = P in [0, 1]:
+        # every component of the policy is applied to a clip with probability P (Karras et al. 2020: below about 0.8 the
+        # augmentation does not leak into the generated clips) -- hl.augment_draw_gated reads P from a state block in device memory.
+        # ada = True or {'target', 'interval', 'kimg'} (ADA_DEFAULTS): P starts at augment_p (or 0) and one launch per iteration
+        # (hl.ada_update, on the real halves of the logits the step has anyway) moves it every `interval` iterations by
+        # interval n / (1000 kimg) towards r_t = E[sign(D(real))] = target, r_t that of the discriminator that overfits more.
+        # The host never reads the block; ada_stats() does, for the log.  No reference counterpart.
+        self.ada = ada_cfg
+        self._ada = hl.ada_state(p0, gen.device) if p0 is not None else None
+        self._ev_ada = None
         self.hyper = hyper or {'image_gen': AdamHyper(), 'image_dis': AdamHyper(), 'video_dis': AdamHyper()}
         self.exchange = exchange
         # grad_stats: False = off (nothing allocated, the launches of before).  True: every network's Adam update is preceded by the
@@ -277,8 +330,9 @@ class TrainStep:
         return hl.concat_label_planes(x_dev, c, dl, labels, out)
 
     # ---- perf-mode randomness bookkeeping ----------------------------------------------------------
-    STREAMS_PER_RANK = 64        # Philox stream ids one rank may consume per iteration (uses 5 x 8, and 40 / 41 with augmentation)
+    STREAMS_PER_RANK = 64        # Philox stream ids one rank may consume per iteration (uses 5 x 8, 40 / 41 with augmentation, 42 / 43 with its gates)
     AUG_STREAM_REAL, AUG_STREAM_FAKE = 40, 41     # ... the augmentation parameters of the real / the generated clips
+    AUG_GATE_REAL, AUG_GATE_FAKE = 42, 43         # ... and, with augment_p / ada, the gates of their components
     MAX_RANKS = 64
 
     def frame_index(self, it, T):
@@ -311,7 +365,9 @@ class TrainStep:
         'augment': {'real': (geo, col), 'fake': (geo, col)} -- int32 [n][8] and float [n][4] device tensors (mcg_augment_draw's
         form); perf mode draws them in-kernel on stream ids base + 40 / 41.  The result then also holds 'x_real_aug', 'x_fake_aug'
         (what the discriminators saw, without label planes), 'gx_aug' (the gradient w.r.t. x_fake_aug) and 'augment' (the
-        parameters); 'x_fake' / 'gx_fake' stay the un-augmented clip and the gradient w.r.t. it."""
+        parameters); 'x_fake' / 'gx_fake' stay the un-augmented clip and the gradient w.r.t. it.
+        With augment_p / ada, perf mode draws the gates on stream ids base + 42 / 43 (geo[:, 6] then says what was applied); parity
+        mode takes inject['augment'] as it is -- the caller gates it -- and the controller's update runs all the same."""
         gen, di, dv = self.gen, self.dis_i, self.dis_v
         u8 = x_real.dtype == torch.uint8
         if u8:
@@ -345,10 +401,13 @@ class TrainStep:
             else:
                 aug_par = dict(inject['augment'])
 
-        def augmented(x, which, sid):
+        def augmented(x, which, sid, gate_sid):
             """x [n][T][H][W][4] -> its augmented copy with the parameters of `which` ('real' | 'fake'), on the current stream"""
             if which not in aug_par:
-                aug_par[which] = hl.augment_draw(n, H, W, aug, seed, base + sid, device=self.device)
+                if self._ada is not None:
+                    aug_par[which] = hl.augment_draw_gated(n, H, W, aug, seed, base + sid, base + gate_sid, self._ada, device=self.device)
+                else:
+                    aug_par[which] = hl.augment_draw(n, H, W, aug, seed, base + sid, device=self.device)
             geo, col = aug_par[which]
             return hl.augment_fwd(x, c_img, geo, col, hl.augment_workspace(n, self.device), torch.empty_like(x))
 
@@ -363,7 +422,7 @@ class TrainStep:
                 tmp = torch.empty((n, T, H, W, lay.pad4(c_img)), device=self.device)
                 (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, lay.pad4(c_img), T, hw, x_real, tmp)
                 if aug:
-                    tmp = augmented(tmp, 'real', self.AUG_STREAM_REAL)
+                    tmp = augmented(tmp, 'real', self.AUG_STREAM_REAL, self.AUG_GATE_REAL)
                 real['aug'] = tmp if aug else None
                 real['x'] = self._concat_label_clip(tmp, t_real) if cgan else tmp
             c_valid_r = c_img + (gen.dim_zl if cgan else 0)
@@ -396,6 +455,8 @@ class TrainStep:
             cs = self._chain_stream
             if (self.input_ready_early or input_event is not None) and self._ev_dv_updated is not None and not cgan:
                 cs.wait_event(self._ev_dv_updated)                   # the previous iteration's Adam(D_V)
+                if self._ev_ada is not None:
+                    cs.wait_event(self._ev_ada)                      # ... and its controller step: the gates below read the p it left
                 if input_event is not None:
                     cs.wait_event(input_event)                       # x_real (otherwise ready by contract)
             else:
@@ -422,7 +483,7 @@ class TrainStep:
         t_fake = draw['labels']
         if cgan or aug:
             x_real_aug = real['aug']
-        x_fake_aug = augmented(x_fake, 'fake', self.AUG_STREAM_FAKE) if aug else None
+        x_fake_aug = augmented(x_fake, 'fake', self.AUG_STREAM_FAKE, self.AUG_GATE_FAKE) if aug else None
         xf = x_fake_aug if aug else x_fake
         if cgan:
             xf = self._concat_label_clip(xf, t_fake)
@@ -507,6 +568,15 @@ class TrainStep:
                 self._ev_dv_updated = torch.cuda.Event()
             self._ev_dv_updated.record(main)
         main.wait_stream(side)                                        # D_I's logits and updated weights (Q5)
+        if self.ada is not None:
+            # the controller's step, where both discriminators' real logits are visible; every draw of this iteration is behind it
+            # (the chain stream's through main.wait_event above), the next iteration's follow in stream order or wait for the event
+            cfg = self.ada
+            hl.ada_update(y_real_v, y_real_i, cfg['target'], cfg['interval'] * n / (cfg['kimg'] * 1000.0), cfg['interval'], self._ada)
+            if self._dv_chains is not None:
+                if self._ev_ada is None:
+                    self._ev_ada = torch.cuda.Event()
+                self._ev_ada.record(main)
         # ------------------------------------------------ image_gen_optimizer.update(loss_gen, ...)   :113
         gen.zero_grad()
         gi, gv = g_i[:n], g_v[:n]                                    # buffers reused: D's backward has consumed them
@@ -553,6 +623,30 @@ class TrainStep:
         'skipped' (updates so far), 'tensors': {parameter: norm}}} of the last iteration, for every network that keeps the
         statistics -- forces a host sync, like losses().  Norms are those of the gradient the update saw (the mean over the ranks)."""
         return {name: net.gstats.read() for name, net in self._nets.items() if net.gstats is not None}
+
+    def ada_state(self):
+        """the eight doubles of the augmentation's state block (hl.ADA_*) as a float64 array, or None without augment_p / ada --
+        forces a host sync"""
+        return None if self._ada is None else self._ada.cpu().numpy()
+
+    def load_ada_state(self, values):
+        """ada_state()'s array back into the block (a resumed run); the host waits for the copy"""
+        if self._ada is None:
+            raise ValueError('this step has no augmentation state: augment_p / ada are off')
+        v = torch.as_tensor(values, dtype=torch.float64).reshape(-1)
+        if v.numel() != hl.ADA_DOUBLES:
+            raise ValueError('the augmentation state is %d doubles, got %d' % (hl.ADA_DOUBLES, v.numel()))
+        self._ada.copy_(v)
+        torch.cuda.synchronize(self.device)
+
+    def ada_stats(self):
+        """{'p', 'rt_video', 'rt_image' (r_t = E[sign(D(real))] at the last adjustment), 'adjustments'} of the augmentation's state
+        block -- forces a host sync, like losses()"""
+        st = self.ada_state()
+        if st is None:
+            raise ValueError('this step has no augmentation state: augment_p / ada are off')
+        return {'p': float(st[hl.ADA_P]), 'rt_video': float(st[hl.ADA_RT_V]), 'rt_image': float(st[hl.ADA_RT_I]),
+                'adjustments': int(st[hl.ADA_ADJUSTMENTS])}
 
     def losses(self):
         """(loss_dis_i, loss_dis_v, loss_gen) of the last iteration -- forces a host sync."""

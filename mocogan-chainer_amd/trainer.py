@@ -593,6 +593,10 @@ class Trainer:
                 for k, v in ema.export_reference_params().items():
                     d['updater/ema:%s/%s' % (name, k)] = v
                 d['updater/ema:%s/k' % name] = np.asarray(ema.k)
+        ada_state = getattr(getattr(u, '_step', None), 'ada_state', None)   # the adaptive augmentation's state block (no Chainer counterpart)
+        ada = ada_state() if ada_state is not None else None
+        if ada is not None:
+            d['updater/ada/state'] = np.asarray(ada, np.float64)
         return d
 
     def load_state(self, d):
@@ -633,6 +637,9 @@ class Trainer:
                     ema.k = int(d[epre + 'k'])
                 else:                                               # a snapshot of a run without averaging: start from what it holds
                     ema.reset_from(link.impl)
+        ada_state = getattr(getattr(u, '_step', None), 'ada_state', None)
+        if ada_state is not None and ada_state() is not None and 'updater/ada/state' in d:
+            u._step.load_ada_state(d['updater/ada/state'])          # (a snapshot without the key: p starts where the flags put it)
 
 
 class extensions:

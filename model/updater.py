@@ -40,15 +40,21 @@ class Updater:
         # False: off; True: per-network gradient norms from the device, reported with the losses at every new epoch (a
         # GradientClipping hook on an optimizer switches them on for its network either way; they are reported only with this)
         self._grad_stats = bool(kwargs.pop('grad_stats', False))
+        # augment_p: None, or P in [0, 1]: every component of the policy is applied to a clip with probability P; ada: None, True or
+        # {'target', 'interval', 'kimg'}: P follows the discriminators' overfitting signal r_t = E[sign(D(real))] (Karras et al.
+        # 2020); P and the two r_t are reported with the losses at every new epoch.  Both need `augment` (step.check_augment_gate)
+        augment_p = kwargs.pop('augment_p', None)
+        ada = kwargs.pop('ada', None)
         if kwargs:
             raise TypeError('unexpected arguments: %s' % sorted(kwargs))
+        self._ada_report = _step.check_augment_gate(augment, augment_p, ada, exchange)[0] is not None
         self.iteration = 0
         self.observation = {}
         hyper = {k: self._optimizers[k].hyper() for k in ('image_gen', 'image_dis', 'video_dis')}
         self._step = _step.TrainStep(self.model, self.image_gen.impl, self.image_dis.impl, self.video_dis.impl,
                                      hyper=hyper, exchange=exchange, seed=seed, rank=rank, overlap=overlap,
                                      precision=precision, sync_bn=sync_bn, ema_decay=ema_decay, augment=augment,
-                                     grad_stats=self._grad_stats)
+                                     grad_stats=self._grad_stats, augment_p=augment_p, ada=ada)
 
     # ---- StandardUpdater surface -------------------------------------------------------------------
     def get_optimizer(self, name):
@@ -176,6 +182,13 @@ class Updater:
             self.observation = dict(l)
             for name, link in self.links().items():
                 self.tf_writer.add_scalar('loss:{}'.format(link.name), l['%s/loss' % name], self.epoch)
+            if self._ada_report:
+                st = self._step.ada_stats()
+                for key, tag, v in (('augment/p', 'augment:p', st['p']),
+                                    ('video_dis/rt', 'rt:{}'.format(self.video_dis.name), st['rt_video']),
+                                    ('image_dis/rt', 'rt:{}'.format(self.image_dis.name), st['rt_image'])):
+                    self.observation[key] = float(v)
+                    self.tf_writer.add_scalar(tag, float(v), self.epoch)
             if self._grad_stats:
                 for name, st in self._step.grad_stats().items():
                     for key in ('grad_norm', 'grad_norm_peak', 'clip_rate', 'skipped'):

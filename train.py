@@ -79,6 +79,18 @@ def parse_args(argv=None):
                    help="'' (default): off.  A comma-separated subset of color,translation,cutout: differentiable augmentation (Zhao et "
                         "al. 2020) of the real and the generated clips in front of both discriminators, one random parameter set per "
                         "clip; the generator's gradient is carried back through it")
+    p.add_argument('--augment_p', type=float, default=None,
+                   help="with --augment: apply each of its components to a clip with this probability in [0, 1] instead of always "
+                        "(Karras et al. 2020: below about 0.8 the augmentation does not leak into the generated clips); with "
+                        "--ada_target the probability the run starts from (default 0)")
+    p.add_argument('--ada_target', type=float, default=None,
+                   help="with --augment: adapt that probability during the run -- every --ada_interval iterations it moves towards "
+                        "r_t = E[sign(D(real))] = this target in (-1, 1), r_t that of the discriminator that overfits more (Karras "
+                        "et al. 2020 use 0.6).  No default: giving it switches the adaptation on")
+    p.add_argument('--ada_interval', type=int, default=4, help="iterations between two adjustments of the probability")
+    p.add_argument('--ada_kimg', type=float, default=500.0,
+                   help="thousands of real clips in which the probability can cross [0, 1]: an adjustment moves it by "
+                        "ada_interval * batchsize / (1000 * ada_kimg)")
     p.add_argument('--grad_clip', type=float, default=0.0,
                    help="0 (default): off.  T > 0: a GradientClipping(T) hook on all three optimizers -- each network's gradient is "
                         "scaled to an L2 norm of at most T (taken on the device, no host sync), and an update whose gradient holds "
@@ -96,7 +108,19 @@ def parse_args(argv=None):
         parse_augment(args.augment)
     except ValueError as e:
         p.error('--augment: %s' % e)
+    try:
+        from mocogan_chainer_amd.step import check_augment_gate
+        check_augment_gate(args.augment, args.augment_p, ada_option(args))
+    except ValueError as e:
+        p.error('--augment_p / --ada_*: %s' % e)
     return args
+
+
+def ada_option(args):
+    """the Updater's `ada` option from the flags: None without --ada_target"""
+    if args.ada_target is None:
+        return None
+    return {'target': args.ada_target, 'interval': args.ada_interval, 'kimg': args.ada_kimg}
 
 
 def main(argv=None):
@@ -183,7 +207,7 @@ def main(argv=None):
                       tensorboard_writer=writer, optimizer=opts, device=args.gpu, seed=args.seed, exchange=exchange, rank=rank,
                       overlap=bool(args.overlap), precision=args.mfma, sync_bn=bool(args.sync_bn),
                       ema_decay=args.ema_decay if args.ema_decay > 0 else None, augment=args.augment or None,
-                      grad_stats=bool(args.grad_stats))
+                      grad_stats=bool(args.grad_stats), augment_p=args.augment_p, ada=ada_option(args))
 
     save_path = Path('result') / args.save_name
     trainer = T.Trainer(updater, (args.max_epoch, 'epoch'), out=save_path)
