@@ -132,7 +132,8 @@ typedef struct mcg_conv_geom {
  *     and with the differentiable augmentation (mcg_augment_* added; no argument list changed)
  *     and with the sliced Wasserstein distance (mcg_swd_*, mcg_sort_* added; no argument list changed)
  *     and with the gradient statistics (mcg_grad_stats*, mcg_adam_wd_ctl added; no argument list changed)
- *     and with the adaptive augmentation (mcg_augment_draw_gated, mcg_ada_update added; no argument list changed). */
+ *     and with the adaptive augmentation (mcg_augment_draw_gated, mcg_ada_update added; no argument list changed)
+ *     and with the geometric augmentation (mcg_warp_* added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -433,6 +434,59 @@ int mcg_augment_draw_gated(int N, int H, int W, int policy, uint64_t seed, uint6
  * negative or NaN, target NaN or outside (-1, 1). */
 int mcg_ada_update(int N, int C, const float* y_video, const float* y_image, double target, double step, int interval, double* ada,
                    void* stream);
+
+/* ---- geometric augmentation: a per-clip affine warp with bilinear taps --------------------------------------------------------
+ * Karras et al. 2020, section 2.3 and figure 4: x-flip, quarter turns, isotropic scaling and arbitrary rotation (no reference
+ * counterpart).  A clip is x[n][T][H][W][Cp], Cp = 4, as mcg_augment_fwd takes it; all four lanes are warped alike, so a zero pad
+ * channel stays exactly +0.0.  Clip n has ONE matrix for all its frames (motion is untouched):
+ *   mat[n] = (m00, m01, m02, m10, m11, m12, flags, 0)      float; it maps an OUTPUT position to its SOURCE
+ * flags is the float value of the MCG_WARP_* components that were applied (the draws below write it; mcg_warp_fwd / mcg_warp_bwd
+ * read words 0..5 only).  With cx = (W-1)/2, cy = (H-1)/2, xc = x - cx, yc = y - cy, every operation rounded to fp32 on its own
+ * (never contracted into an FMA, so that a NumPy float32 statement gives the same bits):
+ *   sx = ((m00*xc) + (m01*yc)) + (cx + m02)        sy = ((m10*xc) + (m11*yc)) + (cy + m12)
+ * sx and sy are clamped to [-2, W + 1] and [-2, H + 1] before anything is converted to an integer (a NaN becomes -2; a clamped
+ * source has no tap inside the frame, as it had none before), then x0 = floor(sx), fx = sx - x0 (exact), likewise y0 and fy.
+ *   out(t, y, x) = sum over the four taps (y0 + j, x0 + i), i, j in {0, 1}, of w_i(fx) w_j(fy) in(t, y0 + j, x0 + i),
+ *   w_0(f) = 1 - f, w_1(f) = f; a tap outside the frame contributes 0 (zero padding, as the translation of mcg_augment_fwd has it),
+ *   and a tap of weight 0 is not read.
+ * Reflection padding and the wavelet low-pass filters of the paper's implementation are NOT here: a magnifying warp interpolates,
+ * a reducing one aliases, and the border is zero.  Any matrix of finite entries is safe -- all-zero, singular, 1e6-scale: no
+ * address outside the clip is formed.  The identity (1, 0, 0, 0, 1, 0) returns the input bit for bit, and a matrix of entries 0
+ * and +-1 with zero offsets (a flip; a quarter turn when H == W) returns an exact permutation: fx = fy = 0, weights exactly 1 and 0.
+ *
+ * mcg_warp_bwd is the exact adjoint, computed as a GATHER: g_in(t, v, u) = sum over the output pixels (y, x) that have (v, u)
+ * among their taps of that tap's weight times g_out(t, y, x).  No float atomics, the candidates are visited in row-major order:
+ * two runs give the same bits.  The candidates of (v, u) are the output pixels of a bounding box -- the image of the square
+ * (u-1, u+1) x (v-1, v+1) under the 2x2 inverse of the linear part, widened by a pixel, clamped to the frame; the whole frame when
+ * the determinant is zero, the inverse is not finite or fp32 rounding of sx, sy could matter at that scale -- and for every
+ * candidate x0, fx, y0, fy are recomputed by the same code as in the forward pass.  A degenerate matrix is slow, never wrong.
+ * One launch each.  MCG_ERR_BAD_ARG: a null pointer, a non-positive extent, C outside 1..Cp, in == out (a gather cannot run in
+ * place); MCG_ERR_UNSUPPORTED: Cp != 4 (or T*H*W > 2^28, N > 65535, as mcg_augment_fwd). */
+enum { MCG_WARP_FLIP = 1, MCG_WARP_ROT90 = 2, MCG_WARP_SCALE = 4, MCG_WARP_ROTATE = 8 };
+int mcg_warp_fwd(int N, int C, int Cp, int T, int H, int W, const float* in, const float* mat, float* out, void* stream);
+int mcg_warp_bwd(int N, int C, int Cp, int T, int H, int W, const float* g_out, const float* mat, float* g_in, void* stream);
+/* The matrices of N clips from Philox4x32-10 keyed by (seed, stream_id): clip i takes counter i, the words w0..w3, and with
+ * u(w) = (w >> 9) * 2^-23 as in mcg_augment_draw, everything in fp32 with separately rounded + - * / and no transcendental:
+ *   flip          f = (w0 & 1) ? -1 : 1
+ *   quarter turn  k = w1 & 3, Q_k = Q_1^k, Q_1 = [[0, -1], [1, 0]]
+ *   scale         a = (2 u(w2) - 1) / 6, s = (1 + a) / (1 - a): s in (5/7, 7/5), symmetric in the logarithm
+ *   rotation      t = 2 u(w3) - 1, c = (1 - t t) / (1 + t t), sn = (2 t) / (1 + t t): the angle 2 atan t in [-90, 90) degrees.  With
+ *                 the quarter turn it covers the whole circle; t is uniform, so the angle's density falls by half from the centre
+ *                 (angle 0) to the ends (+-90 degrees) -- it is NOT uniform in the angle.
+ *   L = (1 / s) [[c, sn], [-sn, c]] Q_k diag(f, 1):  r = 1 / s (one division), the four products r c, r sn, -(r sn), r c (one
+ *   rounding each), then the column permutation and signs of Q_k and the sign f on column 0 (exact); a -0 is stored as +0.
+ *   m00 m01 m10 m11 = L, m02 = m12 = 0, flags = 0, word 7 = 0.
+ * policy: a set of MCG_WARP_* flags; a component that is off takes its identity value (f = 1, k = 0, s = 1, c = 1, sn = 0) and its
+ * word is consumed all the same.  MCG_ERR_BAD_ARG: a null mat, a non-positive extent, a policy outside 0..15;
+ * MCG_ERR_UNSUPPORTED: MCG_WARP_ROT90 with H != W (the turned frame would not cover the frame). */
+int mcg_warp_draw(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, float* mat, void* stream);
+/* mcg_warp_draw with each component kept with probability p = ada[0] (the state block of mcg_ada_update; read, never written):
+ * clip i also takes counter i of (seed, gate_stream_id), words g0..g3, and flip is kept iff (double)u(g0) < p, the quarter turn iff
+ * (double)u(g1) < p, scale iff (double)u(g2) < p, rotation iff (double)u(g3) < p.  A component that fails takes its identity value;
+ * flags = the components that are in the policy and passed.  p = 0 gives identity matrices, p >= 1 mcg_warp_draw's bits except
+ * flags.  MCG_ERR_BAD_ARG: what mcg_warp_draw refuses with it, a null ada, gate_stream_id == stream_id. */
+int mcg_warp_draw_gated(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, uint64_t gate_stream_id,
+                        const double* ada, float* mat, void* stream);
 
 /* ---- GRU motion-code recurrence (L.StatelessGRU, model/net.py:39-41,61-81) ------------------ */
 /* params: the six Linear links packed as [W_r|U_r|W_z|U_z|W|U], each (weights row-major

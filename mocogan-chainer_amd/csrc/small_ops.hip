@@ -1694,6 +1694,226 @@ int augment_apply_blocks(int N, long long P) {
     return (int)(b > cap ? cap : b);
 }
 
+// ------------------------------------------------------------------------------------------
+// Geometric augmentation (Karras et al. 2020, the x-flip / quarter-turn / isotropic-scale / rotation family; no reference
+// counterpart): a per-clip affine warp with bilinear taps and zero padding, the same matrix for every frame of a clip.
+// mat[8] = m00 m01 m02 m10 m11 m12 flags 0 maps an OUTPUT position to its SOURCE (include/mocogan_hip.h states the arithmetic).
+// Forward and backward take the source of an output pixel from ONE function, warp_source, whose operations are rounded one by
+// one (no contraction into FMAs): the weights of a tap are then the same floats in both directions, and the backward pass -- a
+// gather over a conservative box of output pixels, no atomics, fixed order -- is the exact adjoint.
+// ------------------------------------------------------------------------------------------
+// One rounding per operation: the compiler contracts a * b + c into an FMA by default, and its __fmul_rn / __fadd_rn are plain
+// operators compiled under that default, so they fuse as well once inlined.  These four carry the pragma themselves.
+__device__ __forceinline__ float warp_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float warp_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float warp_sub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ float warp_div(float a, float b) {
+#pragma clang fp contract(off)
+    return a / b;
+}
+struct WarpMat { float m00, m01, m02, m10, m11, m12, cx, cy, xmax, ymax; };
+__device__ __forceinline__ WarpMat warp_mat(const float* __restrict__ mat, int n, int H, int W) {
+    const float* q = mat + 8 * (long long)n;
+    WarpMat m = {q[0], q[1], q[2], q[3], q[4], q[5], (float)(W - 1) * 0.5f, (float)(H - 1) * 0.5f, (float)(W + 1), (float)(H + 1)};
+    return m;
+}
+// (x0, y0) = floor of the source of output pixel (y, x), (fx, fy) = its fraction -- exact.  The source is clamped to [-2, extent + 1]
+// BEFORE the conversion (fmaxf drops a NaN): a clamped source has no tap inside the frame, as the unclamped one had none.
+struct WarpSrc { int x0, y0; float fx, fy; };
+__device__ __forceinline__ WarpSrc warp_source(const WarpMat& m, int y, int x) {
+    const float xc = warp_sub((float)x, m.cx), yc = warp_sub((float)y, m.cy);
+    float sx = warp_add(warp_add(warp_mul(m.m00, xc), warp_mul(m.m01, yc)), warp_add(m.cx, m.m02));
+    float sy = warp_add(warp_add(warp_mul(m.m10, xc), warp_mul(m.m11, yc)), warp_add(m.cy, m.m12));
+    sx = fminf(fmaxf(sx, -2.f), m.xmax);
+    sy = fminf(fmaxf(sy, -2.f), m.ymax);
+    const float flx = floorf(sx), fly = floorf(sy);
+    WarpSrc s = {(int)flx, (int)fly, warp_sub(sx, flx), warp_sub(sy, fly)};
+    return s;
+}
+// the weight of tap (y0 + iy, x0 + ix), ix, iy in {0, 1}
+__device__ __forceinline__ float warp_weight(const WarpSrc& s, int iy, int ix) {
+    return warp_mul(ix ? s.fx : warp_sub(1.f, s.fx), iy ? s.fy : warp_sub(1.f, s.fy));
+}
+
+__global__ __launch_bounds__(NT) void warp_fwd_kernel(int P, int H, int W, const float* __restrict__ in, const float* __restrict__ mat,
+                                                      float* __restrict__ out) {
+    const int n = blockIdx.y;
+    const float* clip = in + (long long)n * P * 4;
+    float* oclip = out + (long long)n * P * 4;
+    const WarpMat m = warp_mat(mat, n, H, W);
+    for (int p = blockIdx.x * NT + threadIdx.x; p < P; p += gridDim.x * NT) {
+        const int x = p % W, q = p / W, y = q % H, t = q / H;
+        const WarpSrc s = warp_source(m, y, x);
+        f32x4 o = {};
+#pragma unroll
+        for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+            for (int ix = 0; ix < 2; ++ix) {
+                const int yy = s.y0 + iy, xx = s.x0 + ix;
+                const float w = warp_weight(s, iy, ix);
+                // (the tap is tested before its address is formed: it then lies in frame t of this clip; a tap of weight 0 is not read)
+                if (w != 0.f && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(clip + ((long long)(t * H + yy) * W + xx) * 4);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = fmaf(w, v[k], o[k]);
+                }
+            }
+        *reinterpret_cast<f32x4*>(oclip + (long long)p * 4) = o;
+    }
+}
+
+// The output pixels whose source can touch source pixel (v, u): the image of the open square (u - 1, u + 1) x (v - 1, v + 1) under
+// the inverse of the linear part, widened by a pixel, clamped to the frame.  The inverse is formed in double (the products of two
+// floats are exact there).  The whole frame is taken when the determinant is zero, the inverse is not finite, or the rounding of
+// warp_source (bounded by 2^-21 of the magnitudes it adds) could move a source by half a pixel of the OUTPUT once mapped back.
+struct WarpInv { double i00, i01, i10, i11, ex, ey, ox, oy; bool whole; };
+__device__ __forceinline__ WarpInv warp_inverse(const WarpMat& m, int H, int W) {
+    const double a = m.m00, b = m.m01, c = m.m10, d = m.m11;
+    const double det = a * d - b * c, r = 1.0 / det;
+    WarpInv v;
+    v.i00 = d * r; v.i01 = -b * r; v.i10 = -c * r; v.i11 = a * r;
+    v.ex = fabs(v.i00) + fabs(v.i01); v.ey = fabs(v.i10) + fabs(v.i11);
+    v.ox = (double)m.cx + (double)m.m02; v.oy = (double)m.cy + (double)m.m12;
+    const double mag = (fabs(a) + fabs(b) + fabs(c) + fabs(d)) * (double)(H + W) + fabs(v.ox) + fabs(v.oy);
+    const double slack = (v.ex + v.ey) * mag * 4.76837158203125e-07;           // 2^-21
+    v.whole = !(fabs(det) > 0.0) || !(slack < 0.5);                            // (a NaN or an infinity fails the second test)
+    return v;
+}
+struct WarpBox { int x_lo, x_hi, y_lo, y_hi; };
+__device__ __forceinline__ WarpBox warp_box(const WarpMat& m, const WarpInv& v, int vy, int ux, int H, int W) {
+    WarpBox bx = {0, W - 1, 0, H - 1};
+    if (!v.whole) {
+        const double du = (double)ux - v.ox, dv = (double)vy - v.oy;
+        const double xo = (double)m.cx + (v.i00 * du + v.i01 * dv), yo = (double)m.cy + (v.i10 * du + v.i11 * dv);
+        // (clamped as doubles, then converted: the values are inside the frame; an empty box has lo > hi)
+        bx.x_lo = (int)fmin(fmax(floor(xo - v.ex - 1.0), 0.0), (double)W);
+        bx.x_hi = (int)fmin(fmax(ceil(xo + v.ex + 1.0), -1.0), (double)(W - 1));
+        bx.y_lo = (int)fmin(fmax(floor(yo - v.ey - 1.0), 0.0), (double)H);
+        bx.y_hi = (int)fmin(fmax(ceil(yo + v.ey + 1.0), -1.0), (double)(H - 1));
+    }
+    return bx;
+}
+
+// One thread per source pixel (v, u) and group of WARP_TC frames: the candidates and their weights are those of every frame of the
+// clip, so the search is paid once per group.  Candidates in row-major order, frames innermost: the order of the sum is fixed.
+// g_out is gathered through L2; a block per (frame, clip) that staged the frame in LDS first measured 2.6 x (32 clips) and
+// 1.9 x (256 clips) slower (profiles/warp_notes.md) and is not kept.
+constexpr int WARP_TC = 4;
+__global__ __launch_bounds__(NT) void warp_bwd_kernel(int T, int H, int W, const float* __restrict__ g_out, const float* __restrict__ mat,
+                                                      float* __restrict__ g_in) {
+    const int n = blockIdx.y, HW = H * W;
+    const long long P = (long long)T * HW;
+    const float* clip = g_out + (long long)n * P * 4;
+    float* oclip = g_in + (long long)n * P * 4;
+    const WarpMat m = warp_mat(mat, n, H, W);
+    const WarpInv inv = warp_inverse(m, H, W);
+    const int total = HW * ((T + WARP_TC - 1) / WARP_TC);
+    for (int q = blockIdx.x * NT + threadIdx.x; q < total; q += gridDim.x * NT) {
+        const int pix = q % HW, t0 = (q / HW) * WARP_TC, u = pix % W, v = pix / W;
+        const int nt = T - t0 < WARP_TC ? T - t0 : WARP_TC;
+        const WarpBox bx = warp_box(m, inv, v, u, H, W);
+        f32x4 acc[WARP_TC] = {};
+        for (int y = bx.y_lo; y <= bx.y_hi; ++y)
+            for (int x = bx.x_lo; x <= bx.x_hi; ++x) {
+                const WarpSrc s = warp_source(m, y, x);
+                const int ix = u - s.x0, iy = v - s.y0;
+                if ((unsigned)ix > 1u || (unsigned)iy > 1u) continue;
+                const float w = warp_weight(s, iy, ix);
+                if (w == 0.f) continue;
+                const float* g = clip + ((long long)(t0 * H + y) * W + x) * 4;           // (y, x) lies in the frame: the box is clamped
+#pragma unroll
+                for (int k = 0; k < WARP_TC; ++k)
+                    if (k < nt) {
+                        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + (long long)k * HW * 4);
+#pragma unroll
+                        for (int l = 0; l < 4; ++l) acc[k][l] = fmaf(w, gv[l], acc[k][l]);
+                    }
+            }
+#pragma unroll
+        for (int k = 0; k < WARP_TC; ++k)
+            if (k < nt) *reinterpret_cast<f32x4*>(oclip + ((long long)(t0 + k) * HW + pix) * 4) = acc[k];
+    }
+}
+
+// Clip i: Philox counter i of the stream, words w0..w3 -> flip, quarter turn, scale, rotation; a component the policy leaves out
+// takes its identity value, its word is consumed all the same.  fp32, every + - * / rounded on its own, no transcendental:
+// L = (1 / s) [[c, sn], [-sn, c]] Q_k diag(f, 1) -- one division, four products by 1 / s, then signs and a permutation (exact).
+struct WarpDraw { float m00, m01, m10, m11; };
+__device__ __forceinline__ float warp_pos_zero(float v) { return v == 0.f ? 0.f : v; }              // (-0 -> +0)
+__device__ __forceinline__ WarpDraw warp_draw_clip(int i, int policy, uint64_t seed, uint64_t stream_id) {
+    uint32_t w[4];
+    aug_philox((uint64_t)i, seed, stream_id, w);
+    float f = 1.f, s = 1.f, c = 1.f, sn = 0.f;
+    int k = 0;
+    if (policy & MCG_WARP_FLIP) f = (w[0] & 1u) ? -1.f : 1.f;
+    if (policy & MCG_WARP_ROT90) k = (int)(w[1] & 3u);
+    if (policy & MCG_WARP_SCALE) {
+        const float a = warp_div(warp_sub(warp_mul(2.f, aug_unit(w[2])), 1.f), 6.f);
+        s = warp_div(warp_add(1.f, a), warp_sub(1.f, a));
+    }
+    if (policy & MCG_WARP_ROTATE) {
+        const float t = warp_sub(warp_mul(2.f, aug_unit(w[3])), 1.f), tt = warp_mul(t, t), den = warp_add(1.f, tt);
+        c = warp_div(warp_sub(1.f, tt), den);
+        sn = warp_div(warp_mul(2.f, t), den);
+    }
+    const float r = warp_div(1.f, s), rc = warp_mul(r, c), rs = warp_mul(r, sn);
+    float a00 = rc, a01 = rs, a10 = -rs, a11 = rc;                       // (1 / s) R
+    for (int j = 0; j < k; ++j) {                                        // times Q_1 = [[0, -1], [1, 0]], k times
+        const float b00 = a01, b01 = -a00, b10 = a11, b11 = -a10;
+        a00 = b00; a01 = b01; a10 = b10; a11 = b11;
+    }
+    WarpDraw d = {warp_pos_zero(warp_mul(f, a00)), warp_pos_zero(a01), warp_pos_zero(warp_mul(f, a10)), warp_pos_zero(a11)};
+    return d;
+}
+// (word 6: the components that were applied, as a float -- 0 from the plain draw, the flags that passed from the gated one)
+__device__ __forceinline__ void warp_store(const WarpDraw& d, int applied, int i, float* __restrict__ mat) {
+    float* q = mat + 8 * (long long)i;
+    q[0] = d.m00; q[1] = d.m01; q[2] = 0.f; q[3] = d.m10; q[4] = d.m11; q[5] = 0.f; q[6] = (float)applied; q[7] = 0.f;
+}
+__global__ __launch_bounds__(NT) void warp_draw_kernel(int N, int policy, uint64_t seed, uint64_t stream_id, float* __restrict__ mat) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= N) return;
+    warp_store(warp_draw_clip(i, policy, seed, stream_id), 0, i, mat);
+}
+// the gates of augment_draw_gated_kernel: flip, quarter turn, scale, rotation pass iff u(g0), u(g1), u(g2), u(g3) < p = ada[0]
+__global__ __launch_bounds__(NT) void warp_draw_gated_kernel(int N, int policy, uint64_t seed, uint64_t stream_id, uint64_t gate_stream_id,
+                                                             const double* __restrict__ ada, float* __restrict__ mat) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= N) return;
+    const double p = ada[0];
+    uint32_t g[4];
+    aug_philox((uint64_t)i, seed, gate_stream_id, g);
+    int pass = 0;
+    if ((double)aug_unit(g[0]) < p) pass |= MCG_WARP_FLIP;
+    if ((double)aug_unit(g[1]) < p) pass |= MCG_WARP_ROT90;
+    if ((double)aug_unit(g[2]) < p) pass |= MCG_WARP_SCALE;
+    if ((double)aug_unit(g[3]) < p) pass |= MCG_WARP_ROTATE;
+    const int applied = policy & pass;
+    warp_store(warp_draw_clip(i, applied, seed, stream_id), applied, i, mat);
+}
+
+int check_warp(int N, int C, int Cp, int T, int H, int W, const void* in, const void* mat, const void* out) {
+    if (!in || !mat || !out || N <= 0 || T <= 0 || H <= 0 || W <= 0 || C < 1 || C > Cp) return MCG_ERR_BAD_ARG;
+    if (in == out) return MCG_ERR_BAD_ARG;                                     // a gather: never in place
+    if (Cp != 4) return MCG_ERR_UNSUPPORTED;
+    if ((long long)T * H * W > (1LL << 28) || N > 65535) return MCG_ERR_UNSUPPORTED;     // mcg_augment_fwd's extents
+    return MCG_OK;
+}
+int check_warp_draw(int N, int H, int W, int policy, const void* mat) {
+    if (!mat || N <= 0 || H <= 0 || W <= 0 || policy < 0 || policy > 15) return MCG_ERR_BAD_ARG;
+    if ((policy & MCG_WARP_ROT90) && H != W) return MCG_ERR_UNSUPPORTED;       // a quarter turn maps the frame onto itself only when square
+    return MCG_OK;
+}
+
 }  // namespace
 
 extern "C" int mcg_version(void) { return MCG_ABI_VERSION; }
@@ -2191,5 +2411,34 @@ extern "C" int mcg_augment_bwd(int N, int C, int Cp, int T, int H, int W, const 
                        (double*)workspace);
     hipLaunchKernelGGL(augment_bwd_apply_kernel, dim3(augment_apply_blocks(N, P), N), dim3(NT), 0, (hipStream_t)stream, C, P, H, W, pl.blocks,
                        1.0 / ((double)P * C), g_out, geo, col, (const double*)workspace, g_in);
+    return launch_status();
+}
+
+extern "C" int mcg_warp_fwd(int N, int C, int Cp, int T, int H, int W, const float* in, const float* mat, float* out, void* stream) {
+    if (int e = check_warp(N, C, Cp, T, H, W, in, mat, out)) return e;
+    const int P = T * H * W;
+    hipLaunchKernelGGL(warp_fwd_kernel, dim3(augment_apply_blocks(N, P), N), dim3(NT), 0, (hipStream_t)stream, P, H, W, in, mat, out);
+    return launch_status();
+}
+
+extern "C" int mcg_warp_bwd(int N, int C, int Cp, int T, int H, int W, const float* g_out, const float* mat, float* g_in, void* stream) {
+    if (int e = check_warp(N, C, Cp, T, H, W, g_out, mat, g_in)) return e;
+    const long long work = (long long)H * W * ((T + WARP_TC - 1) / WARP_TC);
+    hipLaunchKernelGGL(warp_bwd_kernel, dim3(augment_apply_blocks(N, work), N), dim3(NT), 0, (hipStream_t)stream, T, H, W, g_out, mat, g_in);
+    return launch_status();
+}
+
+extern "C" int mcg_warp_draw(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, float* mat, void* stream) {
+    if (int e = check_warp_draw(N, H, W, policy, mat)) return e;
+    hipLaunchKernelGGL(warp_draw_kernel, dim3((N + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, N, policy, seed, stream_id, mat);
+    return launch_status();
+}
+
+extern "C" int mcg_warp_draw_gated(int N, int H, int W, int policy, uint64_t seed, uint64_t stream_id, uint64_t gate_stream_id,
+                                   const double* ada, float* mat, void* stream) {
+    if (!ada || gate_stream_id == stream_id) return MCG_ERR_BAD_ARG;
+    if (int e = check_warp_draw(N, H, W, policy, mat)) return e;
+    hipLaunchKernelGGL(warp_draw_gated_kernel, dim3((N + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, N, policy, seed, stream_id,
+                       gate_stream_id, ada, mat);
     return launch_status();
 }

@@ -104,6 +104,10 @@ SIGNATURES = {
     "mcg_ada_update": (_I, [_I, _I, _P, _P, _D, _D, _I, _P, _P]),
     "mcg_augment_fwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcg_augment_bwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mcg_warp_fwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "mcg_warp_bwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "mcg_warp_draw": (_I, [_I, _I, _I, _I, _U64, _U64, _P, _P]),
+    "mcg_warp_draw_gated": (_I, [_I, _I, _I, _I, _U64, _U64, _U64, _P, _P, _P]),
     "mcg_swd_workspace_bytes": (_I64, [_I64, _I, _I]),
     "mcg_swd_pyramid": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mcg_swd_gather": (_I, [_I, _I, _I, _I, _P, _I64, _I, _I, _U64, _U64, _P, _P]),
@@ -1240,6 +1244,76 @@ def augment_fwd(x, c, geo, col, ws, out):
 def augment_bwd(g_out, c, geo, col, ws, g_in):
     """the adjoint of augment_fwd's linear part: gradient w.r.t. the augmented clips -> gradient w.r.t. the clips"""
     return _augment(load().mcg_augment_bwd, "mcg_augment_bwd", g_out, c, geo, col, ws, g_in)
+
+
+# ---- geometric augmentation: a per-clip affine warp (include/mocogan_hip.h: mcg_warp_*) -----------------------------------------
+WARP_FLIP, WARP_ROT90, WARP_SCALE, WARP_ROTATE = 1, 2, 4, 8
+WARP_NAMES = {'flip': WARP_FLIP, 'rot90': WARP_ROT90, 'scale': WARP_SCALE, 'rotate': WARP_ROTATE}
+
+
+def parse_warp(policy):
+    """'flip,rot90,scale,rotate' (any subset, any order), a mask of WARP_* flags, or None / '' / 0 (off) -> the mask (0 = off)"""
+    if policy is None:
+        return 0
+    if isinstance(policy, bool):
+        raise ValueError('a warp policy is a string of names or a mask, got %r' % (policy,))
+    if isinstance(policy, int):
+        if not 0 <= policy <= 15:
+            raise ValueError('a warp mask lies in 0..15, got %r' % (policy,))
+        return policy
+    if not isinstance(policy, str):
+        raise ValueError('a warp policy is a string of names or a mask, got %r' % (policy,))
+    mask = 0
+    for name in policy.split(','):
+        name = name.strip()
+        if not name:
+            continue
+        if name not in WARP_NAMES:
+            raise ValueError('unknown warp %r (known: %s)' % (name, ', '.join(sorted(WARP_NAMES))))
+        mask |= WARP_NAMES[name]
+    return mask
+
+
+def _warp_mat(n, mat, device, name):
+    if mat is None:
+        mat = torch.empty((n, 8), dtype=torch.float32, device=device)
+    if mat.numel() < 8 * n:
+        raise McgError("%s: the matrix tensor is smaller than the clip count" % name)
+    return mat
+
+
+def warp_draw(n, H, W, policy, seed, stream_id, mat=None, device=None):
+    """the matrices of n clips from Philox stream (seed, stream_id): float [n][8] = m00 m01 m02 m10 m11 m12 flags 0"""
+    mat = _warp_mat(n, mat, device, "warp_draw")
+    _check(load().mcg_warp_draw(n, H, W, policy, seed, stream_id, _p(_dense(mat)), _stream()), "mcg_warp_draw")
+    return mat
+
+
+def warp_draw_gated(n, H, W, policy, seed, stream_id, gate_stream_id, ada, mat=None, device=None):
+    """warp_draw with every component of the policy kept with probability ada[0] (device memory; gates from Philox stream
+    (seed, gate_stream_id)); mat[:, 6] holds the flags that were applied"""
+    mat = _warp_mat(n, mat, device, "warp_draw_gated")
+    _check(load().mcg_warp_draw_gated(n, H, W, policy, seed, stream_id, gate_stream_id, _ada_block(ada, "warp_draw_gated"),
+                                      _p(_dense(mat)), _stream()), "mcg_warp_draw_gated")
+    return mat
+
+
+def _warp(fn, name, x, c, mat, out):
+    n, T, H, W, cp = x.shape
+    if out.shape != x.shape or mat.numel() < 8 * n:
+        raise McgError("%s: a tensor is smaller than the extents passed" % name)
+    _check(fn(n, c, cp, T, H, W, _p(_dense(x)), _p(_dense(mat)), _p(_dense(out)), _stream()), name)
+    return out
+
+
+def warp_fwd(x, c, mat, out):
+    """x [n][T][H][W][4] -> out, every clip warped by its matrix (mat [n][8], output position -> source; bilinear, zero padding)"""
+    return _warp(load().mcg_warp_fwd, "mcg_warp_fwd", x, c, mat, out)
+
+
+def warp_bwd(g_out, c, mat, g_in):
+    """the adjoint of warp_fwd: gradient w.r.t. the warped clips -> gradient w.r.t. the clips (a gather: bit-reproducible)"""
+    return _warp(load().mcg_warp_bwd, "mcg_warp_bwd", g_out, c, mat, g_in)
 
 
 # ---- sliced Wasserstein distance (include/mocogan_hip.h: mcg_swd_*, mcg_sort_rows; composed by metrics.py) -------------------------

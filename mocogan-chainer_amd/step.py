@@ -89,12 +89,13 @@ def check_ada(ada):
     return {'target': target, 'interval': int(interval), 'kimg': kimg}
 
 
-def check_augment_gate(augment, augment_p, ada, exchange=None):
-    """TrainStep's augment_p / ada options -> (the starting probability, or None when both are off; check_ada's dict or None)"""
+def check_augment_gate(augment, augment_p, ada, exchange=None, warp=None):
+    """TrainStep's augment_p / ada options -> (the starting probability, or None when both are off; check_ada's dict or None).
+    They gate the components of `augment` and of `warp` alike: one of the two has to be there."""
     cfg = check_ada(ada)
     if augment_p is None and cfg is None:
         return None, None
-    if not hl.parse_augment(augment):
+    if not hl.parse_augment(augment) and not hl.parse_warp(warp):
         raise ValueError('augment_p / ada set how often the augmentation is applied: they need a non-empty augment policy')
     if exchange is not None and exchange.active:
         raise ValueError('augment_p / ada with a gradient exchange: the ranks would need an all-reduce of the sign sums to keep '
@@ -236,9 +237,9 @@ class TrainStep:
     """Holds the three networks, their Adam hyper-parameters and runs update_core on device data."""
 
     def __init__(self, model, gen, dis_i, dis_v, hyper=None, exchange=None, seed=0, rank=0, precision=None, overlap=False, sync_bn=False,
-                 input_ready_early=False, ema_decay=None, augment=None, grad_stats=False, augment_p=None, ada=None):
+                 input_ready_early=False, ema_decay=None, augment=None, grad_stats=False, augment_p=None, ada=None, warp=None):
         assert model in ('normal', 'cgan', 'infogan')
-        p0, ada_cfg = check_augment_gate(augment, augment_p, ada, exchange)      # (refused before anything is touched)
+        p0, ada_cfg = check_augment_gate(augment, augment_p, ada, exchange, warp)      # (refused before anything is touched)
         self.model, self.gen, self.dis_i, self.dis_v = model, gen, dis_i, dis_v
         if precision is not None:                                 # 'f32' | 'bf16': MFMA operand type of every conv GEMM
             assert precision in ('f32', 'bf16', 'f32x3')
@@ -257,6 +258,11 @@ class TrainStep:
         # hl.AUG_* flags: differentiable augmentation (Zhao et al. 2020) of the real and the generated clips in front of BOTH
         # discriminators, one parameter set per clip; the generator's gradient goes back through its adjoint.  No reference counterpart.
         self.augment = hl.parse_augment(augment)
+        # warp: None = off (no launch, no allocation, no stream id more); 'flip,rot90,scale,rotate' (any subset) or a mask of
+        # hl.WARP_* flags: the geometric family of Karras et al. 2020 as a second differentiable stage IN FRONT of `augment` -- one
+        # affine matrix per clip, bilinear taps, zero padding (hl.warp_fwd); the generator's gradient goes back through its exact
+        # adjoint (hl.warp_bwd).  With augment_p / ada its components share the one probability of the state block.
+        self.warp = hl.parse_warp(warp)
         # augment_p, ada: both None = the draws of before (no launch, allocation, stream id or event more).  augment_p = P in [0, 1]:
         # every component of the policy is applied to a clip with probability P (Karras et al. 2020: below about 0.8 the
         # augmentation does not leak into the generated clips) -- hl.augment_draw_gated reads P from a state block in device memory.
@@ -330,9 +336,12 @@ class TrainStep:
         return hl.concat_label_planes(x_dev, c, dl, labels, out)
 
     # ---- perf-mode randomness bookkeeping ----------------------------------------------------------
-    STREAMS_PER_RANK = 64        # Philox stream ids one rank may consume per iteration (uses 5 x 8, 40 / 41 with augmentation, 42 / 43 with its gates)
+    STREAMS_PER_RANK = 64        # Philox stream ids one rank may consume per iteration (uses 5 x 8, 40 / 41 with augmentation, 42 / 43 with its gates,
+    #                              44 / 45 with the warp, 46 / 47 with its gates)
     AUG_STREAM_REAL, AUG_STREAM_FAKE = 40, 41     # ... the augmentation parameters of the real / the generated clips
     AUG_GATE_REAL, AUG_GATE_FAKE = 42, 43         # ... and, with augment_p / ada, the gates of their components
+    WARP_STREAM_REAL, WARP_STREAM_FAKE = 44, 45   # ... the warp's matrices of the real / the generated clips
+    WARP_GATE_REAL, WARP_GATE_FAKE = 46, 47       # ... and the gates of their components
     MAX_RANKS = 64
 
     def frame_index(self, it, T):
@@ -367,7 +376,11 @@ class TrainStep:
         (what the discriminators saw, without label planes), 'gx_aug' (the gradient w.r.t. x_fake_aug) and 'augment' (the
         parameters); 'x_fake' / 'gx_fake' stay the un-augmented clip and the gradient w.r.t. it.
         With augment_p / ada, perf mode draws the gates on stream ids base + 42 / 43 (geo[:, 6] then says what was applied); parity
-        mode takes inject['augment'] as it is -- the caller gates it -- and the controller's update runs all the same."""
+        mode takes inject['augment'] as it is -- the caller gates it -- and the controller's update runs all the same.
+        With the warp on, parity mode needs 'warp': {'real': mat, 'fake': mat} -- float [n][8] device tensors (mcg_warp_draw's form);
+        perf mode draws them on stream ids base + 44 / 45 (gates: base + 46 / 47).  The clips are warped first, then augmented;
+        the result holds 'warp' (the matrices) and 'x_real_aug' / 'x_fake_aug' / 'gx_aug' with the meaning above: what the
+        discriminators saw after BOTH stages, and the gradient with respect to it."""
         gen, di, dv = self.gen, self.dis_i, self.dis_v
         u8 = x_real.dtype == torch.uint8
         if u8:
@@ -400,6 +413,25 @@ class TrainStep:
                 raise ValueError("augmentation is on: parity mode needs inject['augment'] = {'real': (geo, col), 'fake': (geo, col)}")
             else:
                 aug_par = dict(inject['augment'])
+        warp = self.warp
+        warp_par = None
+        if warp:
+            if inject is None:
+                warp_par = {}                                        # (drawn where the clips are warped: stream ids base + 44 / 45)
+            elif 'warp' not in inject:
+                raise ValueError("the warp is on: parity mode needs inject['warp'] = {'real': mat, 'fake': mat}")
+            else:
+                warp_par = dict(inject['warp'])
+        pre = aug or warp                                            # a stage in front of the discriminators: the clips are built first
+
+        def warped(x, which, sid, gate_sid):
+            """x [n][T][H][W][4] -> its warped copy with the matrices of `which` ('real' | 'fake'), on the current stream"""
+            if which not in warp_par:
+                if self._ada is not None:
+                    warp_par[which] = hl.warp_draw_gated(n, H, W, warp, seed, base + sid, base + gate_sid, self._ada, device=self.device)
+                else:
+                    warp_par[which] = hl.warp_draw(n, H, W, warp, seed, base + sid, device=self.device)
+            return hl.warp_fwd(x, c_img, warp_par[which], torch.empty_like(x))
 
         def augmented(x, which, sid, gate_sid):
             """x [n][T][H][W][4] -> its augmented copy with the parameters of `which` ('real' | 'fake'), on the current stream"""
@@ -411,19 +443,28 @@ class TrainStep:
             geo, col = aug_par[which]
             return hl.augment_fwd(x, c_img, geo, col, hl.augment_workspace(n, self.device), torch.empty_like(x))
 
+        def staged(x, which):
+            """the warp, then the augmentation: cutout and the zero border of a translation stay axis-aligned"""
+            real = which == 'real'
+            if warp:
+                x = warped(x, which, self.WARP_STREAM_REAL if real else self.WARP_STREAM_FAKE, self.WARP_GATE_REAL if real else self.WARP_GATE_FAKE)
+            if aug:
+                x = augmented(x, which, self.AUG_STREAM_REAL if real else self.AUG_STREAM_FAKE, self.AUG_GATE_REAL if real else self.AUG_GATE_FAKE)
+            return x
+
         # ------------------------------------------------ forward: real
         x_real_aug = None
-        if cgan or aug:
+        if cgan or pre:
             # label planes (cgan) are part of D's input, and the augmentation reads whole clips: build the device-layout clip once
-            # -- packed without noise, augmented, label planes appended (they are not augmented) -- then add noise
+            # -- packed without noise, warped, augmented, label planes appended (they are neither) -- then add noise
             real = {}
 
             def build_real():
                 tmp = torch.empty((n, T, H, W, lay.pad4(c_img)), device=self.device)
                 (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, lay.pad4(c_img), T, hw, x_real, tmp)
-                if aug:
-                    tmp = augmented(tmp, 'real', self.AUG_STREAM_REAL, self.AUG_GATE_REAL)
-                real['aug'] = tmp if aug else None
+                if pre:
+                    tmp = staged(tmp, 'real')
+                real['aug'] = tmp if pre else None
                 real['x'] = self._concat_label_clip(tmp, t_real) if cgan else tmp
             c_valid_r = c_img + (gen.dim_zl if cgan else 0)
 
@@ -449,7 +490,7 @@ class TrainStep:
         real_chain = None
         # (not for 'f32x3': measured 2-3 % SLOWER at 32 / 64 / 128 clips -- its launches are tuned, form by form, at the 2n batch)
         use_chain = CHAINS and self.side is not None and ex is None and dv.sync_bn is None and dv.precision != 'f32x3' and n >= CHAINS_MIN_N
-        if (cgan or aug) and not (aug and use_chain):
+        if (cgan or pre) and not (pre and use_chain):
             build_real()                                             # on the main stream: every reader is ordered behind it
         if use_chain:
             cs = self._chain_stream
@@ -461,7 +502,7 @@ class TrainStep:
                     cs.wait_event(input_event)                       # x_real (otherwise ready by contract)
             else:
                 cs.wait_stream(main)                                 # x_real (and whatever produced it)
-            if aug:
+            if pre:
                 # the augmented real clips are made on the chain stream, which may run ahead of the main stream (input_event /
                 # input_ready_early): its own reader follows in stream order; the main stream -- D_I's side stream and the
                 # one-batch readers are ordered behind it -- waits for the event
@@ -481,10 +522,10 @@ class TrainStep:
         draw = inject['gen'] if inject is not None else gen.draw(n, (seed, base + 8 * 2))
         x_fake, s_gen = gen.forward(n, draw)
         t_fake = draw['labels']
-        if cgan or aug:
+        if cgan or pre:
             x_real_aug = real['aug']
-        x_fake_aug = augmented(x_fake, 'fake', self.AUG_STREAM_FAKE, self.AUG_GATE_FAKE) if aug else None
-        xf = x_fake_aug if aug else x_fake
+        x_fake_aug = staged(x_fake, 'fake') if pre else None
+        xf = x_fake_aug if pre else x_fake
         if cgan:
             xf = self._concat_label_clip(xf, t_fake)
         c_valid = c_img + (gen.dim_zl if cgan else 0)
@@ -601,9 +642,12 @@ class TrainStep:
         if cgan:                                                     # label planes carry no gradient to G: the clip's channels alone
             gx = hl.concat_label_planes(gx, c_img, 0, None, torch.empty_like(x_fake))
         gx_aug = None
-        if aug:                                                      # the adjoint of the generated clips' augmentation
+        if pre:                                                      # the adjoints of the generated clips' stages, last stage first
             gx_aug = gx
-            gx = hl.augment_bwd(gx_aug, c_img, *aug_par['fake'], hl.augment_workspace(n, self.device), torch.empty_like(gx_aug))
+            if aug:
+                gx = hl.augment_bwd(gx, c_img, *aug_par['fake'], hl.augment_workspace(n, self.device), torch.empty_like(gx))
+            if warp:
+                gx = hl.warp_bwd(gx, c_img, warp_par['fake'], torch.empty_like(gx))
         late_g = []
         lo_g, hi_g = gen.grad_bucket_late()
         gen.backward(s_gen, gx, on_late_bucket=(lambda: late_g.append(ex.start(gen.fp.g[lo_g:hi_g]))) if ex else None)
@@ -613,7 +657,11 @@ class TrainStep:
                 ex.finish(h)
         adam_update(gen, self.hyper['image_gen'], gs)
         self.iteration += 1
-        res = {} if not aug else {'x_real_aug': x_real_aug, 'x_fake_aug': x_fake_aug, 'gx_aug': gx_aug, 'augment': aug_par}
+        res = {} if not pre else {'x_real_aug': x_real_aug, 'x_fake_aug': x_fake_aug, 'gx_aug': gx_aug}
+        if aug:
+            res['augment'] = aug_par
+        if warp:
+            res['warp'] = warp_par
         return {**res, 'x_fake': x_fake, 't_fake': t_fake, 't': t, 'gx_fake': gx, 'saved_gen': s_gen, 'saved_fake_i': s_fake_i, 'saved_fake_v': s_fake_v,
                 'saved_i': s_i, 'saved_v': s_v,
                 'y_real_i': y_real_i, 'y_real_v': y_real_v, 'y_fake_i': y_fake_i, 'y_fake_v': y_fake_v}

@@ -37,24 +37,27 @@ class Updater:
         ema_decay = kwargs.pop('ema_decay', None)
         # None: off; 'color,translation,cutout' (any subset) or a mask: differentiable augmentation in front of both discriminators
         augment = kwargs.pop('augment', None)
+        # None: off; 'flip,rot90,scale,rotate' (any subset) or a mask: the geometric augmentation (a per-clip affine warp), applied
+        # in front of `augment`; augment_p / ada below gate its components too
+        warp = kwargs.pop('warp', None)
         # False: off; True: per-network gradient norms from the device, reported with the losses at every new epoch (a
         # GradientClipping hook on an optimizer switches them on for its network either way; they are reported only with this)
         self._grad_stats = bool(kwargs.pop('grad_stats', False))
         # augment_p: None, or P in [0, 1]: every component of the policy is applied to a clip with probability P; ada: None, True or
         # {'target', 'interval', 'kimg'}: P follows the discriminators' overfitting signal r_t = E[sign(D(real))] (Karras et al.
-        # 2020); P and the two r_t are reported with the losses at every new epoch.  Both need `augment` (step.check_augment_gate)
+        # 2020); P and the two r_t are reported with the losses at every new epoch.  Both need `augment` or `warp` (step.check_augment_gate)
         augment_p = kwargs.pop('augment_p', None)
         ada = kwargs.pop('ada', None)
         if kwargs:
             raise TypeError('unexpected arguments: %s' % sorted(kwargs))
-        self._ada_report = _step.check_augment_gate(augment, augment_p, ada, exchange)[0] is not None
+        self._ada_report = _step.check_augment_gate(augment, augment_p, ada, exchange, warp)[0] is not None
         self.iteration = 0
         self.observation = {}
         hyper = {k: self._optimizers[k].hyper() for k in ('image_gen', 'image_dis', 'video_dis')}
         self._step = _step.TrainStep(self.model, self.image_gen.impl, self.image_dis.impl, self.video_dis.impl,
                                      hyper=hyper, exchange=exchange, seed=seed, rank=rank, overlap=overlap,
                                      precision=precision, sync_bn=sync_bn, ema_decay=ema_decay, augment=augment,
-                                     grad_stats=self._grad_stats, augment_p=augment_p, ada=ada)
+                                     grad_stats=self._grad_stats, augment_p=augment_p, ada=ada, warp=warp)
 
     # ---- StandardUpdater surface -------------------------------------------------------------------
     def get_optimizer(self, name):

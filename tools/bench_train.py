@@ -62,7 +62,9 @@ def main():
                                                                   "keeps the averaged generator as well")
     ap.add_argument('--augment', default='', help="train.py's flag: '' = off, a subset of color,translation,cutout = differentiable "
                                                   "augmentation in front of both discriminators")
-    ap.add_argument('--augment_p', type=float, default=None, help="train.py's flag: each component of --augment is applied with this "
+    ap.add_argument('--warp', default='', help="train.py's flag: '' = off, a subset of flip,rot90,scale,rotate = the geometric augmentation "
+                                               "(a per-clip affine warp) in front of --augment")
+    ap.add_argument('--augment_p', type=float, default=None, help="train.py's flag: each component of --augment / --warp is applied with this "
                                                                    "probability (the start value with --ada_target)")
     ap.add_argument('--ada_target', type=float, default=None, help="train.py's flag: adapt that probability towards r_t = this target "
                                                                     "(one more launch per iteration)")
@@ -121,6 +123,7 @@ def main():
                       iterator=it, tensorboard_writer=T.NullWriter(), optimizer={'image_gen': opt(gen), 'image_dis': opt(di), 'video_dis': opt(dv)},
                       device=0, seed=0, overlap=bool(args.overlap), precision=args.mfma,
                       **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}), **(dict(augment=args.augment) if args.augment else {}),
+                      **(dict(warp=args.warp) if args.warp else {}),
                       **(dict(grad_stats=True) if args.grad_stats else {}),
                       **(dict(augment_p=args.augment_p) if args.augment_p is not None else {}),
                       **(dict(ada={'target': args.ada_target, 'interval': args.ada_interval, 'kimg': args.ada_kimg})
@@ -141,7 +144,7 @@ def main():
     dt = time.perf_counter() - t0
     rec = {"path": "train.py object graph: Trainer + Updater.update_core + %s" % type(it).__name__, "data": args.data,
            "loader_workers": args.loader_workers, "dtype": args.mfma, "model": args.model, "batch": args.batchsize, "iters": args.iters,
-           "ema_decay": args.ema_decay, "augment": args.augment, "augment_p": args.augment_p, "ada_target": args.ada_target, "grad_clip": args.grad_clip, "grad_stats": args.grad_stats, "side_streams": bool(args.overlap), "two_chain_iterations": mstep.chain_iterations - chains0,
+           "ema_decay": args.ema_decay, "augment": args.augment, "warp": args.warp, "augment_p": args.augment_p, "ada_target": args.ada_target, "grad_clip": args.grad_clip, "grad_stats": args.grad_stats, "side_streams": bool(args.overlap), "two_chain_iterations": mstep.chain_iterations - chains0,
            "clips_per_s": round(args.batchsize * args.iters / dt, 1), "ms_per_iteration": round(dt / args.iters * 1e3, 3),
            "epochs_seen": updater.epoch, "dataset_clips": args.size}
     print(json.dumps(rec), flush=True)

@@ -79,12 +79,17 @@ def parse_args(argv=None):
                    help="'' (default): off.  A comma-separated subset of color,translation,cutout: differentiable augmentation (Zhao et "
                         "al. 2020) of the real and the generated clips in front of both discriminators, one random parameter set per "
                         "clip; the generator's gradient is carried back through it")
+    p.add_argument('--warp', default='',
+                   help="'' (default): off.  A comma-separated subset of flip,rot90,scale,rotate: the geometric augmentation of "
+                        "Karras et al. 2020 -- one random affine map per clip (x-flip, quarter turn, isotropic scale in (5/7, 7/5), "
+                        "rotation), bilinear, zero-padded, applied to the real and the generated clips in front of --augment; the "
+                        "generator's gradient is carried back through its exact adjoint.  rot90 needs square frames")
     p.add_argument('--augment_p', type=float, default=None,
-                   help="with --augment: apply each of its components to a clip with this probability in [0, 1] instead of always "
+                   help="with --augment or --warp: apply each of its components to a clip with this probability in [0, 1] instead of always "
                         "(Karras et al. 2020: below about 0.8 the augmentation does not leak into the generated clips); with "
                         "--ada_target the probability the run starts from (default 0)")
     p.add_argument('--ada_target', type=float, default=None,
-                   help="with --augment: adapt that probability during the run -- every --ada_interval iterations it moves towards "
+                   help="with --augment or --warp: adapt that probability during the run -- every --ada_interval iterations it moves towards "
                         "r_t = E[sign(D(real))] = this target in (-1, 1), r_t that of the discriminator that overfits more (Karras "
                         "et al. 2020 use 0.6).  No default: giving it switches the adaptation on")
     p.add_argument('--ada_interval', type=int, default=4, help="iterations between two adjustments of the probability")
@@ -109,8 +114,13 @@ def parse_args(argv=None):
     except ValueError as e:
         p.error('--augment: %s' % e)
     try:
+        from mocogan_chainer_amd.hiplib import parse_warp
+        parse_warp(args.warp)
+    except ValueError as e:
+        p.error('--warp: %s' % e)
+    try:
         from mocogan_chainer_amd.step import check_augment_gate
-        check_augment_gate(args.augment, args.augment_p, ada_option(args))
+        check_augment_gate(args.augment, args.augment_p, ada_option(args), warp=args.warp)
     except ValueError as e:
         p.error('--augment_p / --ada_*: %s' % e)
     return args
@@ -207,7 +217,7 @@ def main(argv=None):
                       tensorboard_writer=writer, optimizer=opts, device=args.gpu, seed=args.seed, exchange=exchange, rank=rank,
                       overlap=bool(args.overlap), precision=args.mfma, sync_bn=bool(args.sync_bn),
                       ema_decay=args.ema_decay if args.ema_decay > 0 else None, augment=args.augment or None,
-                      grad_stats=bool(args.grad_stats), augment_p=args.augment_p, ada=ada_option(args))
+                      grad_stats=bool(args.grad_stats), augment_p=args.augment_p, ada=ada_option(args), warp=args.warp or None)
 
     save_path = Path('result') / args.save_name
     trainer = T.Trainer(updater, (args.max_epoch, 'epoch'), out=save_path)
