@@ -133,7 +133,8 @@ typedef struct mcg_conv_geom {
  *     and with the sliced Wasserstein distance (mcg_swd_*, mcg_sort_* added; no argument list changed)
  *     and with the gradient statistics (mcg_grad_stats*, mcg_adam_wd_ctl added; no argument list changed)
  *     and with the adaptive augmentation (mcg_augment_draw_gated, mcg_ada_update added; no argument list changed)
- *     and with the geometric augmentation (mcg_warp_* added; no argument list changed). */
+ *     and with the geometric augmentation (mcg_warp_* added; no argument list changed)
+ *     and with the nearest-neighbour metrics (mcg_knn_* added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -649,6 +650,37 @@ int mcg_sort_local_span(void);
 int mcg_sort_rows(int rows, int64_t n, float* data, int64_t row_stride, void* workspace, void* stream);
 int mcg_swd_distance(int K, int64_t n_a, int64_t n_b, const float* a, int64_t a_stride, const float* b, int64_t b_stride,
                      double* out, void* workspace, void* stream);
+
+/* ---- nearest-neighbour sample metrics on the int8 matrix pipe (csrc/knn.hip) -------------------------------------------------
+ * Improved precision / recall (Kynkaanniemi et al. 2019), density / coverage (Naeem et al. 2020) and a data-copying score (after
+ * Meehan et al. 2020) all reduce to pairwise squared distances between whole-clip descriptors, the k smallest per row, and counts
+ * (no reference counterpart: the reference has no metric).  The descriptors are bytes, so every quantity is an integer; with
+ * D <= 32768, |a.b| <= 2^29, |a|^2 <= 2^29 and the largest squared distance 255^2 * 32768 = 2 130 739 200 < 2^31: dots, norms and
+ * distances are exact in int32 and equal NumPy's bit for bit.  mocogan-chainer_amd/metrics.py (KnnMetrics) composes the stages.
+ * No atomics, no workspace, no address that depends on data; one launch each.
+ *
+ * mcg_knn_descriptors: uint8 clips [N][T][64][64][C], C = 1..3 (MCG_ERR_UNSUPPORTED for another frame size), pool in {2, 4, 8}.
+ *   With s the sum of a pool x pool box of one channel, q = (2 s + pool^2) / (2 pool^2) (integer division: the mean rounded half
+ *   up, 0..255); desc holds int8(q - 128), row-major over (T, 64/pool, 64/pool, C): D = T (64/pool)^2 C, always a multiple of
+ *   64.  norms[n] = sum of desc[n][:]^2.  D > 32768 is MCG_ERR_UNSUPPORTED.  One workgroup per clip.
+ * mcg_knn_sqdist: out[i][j] = na[i] + nb[j] - 2 sum_d a[i][d] b[j][d] for a [M][D], b [N][D] (both K-contiguous rows, 16-byte
+ *   aligned), on v_mfma_i32_32x32x32_i8.  Any M, N >= 1; D a multiple of 64 in 64..32768 (another multiple of 64:
+ *   MCG_ERR_UNSUPPORTED; no multiple or a misaligned a / b: MCG_ERR_BAD_ARG).  128 x 128 tiles; row indices past M and N are
+ *   clamped on load and their results are not stored: nothing outside a, b, na, nb is read, elements N .. ld of a row of out are
+ *   not written.  a and b may be the same matrix.  M <= 128 * 65535.
+ * mcg_knn_smallest: for every row of dist [M][ld] the k smallest of its first N entries in ascending (value, column) order -- ties
+ *   go to the lower column -- as val [M][k], idx [M][k]; 1 <= k <= 16.  With exclude_self, column self_col0 + i of row i is
+ *   skipped (a row block starting at row self_col0 of a self-distance matrix leaves out its own diagonal).  Missing neighbours
+ *   (fewer than k candidates) are val = INT32_MAX, idx = -1.  One wave per row.
+ * mcg_knn_ball_counts: counts[i] = #{j < N : dist[i][j] <= radius[j]}.  One wave per row.
+ * MCG_ERR_BAD_ARG, refused on the host before any launch: a null pointer, a non-positive extent, C outside 1..3, another pool,
+ *   ld < N, k outside 1..16. */
+int mcg_knn_descriptors(int N, int C, int T, int H, int W, int pool, const uint8_t* clips, int8_t* desc, int32_t* norms, void* stream);
+int mcg_knn_sqdist(int M, int N, int D, const int8_t* a, const int32_t* na, const int8_t* b, const int32_t* nb, int32_t* out, int64_t ld,
+                   void* stream);
+int mcg_knn_smallest(int M, int N, const int32_t* dist, int64_t ld, int k, int exclude_self, int64_t self_col0, int32_t* val, int32_t* idx,
+                     void* stream);
+int mcg_knn_ball_counts(int M, int N, const int32_t* dist, int64_t ld, const int32_t* radius, int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/conv_gemm.hip", "csrc/small_ops.hip", "csrc/metrics.hip"]
+SOURCES = ["csrc/conv_gemm.hip", "csrc/small_ops.hip", "csrc/metrics.hip", "csrc/knn.hip"]
 
 
 def lib_path():
@@ -38,7 +38,7 @@ def _stale():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -O3 -fPIC -> lib/libmocogan_hip.so (in-tree).  The conv GEMM source is compiled as
-    three translation units (one per pass, -DMCG_TU=1..3) next to small_ops.hip and metrics.hip, all five in parallel, then linked."""
+    three translation units (one per pass, -DMCG_TU=1..3) next to small_ops.hip, metrics.hip and knn.hip, all six in parallel, then linked."""
     if not force and not _stale():
         return lib_path()
     os.makedirs(os.path.join(HERE, "lib"), exist_ok=True)
@@ -50,6 +50,7 @@ def build(force=False, verbose=False):
     units = [("conv_gemm_tu%d.o" % tu, ["-DMCG_TU=%d" % tu, os.path.join(HERE, "csrc/conv_gemm.hip")]) for tu in (1, 2, 3)]
     units.append(("small_ops.o", [os.path.join(HERE, "csrc/small_ops.hip")]))
     units.append(("metrics.o", [os.path.join(HERE, "csrc/metrics.hip")]))
+    units.append(("knn.o", [os.path.join(HERE, "csrc/knn.hip")]))
     procs = []
     for obj, args in units:
         cmd = common + args + ["-c", "-o", os.path.join(objdir, obj)]

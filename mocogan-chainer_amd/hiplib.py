@@ -118,6 +118,10 @@ SIGNATURES = {
     "mcg_sort_local_span": (_I, []),
     "mcg_sort_rows": (_I, [_I, _I64, _P, _I64, _P, _P]),
     "mcg_swd_distance": (_I, [_I, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "mcg_knn_descriptors": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "mcg_knn_sqdist": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I64, _P]),
+    "mcg_knn_smallest": (_I, [_I, _I, _P, _I64, _I, _I, _I64, _P, _P, _P]),
+    "mcg_knn_ball_counts": (_I, [_I, _I, _P, _I64, _P, _P, _P]),
 }
 
 ABI_VERSION = 8          # MCG_ABI_VERSION of include/mocogan_hip.h these prototypes were written against
@@ -1411,3 +1415,62 @@ def swd_distance(a, b, n, ws, out):
     _check(load().mcg_swd_distance(a.shape[0], n, n, _p(_dense(a)), a.shape[1], _p(_dense(b)), b.shape[1], _p(out, torch.float64),
                                    _p(ws, torch.float64), _stream()), "mcg_swd_distance")
     return out
+
+
+# ---- nearest-neighbour metrics on the int8 matrix pipe (include/mocogan_hip.h: mcg_knn_*; composed by metrics.py) ------------------
+KNN_POOLS = (2, 4, 8)
+KNN_MAX_D, KNN_MAX_K = 32768, 16
+
+
+def knn_descriptors(clips, pool, desc=None, norms=None):
+    """uint8 clips (N,T,64,64,C) -> (desc [N][D] int8, norms [N] int32): box means over pool x pool, rounded half up, minus 128;
+    D = T * (64 / pool)^2 * C.  desc / norms may be views of a set's matrices at the chunk's rows."""
+    if clips.dtype != torch.uint8 or clips.dim() != 5:
+        raise McgError("knn_descriptors: uint8 clips (N,T,H,W,C), got %s %s" % (clips.dtype, tuple(clips.shape)))
+    n, t, h, w, c = clips.shape
+    if pool not in KNN_POOLS:
+        raise McgError("knn_descriptors: pool is one of %s, got %r" % (KNN_POOLS, pool))
+    d = t * (h // pool) * (w // pool) * c
+    desc = torch.empty(n, d, dtype=torch.int8, device=clips.device) if desc is None else desc
+    norms = torch.empty(n, dtype=torch.int32, device=clips.device) if norms is None else norms
+    if desc.numel() != n * d or norms.numel() != n:
+        raise McgError("knn_descriptors: desc %s / norms %s do not fit %d x %d" % (tuple(desc.shape), tuple(norms.shape), n, d))
+    _check(load().mcg_knn_descriptors(n, c, t, h, w, pool, _p(_dense(clips), torch.uint8), _p(_dense(desc), torch.int8),
+                                      _p(_dense(norms), torch.int32), _stream()), "mcg_knn_descriptors")
+    return desc, norms
+
+
+def knn_sqdist(a, na, b, nb, out):
+    """out [M][ld >= N] int32: out[i][j] = na[i] + nb[j] - 2 a[i].b[j] for int8 a [M][D], b [N][D] (exact); columns N.. untouched"""
+    (m, d), n = a.shape, b.shape[0]
+    if b.shape[1] != d or na.numel() != m or nb.numel() != n or out.dim() != 2 or out.shape[0] != m or out.shape[1] < n:
+        raise McgError("knn_sqdist: a %s, b %s, out %s do not fit" % (tuple(a.shape), tuple(b.shape), tuple(out.shape)))
+    _check(load().mcg_knn_sqdist(m, n, d, _p(_dense(a), torch.int8), _p(_dense(na), torch.int32), _p(_dense(b), torch.int8),
+                                 _p(_dense(nb), torch.int32), _p(_dense(out), torch.int32), out.shape[1], _stream()), "mcg_knn_sqdist")
+    return out
+
+
+def knn_smallest(dist, k, n=None, exclude_self=False, self_col0=0, val=None, idx=None):
+    """(val, idx) [M][k] int32: the k smallest of the first n (default: all) entries of every row of dist [M][ld] in ascending
+    (value, column) order; with exclude_self row i skips column self_col0 + i; missing neighbours are (INT32_MAX, -1)"""
+    m, ld = dist.shape
+    n = ld if n is None else n
+    val = torch.empty(m, k, dtype=torch.int32, device=dist.device) if val is None else val
+    idx = torch.empty(m, k, dtype=torch.int32, device=dist.device) if idx is None else idx
+    if val.numel() != m * k or idx.numel() != m * k:
+        raise McgError("knn_smallest: val %s / idx %s do not fit %d x %d" % (tuple(val.shape), tuple(idx.shape), m, k))
+    _check(load().mcg_knn_smallest(m, n, _p(_dense(dist), torch.int32), ld, k, int(bool(exclude_self)), self_col0,
+                                   _p(_dense(val), torch.int32), _p(_dense(idx), torch.int32), _stream()), "mcg_knn_smallest")
+    return val, idx
+
+
+def knn_ball_counts(dist, radius, n=None, counts=None):
+    """counts [M] int32: how many of the first n (default: all) entries j of row i of dist [M][ld] lie within radius[j]"""
+    m, ld = dist.shape
+    n = ld if n is None else n
+    counts = torch.empty(m, dtype=torch.int32, device=dist.device) if counts is None else counts
+    if radius.numel() < n or counts.numel() != m:
+        raise McgError("knn_ball_counts: radius %s / counts %s do not fit %d x %d" % (tuple(radius.shape), tuple(counts.shape), m, n))
+    _check(load().mcg_knn_ball_counts(m, n, _p(_dense(dist), torch.int32), ld, _p(_dense(radius), torch.int32),
+                                      _p(_dense(counts), torch.int32), _stream()), "mcg_knn_ball_counts")
+    return counts

@@ -4,6 +4,9 @@ of libmocogan_hip.so (include/mocogan_hip.h).  torch supplies memory and the str
 What the number is: per pyramid level, how far the distributions of normalised 7x7(x patch_frames) Laplacian patches of the two
 sets lie apart, x 1e3 as ProGAN reports it.  What it is not: it sees nothing a 7x7(x patch_frames) patch cannot see -- no global
 layout, no identity, no motion beyond patch_frames frames.
+
+KnnMetrics, below it, is the complement: nearest-neighbour precision / recall, density / coverage and a data-copying score on
+whole-clip descriptors, composed from the mcg_knn_* stages (exact integer distances on the int8 matrix pipe).
 """
 import numpy as np
 import torch
@@ -117,3 +120,106 @@ class SlicedWasserstein:
         res = {str(s): float(np.sum(vals[li]) / R * 1e3) for li, s in enumerate(LEVELS)}
         res['avg'] = float(sum(res[str(s)] for s in LEVELS) / len(LEVELS))
         return res
+
+
+# ---- nearest-neighbour metrics: precision / recall, density / coverage, a data-copying score (mcg_knn_*) ----------------------------
+class KnnSet:
+    """The whole-clip descriptors of one set of clips: desc [n][D] int8 and norms [n] int32 (sum of squares) on the device."""
+
+    def __init__(self, desc, norms, shape, pool):
+        self.desc, self.norms, self.shape, self.pool = desc, norms, shape, pool
+        self.n, self.dim = desc.shape
+
+
+class KnnMetrics:
+    """Improved precision / recall (Kynkaanniemi et al. 2019), density / coverage (Naeem et al. 2020) and a data-copying score
+    (after Meehan et al. 2020) between sets of uint8 clips, composed from the mcg_knn_* stages of libmocogan_hip.so.  Distances are
+    squared L2 between pool x pool box means of whole clips, as bytes: every quantity is an integer, the distances come exact from
+    the int8 matrix pipe, and the figures equal tests/knn_ref.py's bit for bit.
+
+    What the numbers are not: the distance compares ALIGNED clips, so a shifted copy is not a copy; the radii, and with them
+    every figure, depend on the set sizes and on k -- compare at equal settings; copy_auc means something only with held-out
+    clips that training never saw."""
+
+    def __init__(self, k=5, pool=4, row_block=4096, device='cuda'):
+        if not 1 <= k <= hl.KNN_MAX_K:
+            raise ValueError('k lies in 1..%d' % hl.KNN_MAX_K)
+        if pool not in hl.KNN_POOLS:
+            raise ValueError('pool is one of %s' % (hl.KNN_POOLS,))
+        if row_block < 1:
+            raise ValueError('row_block is positive')
+        self.k, self.pool, self.row_block, self.device = k, pool, row_block, torch.device(device)
+
+    def descriptors(self, chunks):
+        """chunks: an iterable of uint8 arrays / tensors (N_i, T, 64, 64, C), host or device, N_i of any size (as
+        SlicedWasserstein.raw_descriptors) -> the KnnSet of their concatenation.  A clip's row depends on that clip alone, so the
+        chunking does not change the result."""
+        desc, norms, shape = [], [], None
+        for chunk in chunks:
+            u8 = torch.as_tensor(np.ascontiguousarray(chunk) if isinstance(chunk, np.ndarray) else chunk)
+            if u8.dtype != torch.uint8 or u8.dim() != 5:
+                raise ValueError('clips are uint8 (N,T,64,64,C), got %s %s' % (u8.dtype, tuple(u8.shape)))
+            if shape is None:
+                shape = tuple(u8.shape[1:])
+                d = shape[0] * (64 // self.pool) ** 2 * shape[3]
+                if shape[1:3] != (64, 64) or not 1 <= shape[3] <= 3:
+                    raise ValueError('clips are (N,T,64,64,C) with C in 1..3, got %s' % (tuple(u8.shape),))
+                if d > hl.KNN_MAX_D:
+                    raise ValueError('pool %d gives descriptors of %d bytes, the limit is %d: use a larger pool' % (self.pool, d, hl.KNN_MAX_D))
+            elif tuple(u8.shape[1:]) != shape:
+                raise ValueError('chunks differ in shape: %s and %s' % (shape, tuple(u8.shape[1:])))
+            if u8.shape[0] == 0:
+                continue
+            dn = hl.knn_descriptors(u8.to(self.device).contiguous(), self.pool)
+            desc.append(dn[0])
+            norms.append(dn[1])
+        if not desc:
+            raise ValueError('no clips')
+        one = len(desc) == 1
+        return KnnSet(desc[0] if one else torch.cat(desc), norms[0] if one else torch.cat(norms), shape, self.pool)     # (copies, no arithmetic)
+
+    def _rows(self, a, b, fn):
+        """the device tensors fn(dist block, first row) returns, concatenated over blocks of row_block rows of the squared
+        distances of set a (rows) to set b (columns).  Every stage is per row, so the blocking is exact."""
+        out = torch.empty(min(self.row_block, a.n), b.n, dtype=torch.int32, device=self.device)
+        parts = []
+        for lo in range(0, a.n, self.row_block):
+            hi = min(lo + self.row_block, a.n)
+            parts.append(fn(hl.knn_sqdist(a.desc[lo:hi], a.norms[lo:hi], b.desc, b.norms, out[:hi - lo]), lo))
+        return [torch.cat(p) for p in zip(*parts)]
+
+    def radii(self, x):
+        """rad[i]: the k-th smallest squared distance from x[i] to the other members of x (int32, on the device)"""
+        k = self.k
+        return self._rows(x, x, lambda d, lo: (hl.knn_smallest(d, k, exclude_self=True, self_col0=lo)[0][:, k - 1],))[0].contiguous()
+
+    def report(self, real, fake, holdout=None):
+        """{'precision', 'recall', 'density', 'coverage', 'copy_auc' (None without holdout), 'nn_index', 'nn_dist'} of KnnSets:
+        R = real (the training clips), F = fake, H = held-out real clips.  With rad_X[i] the k-th smallest squared distance of X_i
+        to the rest of X:  precision = share of F inside some ball (R_j, rad_R[j]); recall = share of R inside some ball (F_j,
+        rad_F[j]); density = balls of R a fake lies in, on average, over k; coverage = share of R whose nearest fake lies within
+        rad_R; copy_auc = P(dF < dH) + P(dF == dH) / 2 for dF, dH the distances of a fake / a held-out clip to its nearest
+        training clip (0.5: as far as fresh real clips; towards 1: closer -- copying); nn_index, nn_dist: every fake clip's
+        nearest training clip and its squared distance.  Every O(n^2) step is a kernel; the scalars are integer counts over the
+        O(n) arrays and one float64 division."""
+        sets = [s for s in (real, fake, holdout) if s is not None]
+        if any((s.dim, s.pool) != (real.dim, real.pool) for s in sets):
+            raise ValueError('the sets differ in descriptor size or pool')
+        k = self.k
+        if k > min(real.n, fake.n) - 1:
+            raise ValueError('k = %d needs sets of at least %d clips (got %d real, %d fake)' % (k, k + 1, real.n, fake.n))
+        rad_r, rad_f = self.radii(real), self.radii(fake)
+        one = lambda dist: hl.knn_smallest(dist, 1)
+        counts_f, nn_dist, nn_index = self._rows(fake, real, lambda d, lo: (hl.knn_ball_counts(d, rad_r),) + tuple(v[:, 0] for v in one(d)))
+        counts_r, near_f = self._rows(real, fake, lambda d, lo: (hl.knn_ball_counts(d, rad_f), one(d)[0][:, 0]))
+        host = lambda t: t.cpu().numpy().astype(np.int64)
+        counts_f, nn_dist, nn_index, counts_r, near_f, rad_r = (host(t) for t in (counts_f, nn_dist, nn_index, counts_r, near_f, rad_r))
+        out = {'precision': int((counts_f > 0).sum()) / fake.n, 'recall': int((counts_r > 0).sum()) / real.n,
+               'density': int(counts_f.sum()) / (k * fake.n), 'coverage': int((near_f <= rad_r).sum()) / real.n,
+               'copy_auc': None, 'nn_index': nn_index, 'nn_dist': nn_dist}
+        if holdout is not None:
+            d_h = np.sort(host(self._rows(holdout, real, lambda d, lo: (one(d)[0][:, 0],))[0]))
+            lo_, hi_ = np.searchsorted(d_h, nn_dist, 'left'), np.searchsorted(d_h, nn_dist, 'right')
+            less, equal = int((holdout.n - hi_).sum()), int((hi_ - lo_).sum())       # pairs with dF < dH, with dF == dH
+            out['copy_auc'] = (2 * less + equal) / (2 * fake.n * holdout.n)
+        return out
