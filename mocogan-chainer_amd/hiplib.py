@@ -1151,27 +1151,30 @@ AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
 AUG_NAMES = {'color': AUG_COLOR, 'translation': AUG_TRANSLATION, 'cutout': AUG_CUTOUT}
 
 
-def parse_augment(policy):
-    """'color,translation,cutout' (any subset, any order), a mask of AUG_* flags, or None / '' / 0 (off) -> the mask (0 = off)"""
+def _parse_policy(policy, names, top, noun, a_noun):
+    """a comma-separated string of `names` (any subset, any order), a mask in 0..top, or None / '' / 0 (off) -> the mask (0 = off)"""
     if policy is None:
         return 0
-    if isinstance(policy, bool):
-        raise ValueError('an augmentation policy is a string of names or a mask, got %r' % (policy,))
+    if isinstance(policy, bool) or not isinstance(policy, (int, str)):
+        raise ValueError('%s policy is a string of names or a mask, got %r' % (a_noun, policy))
     if isinstance(policy, int):
-        if not 0 <= policy <= 7:
-            raise ValueError('an augmentation mask lies in 0..7, got %r' % (policy,))
+        if not 0 <= policy <= top:
+            raise ValueError('%s mask lies in 0..%d, got %r' % (a_noun, top, policy))
         return policy
-    if not isinstance(policy, str):
-        raise ValueError('an augmentation policy is a string of names or a mask, got %r' % (policy,))
     mask = 0
     for name in policy.split(','):
         name = name.strip()
         if not name:
             continue
-        if name not in AUG_NAMES:
-            raise ValueError('unknown augmentation %r (known: %s)' % (name, ', '.join(sorted(AUG_NAMES))))
-        mask |= AUG_NAMES[name]
+        if name not in names:
+            raise ValueError('unknown %s %r (known: %s)' % (noun, name, ', '.join(sorted(names))))
+        mask |= names[name]
     return mask
+
+
+def parse_augment(policy):
+    """'color,translation,cutout' (any subset, any order), a mask of AUG_* flags, or None / '' / 0 (off) -> the mask (0 = off)"""
+    return _parse_policy(policy, AUG_NAMES, 7, 'augmentation', 'an augmentation')
 
 
 def augment_workspace(n, device):
@@ -1257,25 +1260,7 @@ WARP_NAMES = {'flip': WARP_FLIP, 'rot90': WARP_ROT90, 'scale': WARP_SCALE, 'rota
 
 def parse_warp(policy):
     """'flip,rot90,scale,rotate' (any subset, any order), a mask of WARP_* flags, or None / '' / 0 (off) -> the mask (0 = off)"""
-    if policy is None:
-        return 0
-    if isinstance(policy, bool):
-        raise ValueError('a warp policy is a string of names or a mask, got %r' % (policy,))
-    if isinstance(policy, int):
-        if not 0 <= policy <= 15:
-            raise ValueError('a warp mask lies in 0..15, got %r' % (policy,))
-        return policy
-    if not isinstance(policy, str):
-        raise ValueError('a warp policy is a string of names or a mask, got %r' % (policy,))
-    mask = 0
-    for name in policy.split(','):
-        name = name.strip()
-        if not name:
-            continue
-        if name not in WARP_NAMES:
-            raise ValueError('unknown warp %r (known: %s)' % (name, ', '.join(sorted(WARP_NAMES))))
-        mask |= WARP_NAMES[name]
-    return mask
+    return _parse_policy(policy, WARP_NAMES, 15, 'warp', 'a warp')
 
 
 def _warp_mat(n, mat, device, name):

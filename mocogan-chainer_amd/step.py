@@ -233,6 +233,72 @@ def set_replica_counters(net, values):
         net.ema.k = int(values[1 + len(names)])
 
 
+class ClipStage:
+    """One differentiable stage on [n][T][H][W][4] clips in front of BOTH discriminators, one parameter set per clip."""
+    # It is applied to the real and to the generated clips, and the generator's gradient goes back through its adjoint.
+    # name: 'warp' | 'augment', also the key of its parameters in run()'s inject and result; mask: the enabled components
+    # ids: {'real' | 'fake': (Philox stream id of the parameters, ... of the gates)}, relative to the iteration's base
+    # gate: the state block of augment_p / ada, or None; draw, draw_gated: hl.*_draw (no gate) / hl.*_draw_gated
+    # fwd, bwd: hl.*_fwd / hl.*_bwd, called as fn(clip, valid channels, *operands(parameters, clip), a new clip) -- what differs
+    # between the stages (two parameter tensors and a workspace, or one matrix tensor) is in `operands` and nowhere else
+    # missing: the error text when parity mode lacks inject[name]
+
+    def __init__(self, name, mask, ids, gate, draw, draw_gated, fwd, bwd, operands, missing):
+        self.name, self.mask, self.ids, self.gate, self.missing = name, mask, ids, gate, missing
+        self.draw, self.draw_gated, self.fwd, self.bwd, self.operands = draw, draw_gated, fwd, bwd, operands
+
+    def forward(self, x, which, it):
+        """x -> its staged copy with the parameters of `which` ('real' | 'fake'), drawn first if need be: on the current stream"""
+        par = it.par[self.name]
+        if which not in par:
+            sid, gate_sid = (it.base + i for i in self.ids[which])
+            if self.gate is None:
+                par[which] = self.draw(it.n, it.H, it.W, self.mask, it.seed, sid, device=x.device)
+            else:
+                par[which] = self.draw_gated(it.n, it.H, it.W, self.mask, it.seed, sid, gate_sid, self.gate, device=x.device)
+        return self.fwd(x, it.c_img, *self.operands(par[which], x), torch.empty_like(x))
+
+    def adjoint(self, g, which, it):
+        """the gradient w.r.t. the staged clips of `which` -> the gradient w.r.t. the clips: on the current stream"""
+        return self.bwd(g, it.c_img, *self.operands(it.par[self.name][which], g), torch.empty_like(g))
+
+
+class _Iteration:
+    """What the phases of one TrainStep.run share."""
+    # Set here: the call's arguments, the shape, the frame index t, the first Philox stream id, the model's flags, the stages'
+    # parameters (the caller's in parity mode, else drawn where the clips are staged), the two streams.  Added by the phases as
+    # they produce them: the built clips (x_real_aug, real_clip, x_fake, x_fake_aug, xf), the first_input writers (first_real,
+    # first_fake: D_V's, D_I's), logits, loss gradients, saved activations.
+
+    def __init__(self, ts, x_real, t_real, inject, input_event):
+        self.x_real, self.t_real, self.inject, self.input_event = x_real, t_real, inject, input_event
+        self.u8 = x_real.dtype == torch.uint8
+        if self.u8:
+            self.n, self.T, self.H, self.W, self.c_img = x_real.shape
+            if not x_real.is_contiguous():
+                raise hl.McgError("uint8 clips must be dense (N,T,H,W,C)")
+        else:
+            self.n, self.c_img, self.T, self.H, self.W = x_real.shape
+        self.hw = self.H * self.W
+        self.seed, self.base = ts.seed, ts.stream_base(ts.iteration, ts.rank)
+        self.t = int(inject['t']) if inject is not None else ts.frame_index(ts.iteration, self.T)
+        self.cgan, self.with_ce = ts.model == 'cgan', ts.model == 'infogan'
+        self.c_valid = self.c_img + (ts.gen.dim_zl if self.cgan else 0)
+        self.par = {}
+        for stage in ts._stages:
+            if inject is not None and stage.name not in inject:
+                raise ValueError(stage.missing)
+            self.par[stage.name] = dict(inject[stage.name]) if inject is not None else {}
+        self.main = torch.cuda.current_stream()
+        self.side = ts.side if ts.side is not None else self.main
+
+    def noise(self, key):
+        return self.inject[key] if self.inject is not None else None
+
+    def rng(self, k):
+        return None if self.inject is not None else (self.seed, self.base + 8 * k)
+
+
 class TrainStep:
     """Holds the three networks, their Adam hyper-parameters and runs update_core on device data."""
 
@@ -273,8 +339,21 @@ class TrainStep:
         self.ada = ada_cfg
         self._ada = hl.ada_state(p0, gen.device) if p0 is not None else None
         self._ev_ada = None
+        # the enabled stages in application order -- the warp, then the augmentation: cutout and the zero border of a translation
+        # stay axis-aligned.  The augmentation has two parameter tensors and a workspace, the warp one matrix tensor.  With a state
+        # block both draw gated by it.
+        self._stages = [stage for stage in (
+            ClipStage('warp', self.warp, {'real': (self.WARP_STREAM_REAL, self.WARP_GATE_REAL), 'fake': (self.WARP_STREAM_FAKE, self.WARP_GATE_FAKE)},
+                      self._ada, hl.warp_draw, hl.warp_draw_gated, hl.warp_fwd, hl.warp_bwd, lambda mat, x: (mat,),
+                      "the warp is on: parity mode needs inject['warp'] = {'real': mat, 'fake': mat}"),
+            ClipStage('augment', self.augment, {'real': (self.AUG_STREAM_REAL, self.AUG_GATE_REAL), 'fake': (self.AUG_STREAM_FAKE, self.AUG_GATE_FAKE)},
+                      self._ada, hl.augment_draw, hl.augment_draw_gated, hl.augment_fwd, hl.augment_bwd,
+                      lambda par, x: (*par, hl.augment_workspace(x.shape[0], x.device)),
+                      "augmentation is on: parity mode needs inject['augment'] = {'real': (geo, col), 'fake': (geo, col)}"),
+        ) if stage.mask]
         self.hyper = hyper or {'image_gen': AdamHyper(), 'image_dis': AdamHyper(), 'video_dis': AdamHyper()}
         self.exchange = exchange
+        self._grad_scale = exchange.grad_scale if exchange else 1.0   # (the collectives SUM: 1 / world goes into the Adam launches)
         # grad_stats: False = off (nothing allocated, the launches of before).  True: every network's Adam update is preceded by the
         # two launches of hl.grad_stats over its flat gradient -- norm, peak, largest element, non-finite count, per-tensor norms,
         # read with grad_stats() -- and stays on the launch it had.  A clipping threshold on an optimizer (AdamHyper.clip) implies the
@@ -381,296 +460,258 @@ class TrainStep:
         perf mode draws them on stream ids base + 44 / 45 (gates: base + 46 / 47).  The clips are warped first, then augmented;
         the result holds 'warp' (the matrices) and 'x_real_aug' / 'x_fake_aug' / 'gx_aug' with the meaning above: what the
         discriminators saw after BOTH stages, and the gradient with respect to it."""
-        gen, di, dv = self.gen, self.dis_i, self.dis_v
-        u8 = x_real.dtype == torch.uint8
-        if u8:
-            n, T, H, W, c_img = x_real.shape
-            if not x_real.is_contiguous():
-                raise hl.McgError("uint8 clips must be dense (N,T,H,W,C)")
+        it = _Iteration(self, x_real, t_real, inject, input_event)
+        self._real_input(it)
+        if it.two_chains:
+            self._start_real_chain(it)
+        self._fake_input(it)
+        self._dis_i_gradient(it)
+        if it.two_chains:
+            self._dis_v_gradient_two_chains(it)
         else:
-            n, c_img, T, H, W = x_real.shape
-        hw = H * W
-        it = self.iteration
-        base = self.stream_base(it, self.rank)
-        seed = self.seed
-        t = int(inject['t']) if inject is not None else self.frame_index(it, T)
+            self._dis_v_gradient_one_batch(it)
+        self._dis_updates(it)
+        if self.ada is not None:
+            self._controller_step(it)
+        self._gen_update(it)
+        self.iteration += 1
+        # (it.par: the enabled stages' parameters under their names, 'warp' / 'augment')
+        res = dict(it.par, x_real_aug=it.x_real_aug, x_fake_aug=it.x_fake_aug, gx_aug=it.gx_aug) if self._stages else {}
+        return {**res, 'x_fake': it.x_fake, 't_fake': it.t_fake, 't': it.t, 'gx_fake': it.gx_fake, 'saved_gen': it.s_gen,
+                'saved_fake_i': it.s_fake_i, 'saved_fake_v': it.s_fake_v, 'saved_i': it.s_i, 'saved_v': it.s_v,
+                'y_real_i': it.y_real_i, 'y_real_v': it.y_real_v, 'y_fake_i': it.y_fake_i, 'y_fake_v': it.y_fake_v}
 
-        def nz(key):
-            return inject[key] if inject is not None else None
+    # ---- the phases of run(), in its order: each takes the iteration's record and says where it enqueues ---------------------
+    def _built_input(self, it, x, which, labels):
+        """A real or generated clip -> (staged, that with label planes, D_V's and D_I's first_input writers for it): current stream"""
+        n, T, hw, t, cp, c_valid = it.n, it.T, it.hw, it.t, self.dis_v.cp0, it.c_valid
+        for stage in self._stages:
+            x = stage.forward(x, which, it)
+        clip = self._concat_label_clip(x, labels) if it.cgan else x
 
-        def rngs(k):
-            return None if inject is not None else (seed, base + 8 * k)
+        def first_v(out, na):
+            hl.bn_act_fwd(n * T * hw, cp, clip, None, hl.ACT_NONE, out, c_valid=c_valid, **na)
 
-        cgan = self.model == 'cgan'
-        with_ce = self.model == 'infogan'
-        cp = dv.cp0
-        aug = self.augment
-        aug_par = None
-        if aug:
-            if inject is None:
-                aug_par = {}                                         # (drawn where the clips are augmented: stream ids base + 40 / 41)
-            elif 'augment' not in inject:
-                raise ValueError("augmentation is on: parity mode needs inject['augment'] = {'real': (geo, col), 'fake': (geo, col)}")
-            else:
-                aug_par = dict(inject['augment'])
-        warp = self.warp
-        warp_par = None
-        if warp:
-            if inject is None:
-                warp_par = {}                                        # (drawn where the clips are warped: stream ids base + 44 / 45)
-            elif 'warp' not in inject:
-                raise ValueError("the warp is on: parity mode needs inject['warp'] = {'real': mat, 'fake': mat}")
-            else:
-                warp_par = dict(inject['warp'])
-        pre = aug or warp                                            # a stage in front of the discriminators: the clips are built first
-
-        def warped(x, which, sid, gate_sid):
-            """x [n][T][H][W][4] -> its warped copy with the matrices of `which` ('real' | 'fake'), on the current stream"""
-            if which not in warp_par:
-                if self._ada is not None:
-                    warp_par[which] = hl.warp_draw_gated(n, H, W, warp, seed, base + sid, base + gate_sid, self._ada, device=self.device)
-                else:
-                    warp_par[which] = hl.warp_draw(n, H, W, warp, seed, base + sid, device=self.device)
-            return hl.warp_fwd(x, c_img, warp_par[which], torch.empty_like(x))
-
-        def augmented(x, which, sid, gate_sid):
-            """x [n][T][H][W][4] -> its augmented copy with the parameters of `which` ('real' | 'fake'), on the current stream"""
-            if which not in aug_par:
-                if self._ada is not None:
-                    aug_par[which] = hl.augment_draw_gated(n, H, W, aug, seed, base + sid, base + gate_sid, self._ada, device=self.device)
-                else:
-                    aug_par[which] = hl.augment_draw(n, H, W, aug, seed, base + sid, device=self.device)
-            geo, col = aug_par[which]
-            return hl.augment_fwd(x, c_img, geo, col, hl.augment_workspace(n, self.device), torch.empty_like(x))
-
-        def staged(x, which):
-            """the warp, then the augmentation: cutout and the zero border of a translation stay axis-aligned"""
-            real = which == 'real'
-            if warp:
-                x = warped(x, which, self.WARP_STREAM_REAL if real else self.WARP_STREAM_FAKE, self.WARP_GATE_REAL if real else self.WARP_GATE_FAKE)
-            if aug:
-                x = augmented(x, which, self.AUG_STREAM_REAL if real else self.AUG_STREAM_FAKE, self.AUG_GATE_REAL if real else self.AUG_GATE_FAKE)
-            return x
-
-        # ------------------------------------------------ forward: real
-        x_real_aug = None
-        if cgan or pre:
-            # label planes (cgan) are part of D's input, and the augmentation reads whole clips: build the device-layout clip once
-            # -- packed without noise, warped, augmented, label planes appended (they are neither) -- then add noise
-            real = {}
-
-            def build_real():
-                tmp = torch.empty((n, T, H, W, lay.pad4(c_img)), device=self.device)
-                (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, lay.pad4(c_img), T, hw, x_real, tmp)
-                if pre:
-                    tmp = staged(tmp, 'real')
-                real['aug'] = tmp if pre else None
-                real['x'] = self._concat_label_clip(tmp, t_real) if cgan else tmp
-            c_valid_r = c_img + (gen.dim_zl if cgan else 0)
-
-            def first_real_v(out, na):
-                hl.bn_act_fwd(n * T * hw, cp, real['x'], None, hl.ACT_NONE, out, c_valid=c_valid_r, **na)
-
-            def first_real_i(out, na):
-                hl.bn_act_fwd(n * hw, cp, real['x'][:, t], None, hl.ACT_NONE, out, c_valid=c_valid_r, rows_per_item=hw,
-                              item_stride=T * hw * cp, **na)
-        else:
-            def first_real_v(out, na):
-                (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, cp, T, hw, x_real, out, **na)
-
-            def first_real_i(out, na):
-                if u8:                                               # frame t of every clip: the clip's item stride, one frame
-                    hl.pack_clip_u8(n, c_img, cp, 1, hw, x_real[:, t], out, stride_n=T * hw * c_img, **na)
-                else:
-                    hl.pack_clip(n, c_img, cp, 1, hw, x_real[:, :, t], out, stride_n=c_img * T * hw, stride_c=T * hw, **na)
-
-        # ------------------------------------------------ forward: D_V on the real clips, as a chain of its own beside G's forward
-        ex = self.exchange
-        main = torch.cuda.current_stream()
-        real_chain = None
-        # (not for 'f32x3': measured 2-3 % SLOWER at 32 / 64 / 128 clips -- its launches are tuned, form by form, at the 2n batch)
-        use_chain = CHAINS and self.side is not None and ex is None and dv.sync_bn is None and dv.precision != 'f32x3' and n >= CHAINS_MIN_N
-        if (cgan or pre) and not (pre and use_chain):
-            build_real()                                             # on the main stream: every reader is ordered behind it
-        if use_chain:
-            cs = self._chain_stream
-            if (self.input_ready_early or input_event is not None) and self._ev_dv_updated is not None and not cgan:
-                cs.wait_event(self._ev_dv_updated)                   # the previous iteration's Adam(D_V)
-                if self._ev_ada is not None:
-                    cs.wait_event(self._ev_ada)                      # ... and its controller step: the gates below read the p it left
-                if input_event is not None:
-                    cs.wait_event(input_event)                       # x_real (otherwise ready by contract)
-            else:
-                cs.wait_stream(main)                                 # x_real (and whatever produced it)
-            if pre:
-                # the augmented real clips are made on the chain stream, which may run ahead of the main stream (input_event /
-                # input_ready_early): its own reader follows in stream order; the main stream -- D_I's side stream and the
-                # one-batch readers are ordered behind it -- waits for the event
-                with torch.cuda.stream(cs):
-                    build_real()
-                    ev = torch.cuda.Event()
-                    ev.record(cs)
-                main.wait_event(ev)
-                for x in {id(v): v for v in real.values() if v is not None}.values():
-                    x.record_stream(main)
-                    if self.side is not None:
-                        x.record_stream(self.side)
-            with torch.cuda.stream(cs), self._dv_chains[0]:
-                real_chain = dv.forward(n, first_real_v, noise=nz('noise_v_real'), rng=rngs(1))
-            x_real.record_stream(cs)
-        # ------------------------------------------------ forward: fake (G needs nothing from D)
-        draw = inject['gen'] if inject is not None else gen.draw(n, (seed, base + 8 * 2))
-        x_fake, s_gen = gen.forward(n, draw)
-        t_fake = draw['labels']
-        if cgan or pre:
-            x_real_aug = real['aug']
-        x_fake_aug = staged(x_fake, 'fake') if pre else None
-        xf = x_fake_aug if pre else x_fake
-        if cgan:
-            xf = self._concat_label_clip(xf, t_fake)
-        c_valid = c_img + (gen.dim_zl if cgan else 0)
-
-        def first_fake_v(out, na):
-            hl.bn_act_fwd(n * T * hw, cp, xf, None, hl.ACT_NONE, out, c_valid=c_valid, **na)
-
-        def first_fake_i(out, na):
-            hl.bn_act_fwd(n * hw, cp, xf[:, t], None, hl.ACT_NONE, out, c_valid=c_valid, rows_per_item=hw,
+        def first_i(out, na):                                        # frame t of every clip: the clip's item stride, one frame
+            hl.bn_act_fwd(n * hw, cp, clip[:, t], None, hl.ACT_NONE, out, c_valid=c_valid, rows_per_item=hw,
                           item_stride=T * hw * cp, **na)
+        return x, clip, (first_v, first_i)
 
-        # ------------------------------------------------ forward: both discriminators on [real | fake]
-        # (model/updater.py:97-98,107-108 as one 2n batch per net; per-call BatchNorm statistics, real first)
-        cd = di.out_channels
-        gs = ex.grad_scale if ex else 1.0
-        side = self.side if self.side is not None else main
-        side.wait_stream(main)                                        # x_fake is ready
-        # ------------------------------------------------ image_dis_optimizer.update(loss_dis, ...)   :111
-        with torch.cuda.stream(side):
-            y_i, s_i = di.forward_groups(n, [dict(first_input=first_real_i, noise=nz('noise_i_real'), rng=rngs(0)),
-                                             dict(first_input=first_fake_i, noise=nz('noise_i_fake'), rng=rngs(3))])
-            y_real_i, y_fake_i = y_i[:n], y_i[n:]
-            g_i = torch.empty((2 * n, cd), device=self.device)      # [d loss / d logits] of (real | fake)
-            di.zero_grad()
-            hl.loss_dis(n, cd, y_real_i, y_fake_i, t_real, t_fake, False, self.loss[0:1], g_i[:n], g_i[n:])
-            di.backward(s_i, g_i, True)
-            work_i = ex.start(di.fp.g) if ex else None
-        # ------------------------------------------------ video_dis_optimizer.update(loss_dis, ...)   :112
-        two_chains = CHAINS and self.side is not None and ex is None and dv.sync_bn is None and real_chain is not None
-        late = []
-        lo, hi = dv.grad_bucket_late()
-        if two_chains:
-            # The real and the fake call as TWO CHAINS on two streams (round 4): the real call needs nothing from G and was queued on
-            # the chain stream BEFORE G's forward (real_chain below); the fake call follows G on the main stream.  One chain's
-            # BatchNorm / activation passes (HBM-bound, 3.3 of 21.5 ms exposed at batch 256 in the one-batch schedule) run beside the
-            # other's GEMMs.  Same kernels on n instead of 2n samples; what the calls share is kept in the reference's order by events
-            # (nets._Net._ordered: running statistics real -> fake, gradient accumulators real -> fake).
-            global chain_iterations
-            chain_iterations += 1
-            cs, (ch_r, ch_f) = self._chain_stream, self._dv_chains
-            y_real_v, s_real = real_chain
-            with ch_f:
-                y_fake_v, s_fake = dv.forward(n, first_fake_v, noise=nz('noise_v_fake'), rng=rngs(4))
-            main.wait_stream(cs)                                     # the real logits
-            y_real_v.record_stream(main)
-            g_v = torch.empty((2 * n, cd), device=self.device)
-            dv.zero_grad()
-            hl.loss_dis(n, cd, y_real_v, y_fake_v, t_real, t_fake, with_ce, self.loss[1:2], g_v[:n], g_v[n:])
-            cs.wait_stream(main)                                     # the loss gradients (and the cleared gradient buffer)
-            g_v.record_stream(cs)
-            with torch.cuda.stream(cs), ch_r:
-                dv.backward(s_real, g_v[:n], True)
-            with ch_f:
-                dv.backward(s_fake, g_v[n:], True)
-            main.wait_stream(cs)
-            s_v = {'n': n, 'G': 2, 'chains': [s_real, s_fake]}
-            del s_real
+    def _build_real_clip(self, it):
+        """The real clips in the device layout, staged, with label planes, and the writers that read them: on the current stream"""
+        # label planes (cgan) are part of D's input, and a stage reads whole clips: the clip is built once -- packed without
+        # noise, warped, augmented, label planes appended (they are neither) -- and the discriminators' first kernels add the noise
+        x = torch.empty((it.n, it.T, it.H, it.W, lay.pad4(it.c_img)), device=self.device)
+        (hl.pack_clip_u8 if it.u8 else hl.pack_clip)(it.n, it.c_img, lay.pad4(it.c_img), it.T, it.hw, it.x_real, x)
+        it.x_real_aug, it.real_clip, it.first_real = self._built_input(it, x, 'real', it.t_real)
+
+    def _real_input(self, it):
+        """Decides the schedule, once, and sets it.first_real.  A clip that is built is built on the main stream, where every reader
+        is ordered behind it -- except with stages under the two-chain schedule: _start_real_chain builds it."""
+        dv = self.dis_v
+        # (not for 'f32x3': measured 2-3 % SLOWER at 32 / 64 / 128 clips -- its launches are tuned, form by form, at the 2n batch)
+        it.two_chains = (CHAINS and self.side is not None and self.exchange is None and dv.sync_bn is None
+                         and dv.precision != 'f32x3' and it.n >= CHAINS_MIN_N)
+        if it.cgan or self._stages:
+            if not (self._stages and it.two_chains):
+                self._build_real_clip(it)
+            return
+        n, c_img, T, hw, t, x_real, u8, cp = it.n, it.c_img, it.T, it.hw, it.t, it.x_real, it.u8, dv.cp0
+
+        def first_v(out, na):
+            (hl.pack_clip_u8 if u8 else hl.pack_clip)(n, c_img, cp, T, hw, x_real, out, **na)
+
+        def first_i(out, na):
+            if u8:                                                   # frame t of every clip: the clip's item stride, one frame
+                hl.pack_clip_u8(n, c_img, cp, 1, hw, x_real[:, t], out, stride_n=T * hw * c_img, **na)
+            else:
+                hl.pack_clip(n, c_img, cp, 1, hw, x_real[:, :, t], out, stride_n=c_img * T * hw, stride_c=T * hw, **na)
+        it.first_real = first_v, first_i
+
+    def _start_real_chain(self, it):
+        """Two-chain schedule only: D_V's forward on the real clips (it.real_chain) on the chain stream, beside G's forward.  That
+        stream waits for the main stream -- or, when the caller vouches for x_real, only for the events of the previous iteration."""
+        cs, main = self._chain_stream, it.main
+        if (self.input_ready_early or it.input_event is not None) and self._ev_dv_updated is not None and not it.cgan:
+            cs.wait_event(self._ev_dv_updated)                       # the previous iteration's Adam(D_V)
+            if self._ev_ada is not None:
+                cs.wait_event(self._ev_ada)                          # ... and its controller step: the gates below read the p it left
+            if it.input_event is not None:
+                cs.wait_event(it.input_event)                        # x_real (otherwise ready by contract)
         else:
-            if real_chain is not None:                              # (decided before G's forward; cannot happen)
-                raise RuntimeError('the real chain ran but the two-chain schedule was not taken')
-            y_v, s_v = dv.forward_groups(n, [dict(first_input=first_real_v, noise=nz('noise_v_real'), rng=rngs(1)),
-                                             dict(first_input=first_fake_v, noise=nz('noise_v_fake'), rng=rngs(4))])
-            y_real_v, y_fake_v = y_v[:n], y_v[n:]
-            g_v = torch.empty((2 * n, cd), device=self.device)
-            dv.zero_grad()
-            hl.loss_dis(n, cd, y_real_v, y_fake_v, t_real, t_fake, with_ce, self.loss[1:2], g_v[:n], g_v[n:])
-            # D_V's gradient is exchanged in two buckets: dc4/W..dc5/b (76 % of the bytes) is final after the
-            # first two layers of the backward pass and travels while dc3..dc1 are still being computed
-            dv.backward(s_v, g_v, True, on_late_bucket=(lambda: late.append(ex.start(dv.fp.g[lo:hi]))) if ex else None)
-        with torch.cuda.stream(side):
-            if ex:
-                ex.finish(work_i)                                    # D_I's exchange overlapped D_V's backward
-            adam_update(di, self.hyper['image_dis'], gs)
-        if ex:
-            rest = [ex.start(dv.fp.g[:lo]), ex.start(dv.fp.g[hi:])]
+            cs.wait_stream(main)                                     # x_real (and whatever produced it)
+        if self._stages:
+            # the augmented real clips are made on the chain stream, which may run ahead of the main stream (input_event /
+            # input_ready_early): its own reader follows in stream order; the main stream -- D_I's side stream and the
+            # one-batch readers are ordered behind it -- waits for the event
+            with torch.cuda.stream(cs):
+                self._build_real_clip(it)
+                ev = cs.record_event()
+            main.wait_event(ev)
+            for x in ([it.x_real_aug] if it.real_clip is it.x_real_aug else [it.x_real_aug, it.real_clip]):
+                x.record_stream(main)
+                x.record_stream(self.side)                           # (the two-chain schedule has side streams)
+        with torch.cuda.stream(cs), self._dv_chains[0]:
+            it.real_chain = self.dis_v.forward(it.n, it.first_real[0], noise=it.noise('noise_v_real'), rng=it.rng(1))
+        it.x_real.record_stream(cs)
+
+    def _fake_input(self, it):
+        """G's forward (it needs nothing from D), the stages, the label planes, the writers: main stream, waits for nothing"""
+        draw = it.inject['gen'] if it.inject is not None else self.gen.draw(it.n, it.rng(2))
+        it.x_fake, it.s_gen = self.gen.forward(it.n, draw)
+        it.t_fake = draw['labels']
+        it.x_fake_aug, it.xf, it.first_fake = self._built_input(it, it.x_fake, 'fake', it.t_fake)
+
+    def _dis_loss(self, it, net, slot, y_real, y_fake, with_ce):
+        """[d loss / d logits] of (real | fake) for one discriminator, its gradient buffer cleared in front: current stream"""
+        n, cd = it.n, net.out_channels
+        g = torch.empty((2 * n, cd), device=self.device)
+        net.zero_grad()
+        hl.loss_dis(n, cd, y_real, y_fake, it.t_real, it.t_fake, with_ce, self.loss[slot:slot + 1], g[:n], g[n:])
+        return g
+
+    def _bucketed_exchange(self, net):
+        """A network's gradient exchange in two buckets -> (on_late_bucket for its backward pass, finish); no exchange: (None, no-op)"""
+        # finish() sends the two remaining slices and makes the current stream wait for all three;
+        # the late bucket (D_V: dc4/W..dc5/b, 76 % of the bytes) is final after the first two layers of the backward pass and
+        # travels while the rest is still being computed
+        ex = self.exchange
+        if ex is None:
+            return None, lambda: None
+        lo, hi = net.grad_bucket_late()
+        late = []
+
+        def finish():
+            rest = [ex.start(net.fp.g[:lo]), ex.start(net.fp.g[hi:])]
             for h in late + rest:
                 ex.finish(h)
-        adam_update(dv, self.hyper['video_dis'], gs)
-        if self._dv_chains is not None:                               # (what the next iteration's real chain has to wait for)
-            if self._ev_dv_updated is None:
-                self._ev_dv_updated = torch.cuda.Event()
-            self._ev_dv_updated.record(main)
-        main.wait_stream(side)                                        # D_I's logits and updated weights (Q5)
-        if self.ada is not None:
-            # the controller's step, where both discriminators' real logits are visible; every draw of this iteration is behind it
-            # (the chain stream's through main.wait_event above), the next iteration's follow in stream order or wait for the event
-            cfg = self.ada
-            hl.ada_update(y_real_v, y_real_i, cfg['target'], cfg['interval'] * n / (cfg['kimg'] * 1000.0), cfg['interval'], self._ada)
-            if self._dv_chains is not None:
-                if self._ev_ada is None:
-                    self._ev_ada = torch.cuda.Event()
-                self._ev_ada.record(main)
-        # ------------------------------------------------ image_gen_optimizer.update(loss_gen, ...)   :113
+        return (lambda: late.append(ex.start(net.fp.g[lo:hi]))), finish
+
+    def _dis_i_gradient(self, it):
+        """D_I's forward, loss, backward, and its exchange started: on the side stream, which first waits for the main stream"""
+        # image_dis_optimizer.update(loss_dis, ...) (model/updater.py:111) with D_I on [real | fake] as one 2n batch (:97,107;
+        # per-call BatchNorm statistics, real first)
+        di, n = self.dis_i, it.n
+        it.side.wait_stream(it.main)                                 # x_fake is ready
+        with torch.cuda.stream(it.side):
+            y_i, it.s_i = di.forward_groups(n, [dict(first_input=it.first_real[1], noise=it.noise('noise_i_real'), rng=it.rng(0)),
+                                                dict(first_input=it.first_fake[1], noise=it.noise('noise_i_fake'), rng=it.rng(3))])
+            it.y_real_i, it.y_fake_i = y_i[:n], y_i[n:]
+            it.g_i = self._dis_loss(it, di, 0, it.y_real_i, it.y_fake_i, False)
+            di.backward(it.s_i, it.g_i, True)
+            it.work_i = self.exchange.start(di.fp.g) if self.exchange else None
+
+    def _dis_v_gradient_one_batch(self, it):
+        """D_V's forward, loss, backward with its late bucket sent, one-batch form: on the main stream, waits for nothing more"""
+        # video_dis_optimizer.update(loss_dis, ...) (:112) with D_V on [real | fake] as one 2n batch (:98,108)
+        dv, n = self.dis_v, it.n
+        y_v, it.s_v = dv.forward_groups(n, [dict(first_input=it.first_real[0], noise=it.noise('noise_v_real'), rng=it.rng(1)),
+                                            dict(first_input=it.first_fake[0], noise=it.noise('noise_v_fake'), rng=it.rng(4))])
+        it.y_real_v, it.y_fake_v = y_v[:n], y_v[n:]
+        it.g_v = self._dis_loss(it, dv, 1, it.y_real_v, it.y_fake_v, it.with_ce)
+        on_late, it.finish_v = self._bucketed_exchange(dv)
+        dv.backward(it.s_v, it.g_v, True, on_late_bucket=on_late)
+
+    def _dis_v_gradient_two_chains(self, it):
+        """The same, two-chain form: the fake call on the main stream, the real half's backward on the chain stream.  The main stream
+        waits for the chain stream twice (the real logits; that backward), the chain stream once for the main stream (the loss)."""
+        # The real and the fake call as TWO CHAINS on two streams (round 4): the real call needs nothing from G and was queued on
+        # the chain stream BEFORE G's forward (_start_real_chain); the fake call follows G on the main stream.  One chain's
+        # BatchNorm / activation passes (HBM-bound, 3.3 of 21.5 ms exposed at batch 256 in the one-batch schedule) run beside the
+        # other's GEMMs.  Same kernels on n instead of 2n samples; what the calls share is kept in the reference's order by events
+        # (nets._Net._ordered: running statistics real -> fake, gradient accumulators real -> fake).
+        global chain_iterations
+        chain_iterations += 1
+        dv, n, main = self.dis_v, it.n, it.main
+        cs, (ch_r, ch_f) = self._chain_stream, self._dv_chains
+        it.y_real_v, s_real = it.real_chain
+        with ch_f:
+            it.y_fake_v, s_fake = dv.forward(n, it.first_fake[0], noise=it.noise('noise_v_fake'), rng=it.rng(4))
+        main.wait_stream(cs)                                         # the real logits
+        it.y_real_v.record_stream(main)
+        it.g_v = self._dis_loss(it, dv, 1, it.y_real_v, it.y_fake_v, it.with_ce)
+        cs.wait_stream(main)                                         # the loss gradients (and the cleared gradient buffer)
+        it.g_v.record_stream(cs)
+        with torch.cuda.stream(cs), ch_r:
+            dv.backward(s_real, it.g_v[:n], True)
+        with ch_f:
+            dv.backward(s_fake, it.g_v[n:], True)
+        main.wait_stream(cs)
+        it.s_v = {'n': n, 'G': 2, 'chains': [s_real, s_fake]}
+
+    def _record_for_next(self, name, stream):
+        """record on `stream` the event self.<name> that the NEXT iteration's real chain waits for: made at first use, with chains only"""
+        if self._dv_chains is not None:
+            if getattr(self, name) is None:
+                setattr(self, name, torch.cuda.Event())
+            getattr(self, name).record(stream)
+
+    def _dis_updates(self, it):
+        """Adam(D_I) on the side stream, Adam(D_V) on the main stream, each behind its exchange; then main waits for the side stream"""
+        with torch.cuda.stream(it.side):
+            if self.exchange:
+                self.exchange.finish(it.work_i)                      # D_I's exchange overlapped D_V's backward
+            adam_update(self.dis_i, self.hyper['image_dis'], self._grad_scale)
+        if not it.two_chains:                                        # (that schedule is taken without an exchange only)
+            it.finish_v()
+        adam_update(self.dis_v, self.hyper['video_dis'], self._grad_scale)
+        self._record_for_next('_ev_dv_updated', it.main)
+        it.main.wait_stream(it.side)                                 # D_I's logits and updated weights (Q5)
+
+    def _controller_step(self, it):
+        """With `ada`: the controller's launch on the main stream, where both discriminators' real logits are visible"""
+        # every draw of this iteration is behind it (the chain stream's through main.wait_event in _start_real_chain), the next
+        # iteration's follow in stream order or wait for the event recorded here
+        cfg = self.ada
+        hl.ada_update(it.y_real_v, it.y_real_i, cfg['target'], cfg['interval'] * it.n / (cfg['kimg'] * 1000.0), cfg['interval'], self._ada)
+        self._record_for_next('_ev_ada', it.main)
+
+    def _gen_update(self, it):
+        """image_gen_optimizer.update(loss_gen, ...) (:113), through the ALREADY UPDATED discriminators (Q5) and the stages' adjoints.
+        Main stream; with overlap D_I's layers run on the side stream, which waits for the main stream and is waited for."""
+        gen, di, dv = self.gen, self.dis_i, self.dis_v
+        n, T, H, W, hw, t, cp = it.n, it.T, it.H, it.W, it.hw, it.t, dv.cp0
         gen.zero_grad()
-        gi, gv = g_i[:n], g_v[:n]                                    # buffers reused: D's backward has consumed them
-        hl.loss_gen(n, cd, y_fake_i, y_fake_v, t_fake, with_ce, self.loss[2:3], gi, gv)
-        gx = torch.empty_like(xf)
-        s_fake_v, s_fake_i = dv.select_group(s_v, 1), di.select_group(s_i, 1)
+        gi, gv = it.g_i[:n], it.g_v[:n]                              # buffers reused: D's backward has consumed them
+        hl.loss_gen(n, di.out_channels, it.y_fake_i, it.y_fake_v, it.t_fake, it.with_ce, self.loss[2:3], gi, gv)
+        gx = torch.empty_like(it.xf)
+        it.s_fake_v, it.s_fake_i = dv.select_group(it.s_v, 1), di.select_group(it.s_i, 1)
         gi_geom = hl.make_geom(n, 1, H, W, cp, di.chans[1], 1, x_stride0=T * hw * cp, precision=di.gemm_precision, ci_valid=di.chans[0])
         if self.side is not None:
             # the two discriminators' input gradients are independent until they meet in frame t of the clip gradient:
             # D_I's layers 5..2 (small kernels) run on the side stream beside D_V's; its LAST launch -- the input gradient of
             # dc1, accumulated onto frame t of what D_V's pass wrote -- follows on the main stream once both are done
-            self.side.wait_stream(main)                              # loss_gen's gradients
+            self.side.wait_stream(it.main)                           # loss_gen's gradients
             with torch.cuda.stream(self.side):
-                last_i = di.backward(s_fake_i, gi, False, gx=gx[:, t], gx_geom=gi_geom, gx_accumulate=True, defer_gx=True)
+                last_i = di.backward(it.s_fake_i, gi, False, gx=gx[:, t], gx_geom=gi_geom, gx_accumulate=True, defer_gx=True)
             gi.record_stream(self.side)
-            dv.backward(s_fake_v, gv, False, gx=gx)                  # new D_V weights, old activations (Q5)
-            main.wait_stream(self.side)
+            dv.backward(it.s_fake_v, gv, False, gx=gx)               # new D_V weights, old activations (Q5)
+            it.main.wait_stream(self.side)
             last_i()
         else:
-            dv.backward(s_fake_v, gv, False, gx=gx)                  # new D_V weights, old activations (Q5)
-            di.backward(s_fake_i, gi, False, gx=gx[:, t], gx_geom=gi_geom, gx_accumulate=True)
-        if cgan:                                                     # label planes carry no gradient to G: the clip's channels alone
-            gx = hl.concat_label_planes(gx, c_img, 0, None, torch.empty_like(x_fake))
-        gx_aug = None
-        if pre:                                                      # the adjoints of the generated clips' stages, last stage first
-            gx_aug = gx
-            if aug:
-                gx = hl.augment_bwd(gx, c_img, *aug_par['fake'], hl.augment_workspace(n, self.device), torch.empty_like(gx))
-            if warp:
-                gx = hl.warp_bwd(gx, c_img, warp_par['fake'], torch.empty_like(gx))
-        late_g = []
-        lo_g, hi_g = gen.grad_bucket_late()
-        gen.backward(s_gen, gx, on_late_bucket=(lambda: late_g.append(ex.start(gen.fp.g[lo_g:hi_g]))) if ex else None)
-        if ex:
-            rest_g = [ex.start(gen.fp.g[:lo_g]), ex.start(gen.fp.g[hi_g:])]
-            for h in late_g + rest_g:
-                ex.finish(h)
-        adam_update(gen, self.hyper['image_gen'], gs)
-        self.iteration += 1
-        res = {} if not pre else {'x_real_aug': x_real_aug, 'x_fake_aug': x_fake_aug, 'gx_aug': gx_aug}
-        if aug:
-            res['augment'] = aug_par
-        if warp:
-            res['warp'] = warp_par
-        return {**res, 'x_fake': x_fake, 't_fake': t_fake, 't': t, 'gx_fake': gx, 'saved_gen': s_gen, 'saved_fake_i': s_fake_i, 'saved_fake_v': s_fake_v,
-                'saved_i': s_i, 'saved_v': s_v,
-                'y_real_i': y_real_i, 'y_real_v': y_real_v, 'y_fake_i': y_fake_i, 'y_fake_v': y_fake_v}
+            dv.backward(it.s_fake_v, gv, False, gx=gx)               # new D_V weights, old activations (Q5)
+            di.backward(it.s_fake_i, gi, False, gx=gx[:, t], gx_geom=gi_geom, gx_accumulate=True)
+        if it.cgan:                                                  # label planes carry no gradient to G: the clip's channels alone
+            gx = hl.concat_label_planes(gx, it.c_img, 0, None, torch.empty_like(it.x_fake))
+        it.gx_aug = gx
+        for stage in reversed(self._stages):                         # the adjoints of the generated clips' stages, last stage first
+            gx = stage.adjoint(gx, 'fake', it)
+        it.gx_fake = gx
+        on_late, finish = self._bucketed_exchange(gen)
+        gen.backward(it.s_gen, gx, on_late_bucket=on_late)
+        finish()
+        adam_update(gen, self.hyper['image_gen'], self._grad_scale)
 
     def grad_stats(self):
         """{network: {'grad_norm', 'grad_norm_peak' (since the last read; zeroed behind it), 'grad_max', 'nonfinite', 'clip_rate',
         'skipped' (updates so far), 'tensors': {parameter: norm}}} of the last iteration, for every network that keeps the
         statistics -- forces a host sync, like losses().  Norms are those of the gradient the update saw (the mean over the ranks)."""
         return {name: net.gstats.read() for name, net in self._nets.items() if net.gstats is not None}
+
+    @property
+    def has_ada_state(self):
+        """does the step hold an augmentation state block (augment_p / ada): is there something for ada_stats() to report?"""
+        return self._ada is not None
 
     def ada_state(self):
         """the eight doubles of the augmentation's state block (hl.ADA_*) as a float64 array, or None without augment_p / ada --

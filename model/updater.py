@@ -50,7 +50,7 @@ class Updater:
         ada = kwargs.pop('ada', None)
         if kwargs:
             raise TypeError('unexpected arguments: %s' % sorted(kwargs))
-        self._ada_report = _step.check_augment_gate(augment, augment_p, ada, exchange, warp)[0] is not None
+        _step.check_augment_gate(augment, augment_p, ada, exchange, warp)     # (refused before models and optimizers are touched)
         self.iteration = 0
         self.observation = {}
         hyper = {k: self._optimizers[k].hyper() for k in ('image_gen', 'image_dis', 'video_dis')}
@@ -185,7 +185,7 @@ class Updater:
             self.observation = dict(l)
             for name, link in self.links().items():
                 self.tf_writer.add_scalar('loss:{}'.format(link.name), l['%s/loss' % name], self.epoch)
-            if self._ada_report:
+            if self._step.has_ada_state:
                 st = self._step.ada_stats()
                 for key, tag, v in (('augment/p', 'augment:p', st['p']),
                                     ('video_dis/rt', 'rt:{}'.format(self.video_dis.name), st['rt_video']),
