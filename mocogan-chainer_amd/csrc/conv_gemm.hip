@@ -3640,8 +3640,11 @@ int launch_wgrad_c4(const Geom& g, const float* x, const float* y, float* dw, hi
     p.g = g; p.x = x; p.y = y; p.dw = dw;
     // (row block, batch item) pairs, at most 512 blocks: with more pairs a block walks several items (every block ends in
     // 64 x kt * 48 float atomics onto the same dw: measured at 512 clips 0.458-0.472 ms with 1024 blocks, 0.397-0.406 with 512,
-    // 0.412-0.420 with 256); with fewer than 256 the frames of an item are split as well (each part re-reads kt - 1 frames;
-    // >= 2 steps per part)
+    // 0.412-0.420 with 256); with fewer than 256 the frames of an item are split as well (each part re-reads kt - 1 frames).
+    // tsplit doubles while To >= 4 tsplit, i.e. >= 2 steps per part ON AVERAGE: a part is ceil(To / tsplit) frames, so the last
+    // live part may hold a single step and the parts behind it none (To = 13: 4, 4, 4, 1; To = 9: 3, 3, 3, 0; To = 17: 3 x 5, 2, 0, 0).
+    // Both kernels take either: a one-step part has nothing to prefetch (`more` / `to + 1 < t1` are false), an empty part's block
+    // runs no step and adds zeros (tests/test_gpu_c4_guard.py runs these plans in the guard arena)
     const int hblocks = g.Ho / R;
     p.nsplit = g.N; p.tsplit = 1;
     if (hblocks * p.nsplit > 512) p.nsplit = 512 / hblocks > 0 ? 512 / hblocks : 1;
