@@ -134,7 +134,8 @@ typedef struct mcg_conv_geom {
  *     and with the gradient statistics (mcg_grad_stats*, mcg_adam_wd_ctl added; no argument list changed)
  *     and with the adaptive augmentation (mcg_augment_draw_gated, mcg_ada_update added; no argument list changed)
  *     and with the geometric augmentation (mcg_warp_* added; no argument list changed)
- *     and with the nearest-neighbour metrics (mcg_knn_* added; no argument list changed). */
+ *     and with the nearest-neighbour metrics (mcg_knn_* added; no argument list changed)
+ *     and with the motion and content metrics (mcg_mc_* added; no argument list changed). */
 #define MCG_ABI_VERSION 8
 int mcg_version(void);
 
@@ -681,6 +682,33 @@ int mcg_knn_sqdist(int M, int N, int D, const int8_t* a, const int32_t* na, cons
 int mcg_knn_smallest(int M, int N, const int32_t* dist, int64_t ld, int k, int exclude_self, int64_t self_col0, int32_t* val, int32_t* idx,
                      void* stream);
 int mcg_knn_ball_counts(int M, int N, const int32_t* dist, int64_t ld, const int32_t* radius, int32_t* counts, void* stream);
+
+/* ---- motion and content metrics on the int8 matrix pipe (csrc/motion.hip) ------------------------------------------------------
+ * Average Content Distance (after Tulyakov et al. 2018, section 5), a temporal lag profile and motion descriptors for the
+ * nearest-neighbour metrics all reduce to squared distances between the frames of ONE clip, plus two reductions (no reference
+ * counterpart: the reference has no metric).  A row of mcg_knn_descriptors is row-major over (T, 64/pool, 64/pool, C), so desc seen
+ * as [N][T][Df], Df = (64/pool)^2 C, holds the per-frame descriptors: Df is a multiple of 64 and at most 3072, and the largest
+ * frame distance is 255^2 * 3072 = 199 756 800.  mocogan-chainer_amd/metrics.py (MotionContent) composes the stages.
+ * No atomics, no workspace, no address that depends on data; one launch each; indices past an extent are clamped on load and
+ * never stored.
+ *
+ * mcg_mc_frame_sqdist: dist[n][s][t] = sum_d (desc[n][s][d] - desc[n][t][d])^2 for desc [N][T][Df] (16-byte aligned), dist
+ *   [N][T][T], exact in int32, on v_mfma_i32_16x16x64_i8 as G[s][s] + G[t][t] - 2 G[s][t] with G the clip's Gram matrix: the norms
+ *   are G's diagonal, the diagonal of dist is exactly 0 and dist is exactly symmetric.  2 <= T <= 64 (padded to tiles of 16 in
+ *   registers only); Df a multiple of 64 in 64..3072; anything else is MCG_ERR_UNSUPPORTED.  One wave per clip, four clips per
+ *   workgroup; every byte of desc is read once.
+ * mcg_mc_clip_stats: pair_sum[n] = sum_{s<t} sqrt((double) dist[n][s][t]), added in double in the fixed order s ascending, then t
+ *   ascending, one accumulator chain per clip: the same input gives the same bits.  lag_sum[n][l] = sum_{t=0}^{T-1-l}
+ *   dist[n][t][t+l] for l = 0..T-1 (lag_sum [N][T]; l = 0 sums the diagonal), exact in int64.  2 <= T <= 64, else
+ *   MCG_ERR_UNSUPPORTED.  One wave per clip.
+ * mcg_mc_motion_descriptors: mdesc[n][t][d] = (desc[n][t+1][d] - desc[n][t][d]) >> 1 for t = 0..T-2 (arithmetic shift: the floor of
+ *   half the difference; -255 -> -128, 255 -> 127, -1 -> -1, 1 -> 0: every value fits int8 with no clamp), mdesc [N][(T-1) Df];
+ *   mnorms[n] = the sum of squares of row n (at most 2^14 (T-1) Df).  desc and mdesc 16-byte aligned.  T >= 2, Df a multiple of 64
+ *   and (T-1) Df <= 32768 -- the rows are valid operands of mcg_knn_sqdist -- else MCG_ERR_UNSUPPORTED.  One workgroup per clip.
+ * MCG_ERR_BAD_ARG, refused on the host before any launch: a null pointer, a non-positive extent, a misaligned desc / mdesc. */
+int mcg_mc_frame_sqdist(int N, int T, int Df, const int8_t* desc, int32_t* dist, void* stream);
+int mcg_mc_clip_stats(int N, int T, const int32_t* dist, double* pair_sum, int64_t* lag_sum, void* stream);
+int mcg_mc_motion_descriptors(int N, int T, int Df, const int8_t* desc, int8_t* mdesc, int32_t* mnorms, void* stream);
 
 #ifdef __cplusplus
 }

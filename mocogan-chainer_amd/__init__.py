@@ -6,7 +6,8 @@
 ``nets.py``    ImageGenerator / ImageDiscriminator / VideoDiscriminator on those kernels
 ``step.py``    one training iteration (losses, hand-scheduled backward, Adam) + data-parallel exchange
 ``metrics.py`` sliced Wasserstein distance between two sets of uint8 clips (evaluate_swd.py); nearest-neighbour precision / recall,
-             density / coverage and a data-copying score on the int8 matrix pipe (evaluate_knn.py)
+             density / coverage and a data-copying score on the int8 matrix pipe (evaluate_knn.py); content distance, lag profile, motion k-NN
+             figures and the content x motion grid (evaluate_motion.py)
 The reference-facing API (``model.net``, ``model.updater``, ``train.py``) at the repo root is a
 thin layer over these modules.
 """

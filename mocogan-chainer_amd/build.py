@@ -4,7 +4,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/conv_gemm.hip", "csrc/small_ops.hip", "csrc/metrics.hip", "csrc/knn.hip"]
+SOURCES = ["csrc/conv_gemm.hip", "csrc/small_ops.hip", "csrc/metrics.hip", "csrc/knn.hip", "csrc/motion.hip"]
 
 
 def lib_path():
@@ -38,7 +38,7 @@ def _stale():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -O3 -fPIC -> lib/libmocogan_hip.so (in-tree).  The conv GEMM source is compiled as
-    three translation units (one per pass, -DMCG_TU=1..3) next to small_ops.hip, metrics.hip and knn.hip, all six in parallel, then linked."""
+    three translation units (one per pass, -DMCG_TU=1..3) next to small_ops.hip, metrics.hip, knn.hip and motion.hip, all seven in parallel, then linked."""
     if not force and not _stale():
         return lib_path()
     os.makedirs(os.path.join(HERE, "lib"), exist_ok=True)
@@ -51,6 +51,7 @@ def build(force=False, verbose=False):
     units.append(("small_ops.o", [os.path.join(HERE, "csrc/small_ops.hip")]))
     units.append(("metrics.o", [os.path.join(HERE, "csrc/metrics.hip")]))
     units.append(("knn.o", [os.path.join(HERE, "csrc/knn.hip")]))
+    units.append(("motion.o", [os.path.join(HERE, "csrc/motion.hip")]))
     procs = []
     for obj, args in units:
         cmd = common + args + ["-c", "-o", os.path.join(objdir, obj)]

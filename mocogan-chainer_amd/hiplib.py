@@ -122,6 +122,9 @@ SIGNATURES = {
     "mcg_knn_sqdist": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I64, _P]),
     "mcg_knn_smallest": (_I, [_I, _I, _P, _I64, _I, _I, _I64, _P, _P, _P]),
     "mcg_knn_ball_counts": (_I, [_I, _I, _P, _I64, _P, _P, _P]),
+    "mcg_mc_frame_sqdist": (_I, [_I, _I, _I, _P, _P, _P]),
+    "mcg_mc_clip_stats": (_I, [_I, _I, _P, _P, _P, _P]),
+    "mcg_mc_motion_descriptors": (_I, [_I, _I, _I, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 8          # MCG_ABI_VERSION of include/mocogan_hip.h these prototypes were written against
@@ -1459,3 +1462,52 @@ def knn_ball_counts(dist, radius, n=None, counts=None):
     _check(load().mcg_knn_ball_counts(m, n, _p(_dense(dist), torch.int32), ld, _p(_dense(radius), torch.int32),
                                       _p(_dense(counts), torch.int32), _stream()), "mcg_knn_ball_counts")
     return counts
+
+
+# ---- motion and content metrics (include/mocogan_hip.h: mcg_mc_*; composed by metrics.py) -----------------------------------------
+MC_MAX_T, MC_MAX_DF = 64, 3072
+
+
+def _frames(desc, name):
+    if desc.dim() != 3:
+        raise McgError("%s: int8 per-frame descriptors (N,T,Df), got %s" % (name, tuple(desc.shape)))
+    return desc.shape
+
+
+def mc_frame_sqdist(desc, dist=None):
+    """int8 desc (N,T,Df) -> dist [N][T][T] int32: the exact squared distances between the frames of every clip"""
+    n, t, df = _frames(desc, "mc_frame_sqdist")
+    dist = torch.empty(n, t, t, dtype=torch.int32, device=desc.device) if dist is None else dist
+    if dist.numel() != n * t * t:
+        raise McgError("mc_frame_sqdist: dist %s does not fit %d x %d x %d" % (tuple(dist.shape), n, t, t))
+    _check(load().mcg_mc_frame_sqdist(n, t, df, _p(_dense(desc), torch.int8), _p(_dense(dist), torch.int32), _stream()), "mcg_mc_frame_sqdist")
+    return dist
+
+
+def mc_clip_stats(dist, pair_sum=None, lag_sum=None):
+    """int32 dist (N,T,T) -> (pair_sum [N] float64: the sum over s < t of sqrt(dist[n][s][t]) in a fixed order, lag_sum [N][T] int64:
+    the sums of the diagonals)"""
+    if dist.dim() != 3 or dist.shape[1] != dist.shape[2]:
+        raise McgError("mc_clip_stats: int32 dist (N,T,T), got %s" % (tuple(dist.shape),))
+    n, t = dist.shape[:2]
+    pair_sum = torch.empty(n, dtype=torch.float64, device=dist.device) if pair_sum is None else pair_sum
+    lag_sum = torch.empty(n, t, dtype=torch.int64, device=dist.device) if lag_sum is None else lag_sum
+    if pair_sum.numel() != n or lag_sum.numel() != n * t:
+        raise McgError("mc_clip_stats: pair_sum %s / lag_sum %s do not fit %d x %d" % (tuple(pair_sum.shape), tuple(lag_sum.shape), n, t))
+    _check(load().mcg_mc_clip_stats(n, t, _p(_dense(dist), torch.int32), _p(_dense(pair_sum), torch.float64), _p(_dense(lag_sum), torch.int64),
+                                    _stream()), "mcg_mc_clip_stats")
+    return pair_sum, lag_sum
+
+
+def mc_motion_descriptors(desc, mdesc=None, mnorms=None):
+    """int8 desc (N,T,Df) -> (mdesc [N][(T-1) Df] int8: the halved differences of consecutive frames (floor), mnorms [N] int32: the
+    rows' sums of squares): operands of knn_sqdist.  mdesc / mnorms may be views of a set's matrices at the chunk's rows."""
+    n, t, df = _frames(desc, "mc_motion_descriptors")
+    d = (t - 1) * df
+    mdesc = torch.empty(n, d, dtype=torch.int8, device=desc.device) if mdesc is None else mdesc
+    mnorms = torch.empty(n, dtype=torch.int32, device=desc.device) if mnorms is None else mnorms
+    if mdesc.numel() != n * d or mnorms.numel() != n:
+        raise McgError("mc_motion_descriptors: mdesc %s / mnorms %s do not fit %d x %d" % (tuple(mdesc.shape), tuple(mnorms.shape), n, d))
+    _check(load().mcg_mc_motion_descriptors(n, t, df, _p(_dense(desc), torch.int8), _p(_dense(mdesc), torch.int8),
+                                            _p(_dense(mnorms), torch.int32), _stream()), "mcg_mc_motion_descriptors")
+    return mdesc, mnorms

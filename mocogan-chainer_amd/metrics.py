@@ -7,7 +7,12 @@ layout, no identity, no motion beyond patch_frames frames.
 
 KnnMetrics, below it, is the complement: nearest-neighbour precision / recall, density / coverage and a data-copying score on
 whole-clip descriptors, composed from the mcg_knn_* stages (exact integer distances on the int8 matrix pipe).
+
+MotionContent, last, looks inside a clip: the distances between its own frames (Average Content Distance, a lag profile), the k-NN
+figures on motion descriptors, and the content x motion grid, composed from the mcg_mc_* stages.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -223,3 +228,114 @@ class KnnMetrics:
             less, equal = int((holdout.n - hi_).sum()), int((hi_ - lo_).sum())       # pairs with dF < dH, with dF == dH
             out['copy_auc'] = (2 * less + equal) / (2 * fake.n * holdout.n)
         return out
+
+
+# ---- motion and content: frame distances inside a clip, a lag profile, k-NN on motion descriptors, the code grid (mcg_mc_*) ---------
+class MotionSet:
+    """One set of clips for MotionContent: pair_sum [n] float64 and lag_sum [n][T] int64 on the host (mcg_mc_clip_stats), the
+    whole-clip KnnSet `clips` and the motion KnnSet `motion` (halved differences of consecutive frames) on the device."""
+
+    def __init__(self, clips, motion, pair_sum, lag_sum):
+        self.clips, self.motion, self.pair_sum, self.lag_sum = clips, motion, pair_sum, lag_sum
+        self.n, self.frames = lag_sum.shape
+        self.frame_dim = clips.dim // self.frames
+        self.shape, self.pool = clips.shape, clips.pool
+
+
+class MotionContent:
+    """What a clip's frames do to one another, composed from the mcg_mc_* and mcg_knn_* stages of libmocogan_hip.so: the mean
+    pairwise frame distance of a clip (Average Content Distance after Tulyakov et al. 2018, section 5, in the descriptor space of
+    KnnMetrics), the temporal structure function (frame distance against lag), the k-NN figures of KnnMetrics on motion
+    descriptors, and for a content x motion grid of generated clips how far each code sets what it is named after.  The frame
+    distances are exact integers from the int8 matrix pipe; the figures equal tests/motion_ref.py's (acd up to the rounding of a
+    sum of square roots).
+
+    What the numbers are not: the frame distance is L2 on pooled bytes, so content means appearance, not identity; the paper's ACD
+    uses OpenFace features or frame-mean colour -- this is the same statistic in another feature space; the motion descriptors are
+    difference images, and a difference image still depends on what moves; every k-NN figure depends on the set sizes and on k."""
+
+    def __init__(self, k=5, pool=4, row_block=4096, device='cuda'):
+        self.knn = KnnMetrics(k, pool, row_block, device)
+        self.k, self.pool, self.row_block, self.device = k, pool, row_block, self.knn.device
+
+    def clip_set(self, chunks):
+        """chunks: uint8 (N_i, T, 64, 64, C) arrays / tensors as KnnMetrics.descriptors takes them -> the MotionSet of their
+        concatenation.  Per chunk: descriptors, frame distances (a scratch block, reused), clip statistics, motion descriptors.  A
+        clip's rows depend on that clip alone, so the chunking changes no bit."""
+        desc, norms, mdesc, mnorms, pair, lag, shape, scratch = [], [], [], [], [], [], None, None
+        for chunk in chunks:
+            if len(chunk) == 0:
+                continue
+            if shape is None and len(chunk.shape) == 5 and not 2 <= chunk.shape[1] <= hl.MC_MAX_T:
+                raise ValueError('frame distances need clips of 2..%d frames, got %d' % (hl.MC_MAX_T, chunk.shape[1]))
+            # refuses other shapes, and rows past 32768 bytes ('use a larger pool'): a motion row, (T - 1) Df bytes, is shorter than that
+            part = self.knn.descriptors([chunk])
+            if shape is None:
+                shape = part.shape
+                T = shape[0]
+            elif part.shape != shape:
+                raise ValueError('chunks differ in shape: %s and %s' % (shape, part.shape))
+            frames = part.desc.view(part.n, T, part.dim // T)
+            if scratch is None or scratch.shape[0] < part.n:
+                scratch = torch.empty(part.n, T, T, dtype=torch.int32, device=self.device)
+            ps, ls = hl.mc_clip_stats(hl.mc_frame_sqdist(frames, scratch[:part.n]))
+            md, mn = hl.mc_motion_descriptors(frames)
+            for lst, v in ((desc, part.desc), (norms, part.norms), (mdesc, md), (mnorms, mn), (pair, ps), (lag, ls)):
+                lst.append(v)
+        if not desc:
+            raise ValueError('no clips')
+        cat = lambda v: v[0] if len(v) == 1 else torch.cat(v)        # (copies, no arithmetic)
+        clips = KnnSet(cat(desc), cat(norms), shape, self.pool)
+        motion = KnnSet(cat(mdesc), cat(mnorms), shape, self.pool)
+        return MotionSet(clips, motion, cat(pair).cpu().numpy(), cat(lag).cpu().numpy())
+
+    def summary(self, s):
+        """{'acd': the mean over clips and frame pairs of the frame distance as an RMS difference per descriptor byte (0..255; 0: a
+        frozen clip), 'lag': [l = 1 .. T-1] the RMS difference per byte of frames l apart (lag[0]: frame-to-frame motion energy; flat:
+        flicker; zero: a still), 'lag1_q': the 5 / 50 / 95 % quantiles over clips of the lag-1 figure}.  Integer sums in int64 on
+        the host, one float64 expression each."""
+        n, T, Df = s.n, s.frames, s.frame_dim
+        P = T * (T - 1) // 2
+        lag_tot = s.lag_sum.astype(np.int64).sum(axis=0)
+        return {'acd': float(np.mean(s.pair_sum)) / (P * math.sqrt(Df)),
+                'lag': [math.sqrt(int(lag_tot[l]) / (n * (T - l) * Df)) for l in range(1, T)],
+                'lag1_q': [float(v) for v in np.quantile(np.sqrt(s.lag_sum[:, 1].astype(np.int64) / ((T - 1) * Df)), [0.05, 0.5, 0.95])]}
+
+    def report(self, real, fake):
+        """{'real', 'fake': the summaries; 'acd_ratio': acd_fake / acd_real (None when acd_real is 0); 'lag_l1': the mean over lags
+        of |lag_fake - lag_real|; 'motion_precision', 'motion_recall', 'motion_density', 'motion_coverage': KnnMetrics.report on
+        the motion descriptors -- whether the generator produces the frame-to-frame changes the data has}"""
+        if (real.shape[0], real.shape[3], real.pool) != (fake.shape[0], fake.shape[3], fake.pool):
+            raise ValueError('the sets differ in frames, channels or pool')
+        sr, sf = self.summary(real), self.summary(fake)
+        motion = self.knn.report(real.motion, fake.motion)
+        out = {'real': sr, 'fake': sf, 'acd_ratio': sf['acd'] / sr['acd'] if sr['acd'] != 0 else None,
+               'lag_l1': float(np.mean(np.abs(np.asarray(sf['lag']) - np.asarray(sr['lag']))))}
+        out.update({'motion_' + key: motion[key] for key in ('precision', 'recall', 'density', 'coverage')})
+        return out
+
+    def _self_dist(self, x):
+        out = torch.empty(x.n, x.n, dtype=torch.int32, device=self.device)
+        return hl.knn_sqdist(x.desc, x.norms, x.desc, x.norms, out).cpu().numpy().astype(np.int64)
+
+    def grid_report(self, s, K):
+        """s holds K^2 clips in content-major order: clip c K + m has content code c and motion path m.  From the exact K^2 x K^2
+        distance matrices of the whole-clip descriptors (appearance) and of the motion descriptors, the means over the ordered
+        pairs (same content, other motion), (other content, same motion), (neither), and their ratios (None over a zero):
+        content_ratio = appearance same_content / neither (small: the content code sets the appearance), motion_leak = appearance
+        same_motion / neither (near 1: the motion path does not), motion_ratio = motion same_motion / neither (small: the path sets
+        the motion whatever the content), content_leak = motion same_content / neither (near 1: the content code does not).
+        'appearance_dist' and 'motion_dist' are the two matrices (int64, host)."""
+        if K < 2 or s.n != K * K:
+            raise ValueError('a K x K grid (K >= 2) holds K^2 clips, got K = %d and %d clips' % (K, s.n))
+        idx = np.arange(K * K)
+        c, m = idx // K, idx % K
+        same_c, same_m = c[:, None] == c[None, :], m[:, None] == m[None, :]
+        masks = {'same_content': same_c & ~same_m, 'same_motion': ~same_c & same_m, 'neither': ~same_c & ~same_m}
+        means = lambda dist: {key: int(dist[mask].sum()) / int(mask.sum()) for key, mask in masks.items()}
+        app_dist, mot_dist = self._self_dist(s.clips), self._self_dist(s.motion)
+        app, mot = means(app_dist), means(mot_dist)
+        ratio = lambda a, b: a / b if b != 0 else None
+        return {'content_ratio': ratio(app['same_content'], app['neither']), 'motion_leak': ratio(app['same_motion'], app['neither']),
+                'motion_ratio': ratio(mot['same_motion'], mot['neither']), 'content_leak': ratio(mot['same_content'], mot['neither']),
+                'appearance_means': app, 'motion_means': mot, 'appearance_dist': app_dist, 'motion_dist': mot_dist}
