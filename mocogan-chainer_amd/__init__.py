@@ -2,6 +2,7 @@
 
 ``csrc/``      hand-written HIP kernels for gfx950 + the C ABI declared in ``include/mocogan_hip.h``
 ``hiplib.py``  ctypes binding of ``lib/libmocogan_hip.so`` (raw device pointers, current HIP stream)
+``tiles.py``   which GEMM tile a conv launch takes: candidate rules, the tile table, the shipped lists, the tuning loop (no torch)
 ``layout.py``  reference (Chainer) layout <-> device layout of activations and parameters
 ``nets.py``    ImageGenerator / ImageDiscriminator / VideoDiscriminator on those kernels
 ``step.py``    one training iteration (losses, hand-scheduled backward, Adam) + data-parallel exchange

@@ -5,13 +5,14 @@ device pointers to a hand-written gfx950 kernel.  There is no fallback: if the l
 missing or a status is non-zero this module raises.
 """
 import ctypes as C
-import json
 import os
-import warnings
 
 import torch
 
+from . import tiles
 from .build import lib_path
+from .tiles import (PREC_F32, PREC_BF16, PREC_BF16_STORE, PREC_SPLIT, PREC_BF16_Y16, TILE_CANDIDATES, FPROP_SPLIT_CANDIDATES,  # noqa: F401
+                    WGRAD_SPLIT_CANDIDATES, V2_CANDIDATES, DENSE_CANDIDATES, LIVE_CANDIDATES, LIVE_WGRAD_CANDIDATES, split_covers)
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 
@@ -153,24 +154,6 @@ def load():
     return lib
 
 
-_tile_override = 0
-
-
-def set_tile_override(t):
-    """Tests / tuning tools: a default for mcg_conv_geom.tile of every conv call that does not set one itself
-    (0 = none).  Lives here, in the caller: the library has no process-global state."""
-    global _tile_override
-    _tile_override = int(t)
-
-
-def _with_override(g):
-    if not _tile_override or g.tile:
-        return g
-    gg = ConvGeom.from_buffer_copy(g)
-    gg.tile = _tile_override
-    return gg
-
-
 _SYNC_EVERY_CALL = os.environ.get("MCG_SYNC", "0") == "1"     # debugging aid: serialise host and device
 
 
@@ -202,10 +185,6 @@ def _dense(t):
     return t
 
 
-PREC_F32, PREC_BF16, PREC_BF16_STORE, PREC_SPLIT, PREC_BF16_Y16 = 0, 1, 2, 3, 4
-# 'bf16': bf16 MFMA on fp32 tensors (rounded in the kernel); 'bf16s': bf16 MFMA on operands that are bf16 in memory;
-# 'f32x3': fp32 values as three bf16 terms (split_planes), six bf16 products per fp32 product -- fp32 results on the bf16 pipe
-# 'bf16y': as 'bf16' with the y-side tensor bf16 in memory (x, w fp32): the clip-side layers of bf16 networks (wgrad, dgrad)
 PRECISIONS = {"f32": PREC_F32, "fp32": PREC_F32, "bf16": PREC_BF16, "bf16s": PREC_BF16_STORE, "f32x3": PREC_SPLIT, "bf16y": PREC_BF16_Y16,
               PREC_F32: PREC_F32, PREC_BF16: PREC_BF16, PREC_BF16_STORE: PREC_BF16_STORE, PREC_SPLIT: PREC_SPLIT,
               PREC_BF16_Y16: PREC_BF16_Y16}
@@ -321,220 +300,12 @@ def _launch(kind, fn, *args):
                   "%s.%s N=%d T=%d H=%d Ci=%d Co=%d" % (_tag, kind, g.N, g.Ti, g.Hi, g.Ci, g.Co))
 
 
-# ------------------------------------------------------------------------------------------
-# per-geometry choice of the GEMM block tile (mcg_conv_geom.tile).  The best of the six candidates
-# depends on how the tile count of a launch divides over the 256 CUs and, for dgrad, on how many blocks
-# skip dead temporal taps -- the library's closed-form heuristic misses by up to 20 % on some layers.
-# With autotune on, the first launch of each (pass, geometry) times every candidate once on scratch
-# tensors and the winner is used from then on.  Off by default (tests, parity runs): bench.py, train.py
-# and generate_samples.py switch it on.
-# ------------------------------------------------------------------------------------------
-TILE_CANDIDATES = (0, 101, 102, 103, 201, 202, 203)     # (the long tiles 4 = 256x64 and 5 = 64x256 exist, but when they
-                                                        # win the isolated timing they lose inside the iteration: measured)
-FPROP_SPLIT_CANDIDATES = (1103, 1203, 1202, 2103, 2203, 2202)     # 2- / 4-way split-K: only when few tiles (see _tuned)
-WGRAD_SPLIT_CANDIDATES = (2007, 2008, 2010, 1010)      # LDS-DMA weight gradient with half / twice the pixel splits (few-tile layers)
-V2_CANDIDATES = (7, 8, 10)                              # gemm_bf16_v2_kernel (bf16-stored / split / fp32 operands): 256x128 / 256x256 (wgrad 128x256 / 256x256) one block per CU; 10 = 128x128, two blocks per CU
-DENSE_CANDIDATES = (17, 20)                             # MCG_PREC_SPLIT only: tiles 7 / 10 with the dense LDS form (no padding-plane slots; the library
-                                                        # refuses it where a triple of K-steps would straddle a tap: channels along the sum not a multiple of 64)
-LIVE_CANDIDATES = (27, 40, 1027, 2027, 1040, 2040)       # MCG_PREC_SPLIT forward only: 17 / 20 with position-major rows -- K-steps of filter taps that read zero padding for every row
-                                                        # of a tile are skipped; + 1000 / + 2000: the tiles cut into blocks of equal LIVE work, one / two per resident slot (no epilogue)
-LIVE_WGRAD_CANDIDATES = (27, 28, 1027, 2027, 1028, 2028)     # MCG_PREC_SPLIT weight gradient: 128x256/3 dense / 256x256/2 padded with a position-major pixel axis -- advances whose position
-                                                        # reads only padding for the column tile's taps are skipped; needs N * To a multiple of 64 / 16 (the library refuses otherwise)
-_autotune = False
-_tile_cache = {}
-
-
-_PRETUNED = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_tiles_mi355x.json')
-# ... and the 'f32x3' launches of that table which take the DENSE LDS form instead (tile codes 17 / 20 in place of the table's
-# padded 7 / 8 / 9 / 10): [[key, dense code], ...], each measured faster than its padded entry by more than the padded form's own
-# spread (tools/ab_dense_split.py, profiles/dense_split_notes.md).  A list of its own, applied by set_autotune(True): the main
-# table and use_pretuned_table() stay the padded reference that the production-batch parity test pins against float64.
-_PRETUNED_DENSE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'dense_tiles_mi355x.json')
-# ... and the forward launches among them which take position-major rows and live K-steps (LIVE_CANDIDATES), measured the same way
-# (tools/ab_live_steps.py, profiles/live_steps_notes.md); applied on top of the dense list where a training step is built with the
-# tuner on (step.TrainStep -> use_live_list): set_autotune()'s table stays the shipped one with the dense entries
-_PRETUNED_LIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'live_tiles_mi355x.json')
-
-
-def set_autotune(on, use_pretuned=True):
-    """on: time the tile candidates at the first launch of every (pass, geometry) not known yet.  use_pretuned: start
-    from the table shipped with the package -- the choices this tuner made on an MI355X for the reference's layer
-    geometries at batch 32 per GPU (tuned_tiles_mi355x.json); anything else is still tuned on first use."""
-    global _autotune
-    _autotune = bool(on)
-    if use_pretuned:
-        # tuner off (train.py --autotune 0): the tile heuristic replaces the table's tile codes, but WHICH FORM a launch of an
-        # 'f32x3' network takes (split on the bf16 pipe / fp32 MFMA) has no heuristic -- those entries are loaded either way,
-        # otherwise such a network would silently run every GEMM on the fp32 kernels (round 4's advice)
-        use_pretuned_table(only_split=not on)
-        if on:
-            use_dense_list()
-
-
-def autotune_on():
-    return _autotune
-
-
-def _merge_table(entries, overwrite, only_split=False):
-    """[[key, tile code], ...] (save_tile_choices' form) into the table; overwrite: an entry replaces the one the table holds"""
-    for k, v in entries:
-        if overwrite:
-            _tile_cache[tuple(k)] = int(v)
-        elif not only_split or str(k[0]).startswith('split-'):
-            _tile_cache.setdefault(tuple(k), int(v))
-
-
-def use_pretuned_table(only_split=False):
-    """Load the shipped table WITHOUT switching the tuner on: what the sampling path reads (conv_dgrad_relu's tile codes, the split /
-    fp32 decisions of 'f32x3'); launches that tune ignore tile codes while the tuner is off, so nothing else changes."""
-    if os.path.exists(_PRETUNED) and os.environ.get('MCG_NO_PRETUNED') != '1':
-        with open(_PRETUNED) as f:
-            _merge_table(json.load(f), overwrite=False, only_split=only_split)
-
-
-def use_dense_list():
-    """Move the launches of dense_tiles_mi355x.json to their dense codes -- where the table holds the SHIPPED padded code for
-    them (a choice loaded from elsewhere, or tuned in this process, stays).  Part of set_autotune(True) with the shipped table;
-    MCG_DENSE_SPLIT=0 keeps the padded codes (A/B timing)."""
-    if not (os.path.exists(_PRETUNED) and os.path.exists(_PRETUNED_DENSE)) or os.environ.get('MCG_DENSE_SPLIT', '1') == '0':
-        return
-    with open(_PRETUNED) as f:
-        shipped = {tuple(k): int(v) for k, v in json.load(f)}
-    with open(_PRETUNED_DENSE) as f:
-        for k, v in json.load(f):
-            if _tile_cache.get(tuple(k), -1) == shipped.get(tuple(k)):
-                _tile_cache[tuple(k)] = int(v)
-
-
-def _read_list(path):
-    if not os.path.exists(path):
-        return {}
-    with open(path) as f:
-        return {tuple(k): int(v) for k, v in json.load(f)}
-
-
-def live_list(path=None):
-    """{key: code} of live_tiles_mi355x.json (or of `path`), checked: forward / weight-gradient launches of the split form, codes of LIVE_CANDIDATES / LIVE_WGRAD_CANDIDATES"""
-    entries = _read_list(path or _PRETUNED_LIVE)
-    for k, v in entries.items():
-        if k[9] != PREC_SPLIT or not ((k[0] == 'fprop' and v in LIVE_CANDIDATES) or (k[0] == 'wgrad' and v in LIVE_WGRAD_CANDIDATES)):
-            raise ValueError("not a live-steps entry: %r -> %r" % (k, v))
-    return entries
-
-
-def use_live_list(path=None):
-    """Move the launches of live_tiles_mi355x.json to their position-major codes -- where the table still holds the shipped code or
-    the dense list's code for them.  Called by step.TrainStep when the tuner is on (bench.py, train.py); set_autotune() does not;
-    MCG_LIVE_STEPS=0 leaves the table as it is (A/B timing).  Returns the number of launches moved."""
-    if not os.path.exists(_PRETUNED) or os.environ.get('MCG_LIVE_STEPS', '1') == '0':
-        return 0
-    shipped, dense = _read_list(_PRETUNED), _read_list(_PRETUNED_DENSE)
-    moved = 0
-    for k, v in live_list(path).items():
-        if k in shipped and _tile_cache.get(k, -1) in (shipped[k], dense.get(k, shipped[k])):
-            _tile_cache[k] = v
-            moved += 1
-    return moved
-
-
-def reset_tuning():
-    """Back to the state of a fresh import: tuner off, no cached tile choices, no tile override.  (tests/conftest.py calls this
-    before every test module so that no module inherits a timing-dependent tile table from an earlier one; train.main() and
-    bench.py switch the tuner on for their own process.)"""
-    global _autotune, _tile_override
-    _autotune = False
-    _tile_override = 0
-    _tile_cache.clear()
-
-
-def tile_choices():
-    """{(pass, geometry...): tile code} chosen so far (for logs / DESIGN.md tables)."""
-    return dict(_tile_cache)
-
-
-def save_tile_choices(path):
-    """Persist the tuned choices (JSON) so that a later process -- or a profiler pass that must not see the
-    tuning launches -- can start from them."""
-    with open(path, 'w') as f:
-        json.dump([[list(k), v] for k, v in _tile_cache.items()], f)
-
-
-def load_tile_choices(path):
-    with open(path) as f:
-        _merge_table(json.load(f), overwrite=True)
-
-
-def replace_tile_choices(entries):
-    """the table becomes exactly `entries` ([[key, tile code], ...]): every data-parallel rank takes rank 0's choices"""
-    _tile_cache.clear()
-    _merge_table(entries, overwrite=True)
-
-
 def with_precision(g, precision):
     """a copy of the geometry for another operand form of the same layer (its tile is chosen afresh)"""
     h = ConvGeom.from_buffer_copy(g)
     h.precision = PRECISIONS[precision]
     h.tile = 0
     return h
-
-
-def split_covers(kind, g):
-    """does the MCG_PREC_SPLIT form of this pass exist for the geometry (the library's own condition, restated for callers)?
-    kind 'fprop': the sum runs over Ci; 'dgrad': over Co, and the LDS-DMA input-gradient tiles need >= 64 output columns;
-    'wgrad': the sum runs over pixels, x and y both in the split layout."""
-    def p2(c, lo):
-        return c >= lo and c & (c - 1) == 0
-    x_el = max((g.N - 1) * g.x_stride0, 0) + g.Ti * g.Hi * g.Wi * g.Ci if not g.x_perm_n else None
-    y_el = g.N * g.To * g.Ho * g.Wo * g.Co
-    w_el = g.Co * g.kt * 16 * g.Ci
-    if w_el * 8 >= 1 << 31:
-        return False
-    if kind == 'fprop':
-        return p2(g.Ci, 16) and x_el is not None and x_el * 8 < 1 << 31
-    if kind == 'wgrad':                                             # both operands split; the LDS-DMA weight-gradient tiles' own limits
-        return (g.Co >= 128 and g.Co % 64 == 0 and p2(g.Ci, 64) and x_el is not None and x_el * 8 < 1 << 31 and y_el * 8 < 1 << 31
-                and (y_el // g.Co) % 16 == 0)
-    return p2(g.Co, 16) and p2(g.Ci, 64) and y_el * 8 < 1 << 31
-
-
-def split_decided(kind, g):
-    """True when a launch of this pass and geometry is KNOWN to take the split form (MCG_SPLIT=always, or the table says so): the
-    producers of its operands may then write the split layout only.  False while undecided."""
-    if not split_covers(kind, g):
-        return False
-    mode = os.environ.get('MCG_SPLIT', 'auto')
-    if mode != 'auto':
-        return mode == 'always'
-    return _tile_cache.get(_geom_key('split-' + kind, g)) == 1
-
-
-_warned_undecided_split = False
-
-
-def split_pays(kind, g, run_plain, run_split):
-    """Which of the two forms of a launch is faster for this geometry -- the fp32-MFMA kernels on fp32 operands (run_plain) or the
-    split form on the bf16 pipe (run_split, INCLUDING whatever it takes to produce the split operands)?  Timed once per (pass,
-    geometry) like the tile candidates and kept in the same table (key 'split-<pass>', value 1 = split); MCG_SPLIT=always / never
-    overrides (tests, A/B timing).  Both forms write the same output; the caller launches the winner afterwards."""
-    mode = os.environ.get('MCG_SPLIT', 'auto')
-    if mode != 'auto':
-        return mode == 'always'
-    key = _geom_key('split-' + kind, g)
-    c = _tile_cache.get(key)
-    if c is None and not _autotune:
-        # tuner off (tests, train.py --autotune 0): nothing is timed -- the table's entries, else the fp32 form.
-        # (Under data parallelism per-rank timing could also leave the ranks on different forms.)
-        global _warned_undecided_split
-        if not _warned_undecided_split:
-            _warned_undecided_split = True
-            warnings.warn("precision 'f32x3': the tile tuner is off and the table holds no decision for %s N=%d T=%d H=%d Ci=%d Co=%d -- "
-                          "this launch (and every other undecided one) runs the fp32-MFMA form; hiplib.set_autotune(True), "
-                          "MCG_SPLIT=always or a loaded tile table decide it" % (kind, g.N, g.Ti, g.Hi, g.Ci, g.Co))
-        return False
-    if c is None:
-        plain_ms = _best_ms(run_plain)
-        _tile_cache[key] = c = int(_best_ms(run_split) < 0.97 * plain_ms)
-    return bool(c)
 
 
 _PASS = {"fprop": 0, "dgrad": 1, "wgrad": 2}
@@ -552,73 +323,25 @@ def dense_split_chunk(kind, g):
     return int(load().mcg_conv_dense_split_chunk(C.byref(g), _PASS[kind]))
 
 
-def _geom_key(kind, g, extra=()):
-    return (kind, g.N, g.Ti, g.Hi, g.Wi, g.Ci, g.Co, g.kt, g.x_perm_n, g.precision) + tuple(extra)
+# ------------------------------------------------------------------------------------------
+# which tile a conv launch takes: tiles.py holds the candidate rules, the table, the shipped lists and the timing loop;
+# here are its public names (one table per process); _measure below is the measurement it is handed
+# ------------------------------------------------------------------------------------------
+_table = tiles.table
+set_autotune, autotune_on, reset_tuning, set_tile_override = _table.set_autotune, _table.autotune_on, _table.reset, _table.set_override
+use_pretuned_table, use_dense_list, use_live_list = _table.use_pretuned, _table.use_dense, _table.use_live
+tile_choices, save_tile_choices, load_tile_choices, replace_tile_choices = _table.as_dict, _table.save, _table.load, _table.replace
+table_tile, split_decided, _with_override = _table.tile, _table.split_decided, _table.with_override
 
 
-def _tuned(kind, g, extra, out_side, run_on):
-    """Returns a copy of g with .tile set to the fastest candidate.  run_on(geom, scratch) launches the pass
-    with its OUTPUT directed to `scratch` (extent of the geometry's `out_side`), so tuning never touches
-    the caller's output or accumulators."""
-    if not _autotune or g.tile:
-        return g
-    key = _geom_key(kind, g, extra)
-    code = _tile_cache.get(key)
-    if code is None:
-        best, code = None, 0
-        gg = ConvGeom.from_buffer_copy(g)
-        scratch = _scratch_like(g, out_side)
-        cands = TILE_CANDIDATES
-        if (kind == "dgrad" and 4 < g.Ci <= 64) or (kind == "fprop" and g.Co <= 64 and g.Ci > 4):
-            cands = cands + (4,)                                # 256 x 64: the widest tile a 64-column output admits
-        if kind == "wgrad" and g.Ci == 4:
-            cands = cands + (6,)                                # patch-in-LDS kernel (also what tile 0 selects when it applies)
-        out_elems = g.N * g.To * g.Ho * g.Wo * g.Co if kind == "fprop" else g.N * g.Ti * g.Hi * g.Wi * g.Ci
-        if kind in ("fprop", "dgrad") and g.Ci > 4 and out_elems <= (1 << (23 if kind == "fprop" else 25)):
-            cands = cands + FPROP_SPLIT_CANDIDATES          # <= 1024 tiles of 64x64: K splits can fill the CUs
-        if g.precision == PREC_BF16_STORE and g.Ci >= 64 and g.Co >= 64:
-            # the LDS-DMA kernels (the library refuses what they do not cover).  fp32 networks can run them too (tile codes
-            # 7 / 8 by request), but measured on the MI355X they do not beat the register-staged fp32 kernels: 110-127
-            # against 128-134 TFLOP/s on the big layers, and one 256-row block per CU quantises badly at batch 32
-            if not (kind == "dgrad" and g.Ci == 64):        # (64 output columns per parity class: the 256x64 tile never wins)
-                cands = cands + V2_CANDIDATES
-                if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
-                    cands = cands + WGRAD_SPLIT_CANDIDATES
-            else:
-                cands = cands + (10,)                       # ... but 256x64 with two buffers lets two blocks share a CU
-                if g.Ho == 16 and g.Wo == 16:
-                    cands = cands + (9,)                    # ... and the patch-stationary kernel, four classes per block, is made for it
-        if g.precision == PREC_F32 and g.Ci >= 64 and g.Co >= 64 and kind != "dgrad" or (g.precision == PREC_F32 and kind == "dgrad" and g.Ci >= 128 and g.Co >= 64):
-            cands = cands + (10,)                           # the LDS-DMA kernel on fp32 operands, 128x128, two blocks per CU
-        if g.precision == PREC_SPLIT:
-            # (the LDS-DMA kernels are the only ones that multiply split operands; one 256-row block per CU: late layers need K splits)
-            cands = V2_CANDIDATES + DENSE_CANDIDATES
-            if kind in ("fprop", "dgrad") and out_elems <= (1 << 25):
-                cands = cands + (1007, 2007, 1010, 2010, 1017, 2017, 1020, 2020)
-            if kind == "fprop":
-                cands = cands + LIVE_CANDIDATES
-            if kind == "wgrad":
-                cands = cands + LIVE_WGRAD_CANDIDATES
-            if kind == "wgrad" and g.Co * g.kt * 16 * g.Ci <= (1 << 21):
-                # few (Co, tap x Ci) tiles -- the 2-D layers: many pixel splits then add onto the same small dw with float
-                # atomics; + 2000 halves / + 1000 doubles the number of splits (round 6)
-                cands = cands + WGRAD_SPLIT_CANDIDATES + (2017, 2020, 1020)
-            if kind == "dgrad" and g.Ci == 64 and g.Ho == 16 and g.Wo == 16:
-                cands = cands + (9,)                        # the patch-stationary kernel (four parity classes per block)
-        for cand in cands:
-            gg.tile = cand
-            try:
-                ms = _best_ms(lambda: run_on(gg, scratch))      # (the warm-up rejects impossible candidates)
-            except McgError:
-                continue
-            if best is None or ms < best:
-                best, code = ms, cand
-        _tile_cache[key] = code
-    if not code:
-        return g
-    gg = ConvGeom.from_buffer_copy(g)
-    gg.tile = code
-    return gg
+def live_list(path=None):
+    """{key: code} of live_tiles_mi355x.json (or of `path`), checked (tiles.live_list)"""
+    return tiles.live_list(path or _table.live)
+
+
+def split_pays(kind, g, run_plain, run_split):
+    """_table.split_pays with the tuners' timing: does the split form of this launch beat the fp32 form?  Timed once per geometry."""
+    return _table.split_pays(kind, g, run_plain, run_split, _best_ms)
 
 
 def _scratch_like(g, which):
@@ -726,50 +449,56 @@ def fprop_tile(g, x, w, bias):
     """the tile code the PLAIN conv_fprop uses for this geometry (tuned now if it has to be): codes >= 1000 split K, and a
     split launch can neither carry an epilogue nor write a bf16 output -- callers that want either ask before they allocate.
     (bf16 networks: the fused / bf16-output form is tuned separately and only over the tiles that admit it.)"""
-    if _autotune and not g.tile:
+    if _table.autotune and not g.tile:
         probe = torch.empty(0, device='cuda')
-        g = _tuned("fprop", g, _ep_key(g, None, probe), 'y', _tune_run("fprop", g, x, w, bias, probe, None))
+        g = _table.tuned("fprop", g, tiles.ep_key(g, None, False), _measure("fprop", g, x, w, bias, probe))
     return _with_override(g).tile
 
 
 def dgrad_tile(g, y, w, bias, act=ACT_NONE, accumulate=False):
-    if _autotune and not g.tile:
+    if _table.autotune and not g.tile:
         probe = torch.empty(0, device='cuda')
-        g = _tuned("dgrad", g, (act, int(accumulate)) + _ep_key(g, None, probe), 'x', _tune_run("dgrad", g, y, w, bias, probe, None, act, accumulate))
+        g = _table.tuned("dgrad", g, (act, int(accumulate)) + tiles.ep_key(g, None, False), _measure("dgrad", g, y, w, bias, probe, None, act, accumulate))
     return _with_override(g).tile
 
 
-def _ep_key(g, ep, out):
-    """bf16 networks tune a geometry per launch FORM: a fused epilogue / a bf16 output change which tile wins (the LDS-DMA
-    kernels' row-wise epilogue costs differently from the register-staged kernels'), so the form is part of the key and the
-    candidates are timed in it.  fp32 geometries keep their single key (and the shipped table)."""
-    if g.precision != PREC_BF16_STORE:
-        return ()
-    return ('ep', int(ep.sums) if ep is not None else 0, int(bool(ep.mask_in)) if ep is not None else 0, int(out.dtype == torch.bfloat16))
+def _measure(kind, g, a, b, bias=None, out_like=None, ep=None, act=ACT_NONE, accumulate=False):
+    """The measurement _table.tuned is handed: measure(geom) -> ms of the caller's form of the launch (epilogue, output type) with
+    that geometry's tile code, None when the library refuses it.  The OUTPUT goes to scratch of its extent, allocated at the first
+    candidate: tuning never touches the caller's output or accumulators.  (a, b) = (x, w) forward, (y, w) dgrad, (x, y) wgrad."""
+    scratch = None
 
+    def measure(gg):
+        nonlocal scratch
+        if scratch is None:
+            scratch = _scratch_like(g, {"fprop": 'y', "dgrad": 'x', "wgrad": 'w'}[kind])
 
-def _tune_run(kind, g, a, w, bias, out_like, ep, act=ACT_NONE, accumulate=False):
-    """the launch a tuning candidate is timed with: the caller's form (epilogue, output type) on scratch output"""
-    def run(gg, scratch):
-        out = scratch.view(torch.bfloat16)[:scratch.numel()] if out_like.dtype == torch.bfloat16 else scratch
-        if g.precision == PREC_BF16_STORE and (ep is not None or out_like.dtype == torch.bfloat16) and gg.tile < 1000:
-            e2 = ep if ep is not None else epilogue(out_bf16=True)
-            (_fprop_ex if kind == "fprop" else _dgrad_ex)(gg, a, w, bias, out, e2, split_ok=True)
-        elif out_like.dtype == torch.bfloat16:
-            raise McgError("a split-K tile cannot write a bf16 output")
-        elif kind == "fprop":
-            _fprop(gg, a, w, bias, scratch)
-        else:
-            _dgrad(gg, a, w, bias, scratch, act, accumulate)
-    return run
+        def run():
+            if kind == "wgrad":
+                return _wgrad(gg, a, b, scratch)
+            out = scratch.view(torch.bfloat16)[:scratch.numel()] if out_like.dtype == torch.bfloat16 else scratch
+            if g.precision == PREC_BF16_STORE and (ep is not None or out_like.dtype == torch.bfloat16) and gg.tile < 1000:
+                e2 = ep if ep is not None else epilogue(out_bf16=True)
+                (_fprop_ex if kind == "fprop" else _dgrad_ex)(gg, a, b, bias, out, e2, split_ok=True)
+            elif out_like.dtype == torch.bfloat16:
+                raise McgError("a split-K tile cannot write a bf16 output")
+            elif kind == "fprop":
+                _fprop(gg, a, b, bias, scratch)
+            else:
+                _dgrad(gg, a, b, bias, scratch, act, accumulate)
+        try:
+            return _best_ms(run)                # (the warm-up rejects impossible candidates)
+        except McgError:
+            return None
+    return measure
 
 
 def conv_fprop(g, x, w, bias, y, ep=None, must_fuse=False):
     """ep: a ConvEpilogue to fuse into the launch.  Returns True when it was fused; False when the tile tuned for this
     geometry splits K (partial tiles cannot carry an epilogue) and must_fuse is off: then the PLAIN convolution ran and
     the caller does the epilogue's work with the stand-alone passes.  must_fuse drops the split instead."""
-    if _autotune and not g.tile:
-        g = _tuned("fprop", g, _ep_key(g, ep, y), 'y', _tune_run("fprop", g, x, w, bias, y, ep))   # x, w are only read
+    if _table.autotune and not g.tile:
+        g = _table.tuned("fprop", g, tiles.ep_key(g, ep, y.dtype == torch.bfloat16), _measure("fprop", g, x, w, bias, y, ep))   # x, w are only read
     if ep is not None and (must_fuse or _with_override(g).tile < 1000):
         _launch("fprop", _fprop_ex, g, x, w, bias, y, ep)
         return True
@@ -780,8 +509,8 @@ def conv_fprop(g, x, w, bias, y, ep=None, must_fuse=False):
 def conv_dgrad(g, y, w, bias, x, act=ACT_NONE, accumulate=False, ep=None, must_fuse=False, tune=True):
     """ep / return value as in conv_fprop (ep needs act == ACT_NONE, no accumulate, dense x).  tune=False: never time candidates
     from this call (the sampling path), whatever set_autotune says."""
-    if _autotune and tune and not g.tile:
-        g = _tuned("dgrad", g, (act, int(accumulate)) + _ep_key(g, ep, x), 'x', _tune_run("dgrad", g, y, w, bias, x, ep, act, accumulate))
+    if _table.autotune and tune and not g.tile:
+        g = _table.tuned("dgrad", g, (act, int(accumulate)) + tiles.ep_key(g, ep, x.dtype == torch.bfloat16), _measure("dgrad", g, y, w, bias, x, ep, act, accumulate))
     if ep is not None and (must_fuse or _with_override(g).tile < 1000):
         assert act == ACT_NONE and not accumulate
         _launch("dgrad", _dgrad_ex, g, y, w, bias, x, ep)
@@ -790,18 +519,13 @@ def conv_dgrad(g, y, w, bias, x, act=ACT_NONE, accumulate=False, ep=None, must_f
     return False
 
 
-def table_tile(kind, g, extra=()):
-    """the tile code the table holds for (pass, geometry, launch form) -- 0 when it holds none.  Never tunes."""
-    return _tile_cache.get(_geom_key(kind, g, extra), 0)
-
-
 def conv_dgrad_relu(g, y, w, bias, x):
     """x = max(conv_transpose(y, w) + bias, 0): the sampling path's deconvolution with test-mode BatchNorm folded into w and bias
     (bn_fold_deconv) and ReLU in the store; x fp32 or bf16.  Takes the tile the table holds for the PLAIN launch of this geometry
     and output type with its split-K part dropped (code % 1000: partial tiles cannot carry an activation), else the library's
     heuristic; the tuner is never run from here."""
     if not g.tile:
-        code = table_tile("dgrad", g, (ACT_NONE, 0) + _ep_key(g, None, x)) % 1000
+        code = table_tile("dgrad", g, (ACT_NONE, 0) + tiles.ep_key(g, None, x.dtype == torch.bfloat16)) % 1000
         if code:
             g = ConvGeom.from_buffer_copy(g)
             g.tile = code
@@ -809,8 +533,8 @@ def conv_dgrad_relu(g, y, w, bias, x):
 
 
 def conv_wgrad(g, x, y, dw):
-    if _autotune and not g.tile:
-        g = _tuned("wgrad", g, (), 'w', lambda gg, out: _wgrad(gg, x, y, out))
+    if _table.autotune and not g.tile:
+        g = _table.tuned("wgrad", g, (), _measure("wgrad", g, x, y))
     _launch("wgrad", _wgrad, g, x, y, dw)
 
 

@@ -312,7 +312,7 @@ class TrainStep:
             for net in (gen, dis_i, dis_v):
                 net.set_precision(precision)
         if hl.autotune_on():
-            # the training step's forward launches that take position-major rows / live K-steps (hiplib.use_live_list: only where the
+            # the training step's forward launches that take position-major rows / live K-steps (hiplib.use_live_list = tiles.table.use_live: only where the
             # table still holds the shipped or the dense code; MCG_LIVE_STEPS=0 leaves it).  set_autotune() itself loads the shipped
             # table and the dense list, nothing else.
             hl.use_live_list()
@@ -761,8 +761,8 @@ def make_models(model='normal', num_labels=6, channel=3, dim_zc=50, dim_zm=10, n
 
 
 def pretune_and_share_tiles(exchange, model, precision, batch, rank, **model_kw):
-    """Data parallel: make every rank run the SAME GEMM tile codes.  With autotune on, a geometry the shipped table does
-    not hold is timed at its first launch -- per rank, so two ranks may keep different winners (results stay identical:
+    """Data parallel: make every rank run the SAME GEMM tile codes.  With autotune on, a geometry the table
+    (tiles.table) does not hold is timed at its first launch -- per rank, so two ranks may keep different winners (results stay identical:
     Adam consumes the all-reduced gradient; but a rank with a slower choice sets the step time).  Here every rank runs ONE
     local iteration (no exchange) on throw-away networks, which tunes whatever is missing, then rank 0's table replaces
     everyone's.  No reference counterpart (the reference is single-device, train.py:87-91)."""

@@ -239,7 +239,7 @@ def test_optimizer_objects_carry_the_reference_hyperparameters():
 
 
 def test_shipped_tile_table_is_well_formed():
-    """mocogan-chainer_amd/tuned_tiles_mi355x.json: [[key, code], ...] with keys as hiplib._geom_key builds them and
+    """mocogan-chainer_amd/tuned_tiles_mi355x.json: [[key, code], ...] with keys as tiles.geom_key builds them and
     codes the C ABI accepts (mcg_conv_geom.tile)."""
     import json
     import os
@@ -258,7 +258,7 @@ def test_shipped_tile_table_is_well_formed():
             assert all(isinstance(v, int) for v in key[1:])
         else:
             base = 12 if kind == 'dgrad' else 10                            # dgrad keys carry (act, accumulate)
-            # bf16-stored geometries (fprop / dgrad) are tuned per launch form: + ('ep', sums, mask, bf16 output)  (hiplib._ep_key)
+            # bf16-stored geometries (fprop / dgrad) are tuned per launch form: + ('ep', sums, mask, bf16 output)  (tiles.ep_key)
             form = 4 if (prec == 2 and kind != 'wgrad') else 0
             assert kind in ('fprop', 'dgrad', 'wgrad') and len(key) == base + form, key
             assert all(isinstance(v, int) for v in key[1:base]) and (not form or (key[base] == 'ep' and all(isinstance(v, int) for v in key[base + 1:]))), key
@@ -314,6 +314,7 @@ def test_split_form_predicates(monkeypatch):
     """hiplib.split_covers / split_decided (host logic of the 'f32x3' networks): which launches have a MCG_PREC_SPLIT form, and when
     a producer may rely on it (MCG_SPLIT=always / never, else the table entry 'split-<pass>' == 1)."""
     import mocogan_chainer_amd.hiplib as hl
+    import mocogan_chainer_amd.tiles as tiles
     wide = hl.make_geom(64, 13, 32, 32, 64, 128, 4)             # D_V dc2 at 64 clips
     clip = hl.make_geom(64, 16, 64, 64, 4, 64, 4, ci_valid=3)   # the 4-channel first layer
     narrow = hl.make_geom(4, 5, 16, 16, 16, 32, 4)
@@ -327,18 +328,18 @@ def test_split_form_predicates(monkeypatch):
     monkeypatch.setenv('MCG_SPLIT', 'never')
     assert not hl.split_decided('fprop', wide)
     monkeypatch.setenv('MCG_SPLIT', 'auto')
-    key = hl._geom_key('split-fprop', wide)
-    old = hl._tile_cache.pop(key, None)
+    key = tiles.geom_key('split-fprop', wide)
+    old = tiles.table.choices.pop(key, None)
     try:
         assert not hl.split_decided('fprop', wide)              # undecided: the producers keep writing fp32
-        hl._tile_cache[key] = 1
+        tiles.table.set(key, 1)
         assert hl.split_decided('fprop', wide)
-        hl._tile_cache[key] = 0
+        tiles.table.set(key, 0)
         assert not hl.split_decided('fprop', wide)
     finally:
-        hl._tile_cache.pop(key, None)
+        tiles.table.choices.pop(key, None)
         if old is not None:
-            hl._tile_cache[key] = old
+            tiles.table.set(key, old)
     g3 = hl.with_precision(wide, 'f32x3')
     assert g3.precision == hl.PREC_SPLIT and g3.tile == 0 and wide.precision == hl.PREC_F32
 

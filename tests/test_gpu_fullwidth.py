@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import ref64
+from mocogan_chainer_amd import tiles
 from oracle import functions as F
 from oracle import net as onet
 from oracle import updater as oupd
@@ -337,7 +338,7 @@ class _Parity:
         self._pending = []
 
     def code(self, kind, g, extra=()):
-        key = self.hl._geom_key(kind, g, extra)
+        key = tiles.geom_key(kind, g, extra)
         self._pending.append(key)
         if key not in self.table:
             if key not in self.missing:
@@ -451,7 +452,7 @@ class _LayerCase:
         xs, wf, _, _ = self.ops(form)
         y = torch.full(self.y_ref.shape, 3.0, device='cuda', dtype=torch.bfloat16 if out16 else torch.float32)
         if code is None:
-            code = P.code("fprop", g, hl._ep_key(g, None, y))
+            code = P.code("fprop", g, tiles.ep_key(g, None, y.dtype == torch.bfloat16))
         hl.conv_fprop(P.geom(g, code), xs, wf, self.b, y)
         P.judge(self.name, "fprop", form, code, y, self.y_ref, FWD_TOL + (BF16_STORE_EPS if out16 else 0), f32_err=self.f32_err("fprop"),
                 note=note or (" (bf16 store)" if out16 else ""))
@@ -462,7 +463,7 @@ class _LayerCase:
         _, _, wd, ys = self.ops(form)
         gx = torch.full(self.x.shape, 7.0, device='cuda', dtype=torch.bfloat16 if out16 else torch.float32)
         if code is None:
-            code = P.code("dgrad", g, (hl.ACT_NONE, 0) + hl._ep_key(g, None, gx))
+            code = P.code("dgrad", g, (hl.ACT_NONE, 0) + tiles.ep_key(g, None, gx.dtype == torch.bfloat16))
         hl.conv_dgrad(P.geom(g, code), ys, wd, None, gx)
         P.judge(self.name, "dgrad", form, code, gx, self.gx_ref, BWD_TOL + (BF16_STORE_EPS if out16 else 0), f32_err=self.f32_err("dgrad"),
                 note=note or (" (bf16 store)" if out16 else ""))
@@ -628,7 +629,7 @@ def test_production_batch_conv_launches_match_float64(pkg, family, batch):
                             if c16 != c32:                          # the bf16 store's tile code, stored in fp32: held to the tight bound
                                 launch(g, form, code=c16, note=" (the bf16 store's code, fp32 store)")
                             groups = 2 if name.startswith("D_") and N == 2 * batch else 1
-                            for key in sorted(k for k in table if k[0] == kind and k[:10] == hl._geom_key(kind, g) and 'ep' in k):
+                            for key in sorted(k for k in table if k[0] == kind and k[:10] == tiles.geom_key(kind, g) and 'ep' in k):
                                 sums, mask, o16 = key[key.index('ep') + 1:]
                                 if sums or mask:
                                     L.epilogue_form(g, kind, sums, mask, bool(o16), groups)
@@ -1258,7 +1259,7 @@ def test_production_batch_relu_store(pkg, layer):
             out = torch.full(ref.shape, -3.0, device='cuda', dtype=dt)
             hl.conv_dgrad_relu(g, gy, w, bias, out)
             rep = ref64.compare(out, ref)
-            code = hl.table_tile("dgrad", g, (hl.ACT_NONE, 0) + hl._ep_key(g, None, out)) % 1000
+            code = hl.table_tile("dgrad", g, (hl.ACT_NONE, 0) + tiles.ep_key(g, None, out.dtype == torch.bfloat16)) % 1000
             print("%s N=%d relu store %s code %d: %s" % (name, N, dt, code, rep))
             _parity_table_row(("relu-store-N%d" % N, name, "dgrad + relu (%s store)" % ("bf16" if dt == torch.bfloat16 else "fp32"), "bf16s", code, "%.2e" % rep.rel, "%.2e" % rep.block))
             assert rep.ok(BWD_TOL + (BF16_STORE_EPS if dt == torch.bfloat16 else 0)), str(rep)

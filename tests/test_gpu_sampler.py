@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from mocogan_chainer_amd import tiles
 from oracle import functions as F
 from oracle import net as onet
 
@@ -197,7 +198,7 @@ def test_dgrad_relu_refusals(hl):
     torch.cuda.synchronize()
     assert float(out.max()) == -3.0 and float(out.min()) == -3.0
     # the table's split-K codes reach the launch without their split part
-    hl._tile_cache[hl._geom_key("dgrad", hl.make_geom(frames, 1, 2 * h, 2 * h, 128, 256, 1), (hl.ACT_NONE, 0))] = 2203
+    tiles.table.set(tiles.geom_key("dgrad", hl.make_geom(frames, 1, 2 * h, 2 * h, 128, 256, 1), (hl.ACT_NONE, 0)), 2203)
     try:
         g0 = hl.make_geom(frames, 1, 2 * h, 2 * h, 128, 256, 1)
         hl.conv_dgrad_relu(g0, yd, wd, bd, out)

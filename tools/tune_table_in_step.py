@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import mocogan_chainer_amd.hiplib as hl            # noqa: E402
 import mocogan_chainer_amd.step as mstep           # noqa: E402
+import mocogan_chainer_amd.tiles as tiles          # noqa: E402
 
 
 def main():
@@ -53,7 +54,7 @@ def main():
 
     for _ in range(6):
         ts.run(x, t)                                    # every geometry gets an entry (pre-tuned or tuned now)
-    cache = hl._tile_cache
+    cache = tiles.table.choices
     # per-key cost of the current choice: one-stream pass with event timing
     ts.set_overlap(False)
     hl.timing_begin()
